@@ -4,10 +4,13 @@
 A step = one pass of the whole 66-node graph over one batch of 256 synthetic 3x224x224 images
 already resident in HBM (per GPU: weak scaling), plus, for N > 1, the RCCL all-gather of the
 [256, 1000] softmax rows (the only collective, BASELINE.json north_star).  Prints one JSON line
-on rank 0 with the roofline of the dominant kernel (the MFMA implicit-GEMM conv) and the CPU
-baseline (the C restatement of the reference's algorithm, timed on this host's cores).
+on rank 0.  A plain run sets up (model, seeded batch, per-layer tile autotune), warms up, times the
+K steps and prints the headline figure; --full adds everything else: the roofline of the dominant
+kernel (the MFMA implicit-GEMM conv) from a per-kernel HIP-event pass, the max-abs sample against
+the oracle, the fp16 line, the batch-1 latency probe and the CPU baseline (the C restatement of
+the reference's algorithm, timed on this host's cores).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 import argparse
@@ -45,6 +48,13 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: this many images per step split over the GPUs (SURVEY §8(d) B=2048)")
     ap.add_argument("--hw", type=int, default=224)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the reporting legs after the timed steps: the per-kernel HIP-event pass (roofline, "
+                         "breakdown, --layers), the max-abs sample vs the oracle, and at N = 1 the fp16 line, the batch-1 "
+                         "latency probe and the CPU baseline (each leg has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned -- the [G, 1000] softmax rows "
+                         "(gathered over the ranks for N > 1) -- as DIR/probs.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU this process may use (affinity and cgroup quota; see usable_cpus)")
@@ -55,9 +65,9 @@ def parse():
                     help="take the N > 1 path (process group, per-step all-gather, max over ranks) even at N = 1: a "
                          "one-rank RCCL communicator runs the product collective on a one-GPU box")
     ap.add_argument("--no-step-timing", action="store_true",
-                    help="skip the per-kernel HIP-event pass (no roofline / breakdown)")
-    ap.add_argument("--layers", action="store_true", help="print per-kernel-step times to stderr")
-    ap.add_argument("--no-b1", action="store_true", help="skip the batch-1 latency probe")
+                    help="--full: skip the per-kernel HIP-event pass (no roofline / breakdown)")
+    ap.add_argument("--layers", action="store_true", help="--full: print per-kernel-step times to stderr")
+    ap.add_argument("--no-b1", action="store_true", help="--full: skip the batch-1 latency probe")
     ap.add_argument("--graph", action="store_true", help="time one HIP-graph replay per step instead of plain launches")
     ap.add_argument("--no-autotune", action="store_true", help="keep the heuristic per-layer conv tiles")
     ap.add_argument("--tune-reps", type=int, default=3, help="timed launches per autotune candidate")
@@ -67,7 +77,7 @@ def parse():
                          "modules' expand1x1 beside their Winograd expand3x3 -- on a side stream (bit-identical; "
                          "71.1 k vs 70.5 k img/s at B = 256); 1: one stream")
     ap.add_argument("--no-f16-line", action="store_true",
-                    help="skip the config-5 fp16 measurement reported under \"f16\" of the f32 line (run at N = 1 "
+                    help="--full: skip the config-5 fp16 measurement reported under \"f16\" of the f32 line (run at N = 1 "
                          "only, like the batch-1 probe and the CPU baseline)")
     ap.add_argument("--no-winograd", action="store_true",
                     help="f32: 3x3 stride-1 convs on the direct kernels only (ORE_LOAD_NO_WINOGRAD)")
@@ -285,6 +295,60 @@ def f16_line(ctx, model_bytes, x, B, args, ref, pos):
     return res
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(dirname, rows):
+    """--dump-outputs: the rows the last timed step returned, as DIR/probs.npy (float32).  Past 64 MB
+    (G > 16 k images) a fixed seeded sample of the rows, in batch order."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    y = np.ascontiguousarray(rows.detach().cpu().numpy(), dtype=np.float32)
+    keep = (DUMP_MAX_BYTES - 4096) // y[0].nbytes  # 4096: room for the .npy header
+    if len(y) > keep:
+        y = y[np.sort(np.random.default_rng(1000).choice(len(y), size=keep, replace=False))]
+    np.save(os.path.join(dirname, "probs.npy"), y)
+
+
+def report_full(result, args, ctx, model_bytes, x, B, dev, world, gathered, sample_idx, x_sample, collective):
+    """--full, after the timed steps: the max-abs sample against the oracle and, at N = 1, the fp16
+    line, the batch-1 latency probe and the CPU baseline, added to the result line."""
+    import numpy as np
+    import torch
+    import oracle
+    f16 = args.precision == "f16"
+    # max-abs vs the CPU restatement on a bounded sample: the fixture images at their global positions as
+    # they come out of the timed steps (for N > 1 out of the gathered rows, i.e. through the collective)
+    torch.cuda.synchronize()
+    got = gathered[sample_idx].cpu().numpy()
+    ref = oracle.Model(model_bytes).run(x_sample, 1000)
+    per_img = np.abs(got - ref).max(axis=1)
+    result["max_abs_diff_vs_cpu"] = float(per_img.max())
+    result["max_abs_per_image"] = [float(v) for v in per_img]
+    result["top1_agrees_with_cpu"] = bool((got.argmax(1) == ref.argmax(1)).all())
+    result["max_abs_sample"] = (f"{len(sample_idx)} images at global positions {sample_idx} of the timed batch"
+                                f"{' (gathered over ' + collective + ')' if collective else ''}: "
+                                f"{'the strict-parity fixture (zoo image + 15 U(-50,50) draws; zoo-calibrated model, softmax max 0.074 on the zoo image)' if args.hw == 224 else 'seeded U(-50,50) images'}"
+                                f" vs the oracle (C restatement of the reference, f32) run live on this host")
+    result["max_abs_comparability"] = ("zoo-calibrated model (conv10 x ZOO_LOGIT_GAIN) since round 5; rounds 1-4 "
+                                       "sampled the uncalibrated He-normal model, whose peakier logits put the "
+                                       "same f32 roundings at up to ~1e-5 (DESIGN.md 5.1): not comparable across "
+                                       "that change")
+    # the reporting legs run at N = 1 only (SURVEY §8(d): the CPU baseline on rank 0 at N = 1), so no
+    # rank waits on the others' collectives meanwhile
+    if world == 1:
+        if not f16 and not args.no_f16_line:
+            result["f16"] = f16_line(ctx, model_bytes, x, B, args, ref, sample_idx)
+        if not args.no_b1:
+            result["b1_latency_ms"] = b1_latency(model_bytes, args.hw, dev, args.precision,
+                                                 winograd=not args.no_winograd)
+        if not args.no_cpu_baseline:
+            usable, cpu_info = usable_cpus()
+            threads = args.cpu_threads or usable
+            result["cpu_baseline"] = cpu_baseline(model_bytes, args.hw, threads)
+            result["cpu_baseline"].update(cpu_info, usable_cpus=usable)
+
+
 def main():
     args = parse()
     import numpy as np
@@ -401,12 +465,14 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if gloo else f"cuda:{dev}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # the last timed step's rows, before any other pass writes `out` again
+        dump_outputs(args.dump_outputs, gathered)
 
     # per-kernel durations (roofline, breakdown): the same K steps again with a HIP event on the
     # launch stream between consecutive kernels (ore_model_enable_timing).  A separate pass because
     # the events and the per-step read-back add ~0.12 ms of gaps per step (measured 5.22 vs
     # 5.10 ms) that are not part of the workload; the kernels inside are the same launches.
-    timing = not args.no_step_timing
+    timing = args.full and not args.no_step_timing
     infos = model.steps() if timing else []
     per_step_ms = np.zeros(len(infos)) if timing else None
     if timing:
@@ -516,37 +582,9 @@ def main():
                     gbs = info["bytes"] / (ms * 1e-3) / 1e9
                     print(f"{info['name']:24s} {info['op']:18s} {1000 * ms:9.1f} us {tf:7.1f} TF/s {gbs:8.1f} GB/s",
                           file=sys.stderr)
-        # max-abs vs the CPU restatement on a bounded sample: the fixture images at their global positions as
-        # they come out of the timed steps (for N > 1 out of the gathered rows, i.e. through the collective)
-        import oracle
-        torch.cuda.synchronize()
-        got = gathered[sample_idx].cpu().numpy()
-        ref = oracle.Model(model_bytes).run(x_sample, 1000)
-        per_img = np.abs(got - ref).max(axis=1)
-        result["max_abs_diff_vs_cpu"] = float(per_img.max())
-        result["max_abs_per_image"] = [float(v) for v in per_img]
-        result["top1_agrees_with_cpu"] = bool((got.argmax(1) == ref.argmax(1)).all())
-        result["max_abs_sample"] = (f"{len(sample_idx)} images at global positions {sample_idx} of the timed batch"
-                                    f"{' (gathered over ' + ('gloo' if gloo else 'RCCL') + ')' if use_dist else ''}: "
-                                    f"{'the strict-parity fixture (zoo image + 15 U(-50,50) draws; zoo-calibrated model, softmax max 0.074 on the zoo image)' if args.hw == 224 else 'seeded U(-50,50) images'}"
-                                    f" vs the oracle (C restatement of the reference, f32) run live on this host")
-        result["max_abs_comparability"] = ("zoo-calibrated model (conv10 x ZOO_LOGIT_GAIN) since round 5; rounds 1-4 "
-                                           "sampled the uncalibrated He-normal model, whose peakier logits put the "
-                                           "same f32 roundings at up to ~1e-5 (DESIGN.md 5.1): not comparable across "
-                                           "that change")
-        # the reporting legs run at N = 1 only (the CPU baseline on rank 0 at N = 1), so no
-        # rank waits on the others' collectives meanwhile
-        if world == 1:
-            if not f16 and not args.no_f16_line:
-                result["f16"] = f16_line(ctx, model_bytes, x, B, args, ref, sample_idx)
-            if not args.no_b1:
-                result["b1_latency_ms"] = b1_latency(model_bytes, args.hw, dev, args.precision,
-                                                     winograd=not args.no_winograd)
-            if not args.no_cpu_baseline:
-                usable, cpu_info = usable_cpus()
-                threads = args.cpu_threads or usable
-                result["cpu_baseline"] = cpu_baseline(model_bytes, args.hw, threads)
-                result["cpu_baseline"].update(cpu_info, usable_cpus=usable)
+        if args.full:
+            report_full(result, args, ctx, model_bytes, x, B, dev, world, gathered, sample_idx, x_sample,
+                        "gloo" if gloo else "RCCL" if use_dist else None)
         print(json.dumps(result), flush=True)
 
     model.close()

@@ -228,7 +228,7 @@ def test_bench_world1_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
            "--gpus", "1", "--dist", "--dist-backend", "nccl", "--steps", "3", "--warmup", "1", "--batch", "64",
-           "--no-cpu-baseline", "--no-b1", "--no-f16-line", "--no-step-timing"]
+           "--full", "--no-cpu-baseline", "--no-b1", "--no-f16-line", "--no-step-timing"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -260,7 +260,7 @@ def test_bench_world2_gloo(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--dist-backend", "gloo",
-           "--no-cpu-baseline", "--no-b1", "--no-f16-line", "--no-step-timing"] + extra
+           "--full", "--no-cpu-baseline", "--no-b1", "--no-f16-line", "--no-step-timing"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -11,7 +11,7 @@ mkdir -p "$ROOT/gpurun_out"
 : > "$OUT"
 for name in "$@"; do
   if [ "$name" = cur ]; then lib="$ROOT/onnx-rusty-inference-engine_amd/lib/libore.so"; else lib="$ROOT/onnx-rusty-inference-engine_amd/lib/exp/libore_$name.so"; fi
-  ORE_LIB="$lib" timeout -k 10 240 python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-b1 --no-f16-line \
+  ORE_LIB="$lib" timeout -k 10 240 python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-b1 --no-f16-line \
     --no-step-timing ${BENCH_ARGS:-} > "$OUT.tmp" 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then cat "$OUT.tmp" >> "$OUT"; echo "[$name] rc=$rc" >> "$OUT"; tail -5 "$OUT"; exit $rc; fi

@@ -20,7 +20,7 @@ if [ -n "${TESTS:-}" ]; then
   tail -2 "$OUT/${TAG}_tests.log"
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 600 python3 bench.py ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || {
+  timeout -k 10 600 python3 bench.py --full ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || {
     tail -20 "$OUT/${TAG}_bench.err"; exit 1; }
   cat "$OUT/${TAG}_bench.json"
 fi

@@ -25,19 +25,19 @@ if has tests; then
   if fatal $rc || [ $rc -gt 1 ]; then exit $rc; fi
 fi
 if has bench; then
-  timeout -k 10 600 python3 bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+  timeout -k 10 600 python3 bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
   rc=$?; echo "bench rc=$rc"; cat "$OUT/bench_$TAG.json"; tail -5 "$OUT/bench_$TAG.err"
   if [ $rc -ne 0 ]; then exit $rc; fi
 fi
 if has bench16; then
-  timeout -k 10 600 python3 bench.py --precision f16 --no-cpu-baseline > "$OUT/bench16_$TAG.json" 2> "$OUT/bench16_$TAG.err"
+  timeout -k 10 600 python3 bench.py --full --precision f16 --no-cpu-baseline > "$OUT/bench16_$TAG.json" 2> "$OUT/bench16_$TAG.err"
   rc=$?; echo "bench16 rc=$rc"; cat "$OUT/bench16_$TAG.json"; tail -5 "$OUT/bench16_$TAG.err"
   if [ $rc -ne 0 ]; then exit $rc; fi
 fi
 if has prof; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o run -- \
-    python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-b1 --no-f16-line > "$OUT/prof_bench_$TAG.json" 2> "$OUT/prof_$TAG.err"
+    python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-b1 --no-f16-line > "$OUT/prof_bench_$TAG.json" 2> "$OUT/prof_$TAG.err"
   rc=$?; echo "prof rc=$rc"; cat "$OUT/prof_bench_$TAG.json"
   find "$OUT/prof_$TAG" -name "*stats*" | head
   if [ $rc -ne 0 ]; then tail -20 "$OUT/prof_$TAG.err"; exit $rc; fi
