@@ -162,6 +162,21 @@ ore_status ore_dropout_f32(ore_ctx* ctx, const ore_tensor* x, ore_tensor* y);
 /* "Reshape"  reshape()  reshape_op.rs:16-92: metadata only (row-major reinterpretation to
  *            2-D; a 0 in `shape` copies the input dim).  Writes the resulting view to y. */
 ore_status ore_reshape(const ore_tensor* x, const int64_t* shape, int32_t n_shape, ore_tensor* y);
+/* Input preprocessing (extension; no reference counterpart -- the reference reads a float TensorProto from
+ * a .pb file, main.rs): a batch of uint8 images as a decoder leaves them, interleaved [n,h,w,c] and
+ * contiguous with 1 <= c <= 4, to the float32 NCHW tensor the entry points above and ore_model_run take,
+ * in one launch (ore_preproc.hip):
+ *     y[i,ch,r,q] = fadd_rn(fmul_rn((float)x[i,r,q,cs], scale[ch]), shift[ch])
+ * with cs = ch, or cs = c-1-ch under ORE_PRE_REVERSE_CHANNELS (RGB <-> BGR; c == 3 only, ORE_ERR_INVALID
+ * otherwise).  The multiply and the add round separately, never as one FMA, so a host computes the same
+ * bits with (float)x * scale + shift in two float32 operations.  x is a DEVICE pointer; scale / shift are
+ * HOST arrays of c floats, read before the call returns (NULL: 1 / 0).  y is a [n,c,h,w] view and may be
+ * a slice (nstride >= c*h*w; the elements between images are not written).  h*w a multiple of 4, x
+ * 4-byte aligned and y's planes 16-byte aligned take the vector kernel; anything else a scalar one with
+ * the same results.  n == 0 is ORE_OK and launches nothing. */
+#define ORE_PRE_REVERSE_CHANNELS 1
+ore_status ore_preprocess_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t h, int64_t w, int64_t c,
+                             const float* scale, const float* shift, int32_t flags, ore_tensor* y);
 
 /* ------------------------------------------------------------------ graph walker (inference()) */
 /* Parse an ONNX ModelProto (bytes), upload every initializer to HBM once, plan the value
@@ -310,6 +325,27 @@ ore_status ore_model_set_streams(ore_model* m, int32_t streams);
  * ore_model_set_fusion / set_streams.  Needs a non-null context stream. */
 ore_status ore_model_graph_capture(ore_model* m, const float* d_input, int64_t n, float* d_output);
 ore_status ore_model_graph_launch(ore_model* m);
+/* uint8 input (extension, see ore_preprocess_u8): the _u8 entries take n images as device uint8
+ * [n,H,W,C] (C, H, W = ore_model_input_dims), convert them into a model-owned float32 NCHW staging buffer
+ * and run the graph on it, for f32 and f16 models alike (the staging tensor is the float32 model input
+ * both consume).
+ *  ore_model_set_input_norm: the scale / shift (HOST arrays of c floats, NULL = 1 / 0, copied) and flags
+ *    (ORE_PRE_REVERSE_CHANNELS) of the conversion; c must equal the model input's channel count.
+ *    Defaults: scale 1, shift 0, no reversal.  Also allocates the staging buffer.
+ *  The staging buffer holds run_batch images (154 MB at 256 x 3 x 224 x 224) and lives until
+ *    ore_model_destroy.  It is allocated by ore_model_set_input_norm, ore_model_graph_capture_u8 or the
+ *    first ore_model_run_u8 -- never inside a stream capture: a caller capturing ore_model_run_u8 into a
+ *    graph of its own calls ore_model_set_input_norm first (ORE_ERR_INVALID otherwise).
+ *  ore_model_run_u8: as ore_model_run, chunks included (the same chunks: convert a chunk, run it).
+ *    ore_model_read_value afterwards behaves as after ore_model_run; the input value reads back as the
+ *    converted float32 tensor.  The conversion is not an exec step: ore_model_step_count / _step_info /
+ *    _step_tile / _step_times do not see it, and ore_model_autotune stays float32-only (tune on a batch
+ *    converted with ore_preprocess_u8).
+ *  ore_model_graph_capture_u8: as ore_model_graph_capture, with the conversion inside the graph:
+ *    ore_model_graph_launch converts and runs whatever d_input holds at that moment. */
+ore_status ore_model_set_input_norm(ore_model* m, const float* scale, const float* shift, int32_t c, int32_t flags);
+ore_status ore_model_run_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
+ore_status ore_model_graph_capture_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);
 int32_t ore_model_step_count(ore_model* m);
 ore_status ore_model_step_info(ore_model* m, int32_t i, const char** op, const char** name, double* flops,

@@ -170,6 +170,11 @@ ore_status run_maxpool(ore_ctx* ctx, const float* x, int64_t N, int64_t C, int64
                        int64_t x_nstride, int64_t kh, int64_t kw, const Window& win, int64_t sh, int64_t sw,
                        float* y, int64_t y_nstride, int64_t x_ps = 0, int64_t y_ps = 0,
                        int es = 4);  // element bytes of x and y; ctx->pool_variant selects a kernel
+// the geometry and normalisation of a uint8 [.,h,w,c] -> f32 NCHW conversion (ore_preprocess_u8 and the
+// model's _u8 entries): checks c, h, w and flags, and resolves the channel reversal into p->plane;
+// scale / shift: host arrays of c floats or null (1 / 0).  x, y, N and y_nstride are the caller's to set.
+ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const float* scale, const float* shift,
+                          int32_t flags, PreprocParams* p);
 // MaxPool over NHWC f16 (f16 models); x_cs / y_cs: pixel strides
 ore_status run_maxpool_nhwc(ore_ctx* ctx, const void* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t x_nstride,
                             int64_t x_cs, int64_t kh, int64_t kw, const Window& win, int64_t sh, int64_t sw, void* y,

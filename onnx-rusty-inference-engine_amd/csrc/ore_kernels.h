@@ -433,5 +433,17 @@ void launch_softmax(const float* x, float* y, long long rows, int D, hipStream_t
 void launch_gap(const void* x, int es, float* y, long long rows, int HW, int ps, hipStream_t s);
 void launch_concat(const void* a, const void* b, void* y, int es, long long outer, long long ia, long long ib,
                    hipStream_t s);
+// uint8 NHWC -> f32 NCHW with a per-channel scale and shift (ore_preproc.hip).  Indexed by SOURCE channel s
+// (the byte's position in a pixel): it is written to plane[s] of y as fadd_rn(fmul_rn(byte, scale[s]), shift[s]).
+struct PreprocParams {
+  const unsigned char* x;  // [N][HW][C]
+  float* y;                // [N][C][HW] at an image stride of y_nstride elements
+  long long N;
+  long long y_nstride;
+  int HW, C;               // C * HW < 2^31
+  int plane[4];
+  float scale[4], shift[4];
+};
+void launch_preproc_u8(const PreprocParams& p, hipStream_t s);
 
 }  // namespace ore

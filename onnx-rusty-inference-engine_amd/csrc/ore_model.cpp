@@ -176,6 +176,12 @@ struct ore_model {
   bool out_bound = false;
   int64_t last_n = 0;
   bool last_chunked = false;     // the last run went in image chunks (arena values hold only the last one)
+  // uint8 input (ore_model_run_u8): the f32 NCHW staging buffer of run_batch images the conversion writes
+  // and the graph reads, and the normalisation of ore_model_set_input_norm (per output channel)
+  float* stage = nullptr;
+  size_t stage_bytes = 0;
+  float in_scale[4] = {1.f, 1.f, 1.f, 1.f}, in_shift[4] = {0.f, 0.f, 0.f, 0.f};
+  int32_t in_flags = 0;
 };
 
 namespace {
@@ -1894,6 +1900,7 @@ ore_status ore_model_destroy(ore_model* m) {
   if (m->packed) (void)hipFree(m->packed);
   for (auto& kv : m->fire_packs) (void)hipFree(kv.second);
   if (m->xcvt) (void)hipFree(m->xcvt);
+  if (m->stage) (void)hipFree(m->stage);
   delete m;
   return ORE_OK;
 }
@@ -1961,11 +1968,50 @@ static ore_status run_pass(ore_model* m, const float* d_input, int64_t n, float*
   return ORE_OK;
 }
 
-ore_status ore_model_run(ore_model* m, const float* d_input, int64_t n, float* d_output) {
-  if (!m || !d_input || !d_output) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+// the staging buffer of the _u8 entries, sized for run_batch images (plan() may have changed it); never
+// allocated inside a stream capture
+static ore_status ensure_stage(ore_model* m) {
   ore_ctx* ctx = m->ctx;
-  if (n < 0 || n > m->max_batch) return set_error(ctx, ORE_ERR_INVALID, "batch %lld exceeds max_batch %lld", (long long)n, (long long)m->max_batch);
+  const size_t need = size_t(m->values[m->input_value].per_image()) * size_t(m->run_batch) * 4;
+  if (m->stage && m->stage_bytes >= need) return ORE_OK;
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return set_error(ctx, ORE_ERR_INVALID, "the uint8 staging buffer cannot be allocated inside a stream capture: call "
+                                           "ore_model_set_input_norm first");
+  ORE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // an earlier run may still read the old buffer
+  if (m->stage) (void)hipFree(m->stage);
+  m->stage = nullptr;
+  m->stage_bytes = 0;
+  if (hipMalloc(&m->stage, need) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_error(ctx, ORE_ERR_OOM, "uint8 input staging buffer (%zu bytes) allocation failed", need);
+  }
+  m->stage_bytes = need;
+  return ORE_OK;
+}
+
+// argument checks of the run / capture entries; d_input is the float32 or the uint8 batch
+static ore_status check_run_args(ore_model* m, const void* d_input, int64_t n, float* d_output) {
+  if (!m || !d_input || !d_output) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+  if (n < 0 || n > m->max_batch)
+    return set_error(m->ctx, ORE_ERR_INVALID, "batch %lld exceeds max_batch %lld", (long long)n, (long long)m->max_batch);
+  return ORE_OK;
+}
+
+// ore_model_run and ore_model_run_u8: the graph over n images, in chunks of at most run_batch.  With d_u8 the
+// input is the uint8 NHWC batch: each chunk is converted into the staging buffer (ensure_stage), then run.
+static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output) {
+  ore_ctx* ctx = m->ctx;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const Value& iv = m->values[m->input_value];
+  PreprocParams pre;
+  if (d_u8) {
+    if (ore_status st = preproc_params(ctx, iv.dims[2], iv.dims[3], iv.dims[1], m->in_scale, m->in_shift, m->in_flags, &pre))
+      return st;
+    pre.y = m->stage;
+    pre.y_nstride = iv.per_image();
+  }
   m->last_n = n;
   const Value& ov = m->values[m->output_value];
   // bind the output buffer directly when its producer writes a plain contiguous tensor
@@ -1987,14 +2033,50 @@ ore_status ore_model_run(ore_model* m, const float* d_input, int64_t n, float* d
     ORE_HIP_CHECK(ctx, hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
     ORE_HIP_CHECK(ctx, hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
   }
-  const int64_t in_img = m->values[m->input_value].per_image(), out_img = ov.per_image();
+  const int64_t in_img = iv.per_image(), out_img = ov.per_image();
   for (int64_t c = 0, i0 = 0; c < nchunks; ++c, i0 += chunk) {
     const int64_t nc = std::min(chunk, n - i0);
-    if (ore_status st = run_pass(m, d_input + i0 * in_img, nc, d_output + i0 * out_img,
+    const float* x = d_input ? d_input + i0 * in_img : m->stage;
+    if (d_u8) {  // before the pass's first timing event: ore_model_step_times does not include it
+      pre.x = d_u8 + i0 * in_img;
+      pre.N = nc;
+      launch_preproc_u8(pre, ctx->stream);
+      ORE_HIP_CHECK(ctx, hipGetLastError());
+    }
+    if (ore_status st = run_pass(m, x, nc, d_output + i0 * out_img,
                                  m->timing ? m->events.data() + size_t(c) * nev : nullptr))
       return st;
   }
   return ORE_OK;
+}
+
+ore_status ore_model_run(ore_model* m, const float* d_input, int64_t n, float* d_output) {
+  if (ore_status st = check_run_args(m, d_input, n, d_output)) return st;
+  return run_chunks(m, d_input, nullptr, n, d_output);
+}
+
+ore_status ore_model_set_input_norm(ore_model* m, const float* scale, const float* shift, int32_t c, int32_t flags) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  ore_ctx* ctx = m->ctx;
+  const Value& iv = m->values[m->input_value];
+  if (c != iv.dims[1])
+    return set_error(ctx, ORE_ERR_INVALID, "input norm for %d channels, the model input has %lld", int(c), (long long)iv.dims[1]);
+  PreprocParams pre;
+  if (ore_status st = preproc_params(ctx, iv.dims[2], iv.dims[3], c, scale, shift, flags, &pre)) return st;
+  if (ore_status st = ensure_stage(m)) return st;
+  for (int i = 0; i < c; ++i) {
+    m->in_scale[i] = scale ? scale[i] : 1.0f;
+    m->in_shift[i] = shift ? shift[i] : 0.0f;
+  }
+  m->in_flags = flags;
+  return ORE_OK;
+}
+
+ore_status ore_model_run_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output) {
+  if (ore_status st = check_run_args(m, d_input, n, d_output)) return st;
+  if (n == 0) return ORE_OK;
+  if (ore_status st = ensure_stage(m)) return st;
+  return run_chunks(m, nullptr, d_input, n, d_output);
 }
 
 ore_status ore_model_read_value(ore_model* m, const char* name, float* host_dst, size_t cap, int64_t dims[4],
@@ -2173,8 +2255,8 @@ ore_status ore_model_set_streams(ore_model* m, int32_t streams) {
   return ORE_OK;
 }
 
-ore_status ore_model_graph_capture(ore_model* m, const float* d_input, int64_t n, float* d_output) {
-  if (!m || !d_input || !d_output) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+// ore_model_graph_capture and ore_model_graph_capture_u8: one run_chunks(d_input, d_u8, n, d_output) as a HIP graph
+static ore_status capture_run(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output) {
   ore_ctx* ctx = m->ctx;
   if (m->timing) return set_error(ctx, ORE_ERR_INVALID, "disable step timing before capturing a graph");
   if (!ctx->stream) return set_error(ctx, ORE_ERR_INVALID, "graph capture needs a non-null context stream");
@@ -2186,8 +2268,10 @@ ore_status ore_model_graph_capture(ore_model* m, const float* d_input, int64_t n
     ORE_HIP_CHECK(ctx, hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
     ORE_HIP_CHECK(ctx, hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
   }
+  if (d_u8)  // allocated outside the capture
+    if (ore_status st = ensure_stage(m)) return st;
   ORE_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  ore_status st = ore_model_run(m, d_input, n, d_output);
+  ore_status st = run_chunks(m, d_input, d_u8, n, d_output);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
   if (st) {
@@ -2198,6 +2282,16 @@ ore_status ore_model_graph_capture(ore_model* m, const float* d_input, int64_t n
   m->graph = g;
   ORE_HIP_CHECK(ctx, hipGraphInstantiate(&m->graph_exec, m->graph, nullptr, nullptr, 0));
   return ORE_OK;
+}
+
+ore_status ore_model_graph_capture(ore_model* m, const float* d_input, int64_t n, float* d_output) {
+  if (ore_status st = check_run_args(m, d_input, n, d_output)) return st;
+  return capture_run(m, d_input, nullptr, n, d_output);
+}
+
+ore_status ore_model_graph_capture_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output) {
+  if (ore_status st = check_run_args(m, d_input, n, d_output)) return st;
+  return capture_run(m, nullptr, d_input, n, d_output);
 }
 
 ore_status ore_model_graph_launch(ore_model* m) {

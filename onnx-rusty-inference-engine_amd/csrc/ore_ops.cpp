@@ -113,6 +113,27 @@ static int64_t image_chunk(int64_t N, int64_t x_nstride, int64_t x_img_bytes, in
   return nb;
 }
 
+ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const float* scale, const float* shift,
+                          int32_t flags, PreprocParams* p) {
+  if (c < 1 || c > 4) return set_error(ctx, ORE_ERR_INVALID, "uint8 input: %lld channels (1..4 supported)", (long long)c);
+  if (flags & ~ORE_PRE_REVERSE_CHANNELS)
+    return set_error(ctx, ORE_ERR_INVALID, "unknown preprocess flags 0x%x", unsigned(flags & ~ORE_PRE_REVERSE_CHANNELS));
+  const bool rev = (flags & ORE_PRE_REVERSE_CHANNELS) != 0;
+  if (rev && c != 3) return set_error(ctx, ORE_ERR_INVALID, "ORE_PRE_REVERSE_CHANNELS needs 3 channels, not %lld", (long long)c);
+  if (h <= 0 || w <= 0 || !fits_i32(h) || !fits_i32(w) || !fits_i32(h * w) || !fits_i32(h * w * c))
+    return set_error(ctx, ORE_ERR_INVALID, "uint8 input: image of %lld x %lld x %lld", (long long)h, (long long)w, (long long)c);
+  *p = PreprocParams{};
+  p->HW = int(h * w);
+  p->C = int(c);
+  for (int s = 0; s < int(c); ++s) {  // source channel s is output channel ch
+    const int ch = rev ? int(c) - 1 - s : s;
+    p->plane[s] = ch;
+    p->scale[s] = scale ? scale[ch] : 1.0f;
+    p->shift[s] = shift ? shift[ch] : 0.0f;
+  }
+  return ORE_OK;
+}
+
 ConvPlan conv_plan(int64_t M, int64_t C, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
                    const Window& win, bool f16, int xmode, bool wino, int forced) {
   return plan_conv(int(M), int(C), int(H), int(W), int(kh), int(kw), int(sh), int(sw), int(win.pt), int(win.pl),
@@ -831,6 +852,25 @@ ore_status ore_dropout_f32(ore_ctx* ctx, const ore_tensor* x, ore_tensor* y) {
     return set_error(ctx, ORE_ERR_INVALID, "Dropout size mismatch");
   if (x->data == y->data) return ORE_OK;
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(y->data, x->data, size_t(numel(x)) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  return ORE_OK;
+}
+
+ore_status ore_preprocess_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t h, int64_t w, int64_t c, const float* scale,
+                             const float* shift, int32_t flags, ore_tensor* y) {
+  if (!ctx || !x || !y || !y->data) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  PreprocParams p;
+  if (ore_status st = preproc_params(ctx, h, w, c, scale, shift, flags, &p)) return st;
+  if (n < 0) return set_error(ctx, ORE_ERR_INVALID, "negative batch %lld", (long long)n);
+  if (y->ndim != 4 || y->dims[0] != n || y->dims[1] != c || y->dims[2] != h || y->dims[3] != w || nstride_of(y) < c * h * w)
+    return set_error(ctx, ORE_ERR_INVALID, "preprocess output must be a [n,c,h,w] view of the [n,h,w,c] input");
+  if (n == 0) return ORE_OK;
+  p.x = x;
+  p.y = y->data;
+  p.N = n;
+  p.y_nstride = nstride_of(y);
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_preproc_u8(p, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }
 

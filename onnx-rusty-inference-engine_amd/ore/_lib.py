@@ -27,6 +27,7 @@ LOAD_NO_WINOGRAD = 4  # ore_model_load_ex flag: 3x3 stride-1 convs on the direct
 LOAD_RETIRED_MASK = 10  # ABI 1's LOAD_X3 / LOAD_X3_ALL: rejected (ORE_ERR_UNSUPPORTED) since ABI 2
 ABI_VERSION = 2  # ORE_ABI_VERSION this binding was written against
 CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD = 0, 1  # ore_ctx_set_conv_algo (per-op ore_conv2d_f32)
+PRE_REVERSE_CHANNELS = 1  # ore_preprocess_u8 / ore_model_set_input_norm flag: RGB <-> BGR
 PAD = {"NOTSET": 0, "NOT_SET": 0, "SAME_UPPER": 1, "SAME_LOWER": 2, "VALID": 3}
 
 # every symbol include/ore.h declares (checked by tests/test_abi.py on CPU)
@@ -35,7 +36,8 @@ EXPORTED = [
     "ore_ctx_set_conv_algo", "ore_ctx_set_conv_tile", "ore_ctx_set_pool_variant", "ore_sync", "ore_last_error", "ore_malloc", "ore_free", "ore_upload", "ore_download",
     "ore_conv_out_shape", "ore_pool_out_shape", "ore_conv2d_f32", "ore_maxpool2d_f32", "ore_relu_f32",
     "ore_add_f32", "ore_softmax_f32", "ore_matmul_f32", "ore_gap_f32", "ore_concat_f32", "ore_dropout_f32",
-    "ore_reshape", "ore_model_parse", "ore_model_load", "ore_model_load_ex", "ore_model_destroy", "ore_model_set_fusion", "ore_model_input_dims",
+    "ore_reshape", "ore_preprocess_u8", "ore_model_set_input_norm", "ore_model_run_u8", "ore_model_graph_capture_u8",
+    "ore_model_parse", "ore_model_load", "ore_model_load_ex", "ore_model_destroy", "ore_model_set_fusion", "ore_model_input_dims",
     "ore_model_output_elems", "ore_model_run", "ore_model_read_value", "ore_model_autotune",
     "ore_model_step_tile", "ore_model_set_step_tile", "ore_model_step_mfma_flops", "ore_model_set_streams",
     "ore_model_graph_capture", "ore_model_graph_launch", "ore_model_enable_timing",
@@ -79,6 +81,7 @@ def load():
     vp, i32, i64, cs = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_char_p
     T = ctypes.POINTER(Tensor)
     I64P = ctypes.POINTER(ctypes.c_int64)
+    F32P = ctypes.POINTER(ctypes.c_float)
     sig = {
         "ore_abi_version": (i32, []),
         "ore_ctx_create": (i32, [i32, ctypes.POINTER(vp)]),
@@ -106,6 +109,10 @@ def load():
         "ore_concat_f32": (i32, [vp, T, T, i64, T]),
         "ore_dropout_f32": (i32, [vp, T, T]),
         "ore_reshape": (i32, [T, I64P, i32, T]),
+        "ore_preprocess_u8": (i32, [vp, vp, i64, i64, i64, i64, F32P, F32P, i32, T]),
+        "ore_model_set_input_norm": (i32, [vp, F32P, F32P, i32, i32]),
+        "ore_model_run_u8": (i32, [vp, vp, i64, vp]),
+        "ore_model_graph_capture_u8": (i32, [vp, vp, i64, vp]),
         "ore_model_parse": (i32, [ctypes.c_char_p, ctypes.c_size_t]),
         "ore_model_load": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, ctypes.POINTER(vp)]),
         "ore_model_load_ex": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, i32, ctypes.POINTER(vp)]),

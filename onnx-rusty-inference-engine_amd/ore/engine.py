@@ -16,11 +16,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import LOAD_F16, LOAD_NO_WINOGRAD, ConvAttrs, OreError, PoolAttrs, Tensor, check, load
+from ._lib import LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, OreError, PoolAttrs, Tensor, check, load
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "inference", "conv_out_shape",
-           "pool_out_shape"]
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "inference",
+           "conv_out_shape", "pool_out_shape"]
 
 
 def _torch():
@@ -229,6 +229,46 @@ def reshape(x, shape: Sequence[int]):
     return x.view(int(y.dims[0]), int(y.dims[1]))
 
 
+def _check_u8(x, device: int, name: str = "x"):
+    """A uint8 image batch handed to the library as a raw device pointer: a contiguous torch.uint8 CUDA
+    tensor [n, H, W, C] on the context's device."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.uint8:
+        raise OreError(1, f"{name}: expected a uint8 CUDA tensor")
+    if x.device.index != device:
+        raise OreError(1, f"{name}: on cuda:{x.device.index}, the context is on cuda:{device}")
+    if x.dim() != 4:
+        raise OreError(1, f"{name}: expected [n, H, W, C], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise OreError(1, f"{name}: expected a contiguous tensor")
+
+
+def _norm_arg(v, c: int, name: str):
+    """scale / shift -> a ctypes float[c] (None stays None: the library's default)."""
+    if v is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1))
+    if a.size != c:
+        raise OreError(1, f"{name}: {a.size} values for {c} channels")
+    return (ctypes.c_float * c)(*a.tolist())
+
+
+def preprocess_u8(ctx: Context, x, scale=None, shift=None, reverse_channels: bool = False):
+    """ore_preprocess_u8 (extension): uint8 [n, H, W, C] -> float32 [n, C, H, W] with
+    y[:, c] = float32(x[..., cs]) * scale[c] + shift[c] (two float32 roundings; cs = C-1-c when
+    reverse_channels).  scale / shift: C floats each (None: 1 / 0)."""
+    torch = _torch()
+    _check_u8(x, ctx.device)
+    n, h, w, c = (int(d) for d in x.shape)
+    if not 1 <= c <= 4:
+        raise OreError(1, f"x: {c} channels (1..4 supported)")
+    y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    flags = PRE_REVERSE_CHANNELS if reverse_channels else 0
+    check(load().ore_preprocess_u8(ctx.h, ctypes.c_void_p(x.data_ptr()), n, h, w, c, _norm_arg(scale, c, "scale"),
+                                   _norm_arg(shift, c, "shift"), flags, ctypes.byref(_desc(y))), ctx.h)
+    return y
+
+
 # ------------------------------------------------------------------------------ graph walker
 class Model:
     """ore_model: the device-resident walker over one ONNX graph."""
@@ -293,6 +333,56 @@ class Model:
         torch = _torch()
         out = torch.empty((x.shape[0], self.output_elems), dtype=torch.float32, device=x.device)
         return self.run_into(x, out)
+
+    def set_input_norm(self, scale=None, shift=None, reverse_channels: bool = False):
+        """ore_model_set_input_norm: the per-channel scale / shift (C floats each, None: 1 / 0) and the
+        channel reversal run_u8 / capture_u8 apply (see preprocess_u8)."""
+        c = int(self.input_dims[0])
+        flags = PRE_REVERSE_CHANNELS if reverse_channels else 0
+        sc, sh = _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift")
+        check(load().ore_model_set_input_norm(self.h, sc, sh, c, flags), self.ctx.h)
+
+    def _check_io_u8(self, x, out):
+        """As _check_io for a uint8 input: x [n, H, W, C] matching the model's (C, H, W), n <= max_batch."""
+        torch = _torch()
+        _check_u8(x, self.ctx.device)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise OreError(1, "out: expected a float32 CUDA tensor")
+        if out.device.index != self.ctx.device:
+            raise OreError(1, f"out: on cuda:{out.device.index}, the context is on cuda:{self.ctx.device}")
+        if not out.is_contiguous():
+            raise OreError(1, "out: expected a contiguous tensor")
+        n, h, w, c = (int(d) for d in x.shape)
+        if (c, h, w) != tuple(self.input_dims):
+            raise OreError(1, f"input dims (H, W, C) = {(h, w, c)} != model (C, H, W) = {self.input_dims}")
+        if n > self.max_batch:
+            raise OreError(1, f"batch {n} exceeds max_batch {self.max_batch}")
+        if out.numel() < n * self.output_elems:
+            raise OreError(1, f"out holds {out.numel()} floats, {n} images need {n * self.output_elems}")
+        return n
+
+    def run_u8_into(self, x, out):
+        """ore_model_run_u8: run_into on a uint8 [n, H, W, C] batch, converted on the device with the
+        normalisation of set_input_norm (asynchronous on the context stream)."""
+        n = self._check_io_u8(x, out)
+        check(load().ore_model_run_u8(self.h, ctypes.c_void_p(x.data_ptr()), int(n), ctypes.c_void_p(out.data_ptr())),
+              self.ctx.h)
+        return out
+
+    def run_u8(self, x):
+        torch = _torch()
+        _check_u8(x, self.ctx.device)
+        out = torch.empty((x.shape[0], self.output_elems), dtype=torch.float32, device=x.device)
+        return self.run_u8_into(x, out)
+
+    def capture_u8(self, x, out):
+        """ore_model_graph_capture_u8: capture run_u8_into(x, out), the conversion included, as a HIP
+        graph; replay() converts and runs whatever the uint8 buffer holds then."""
+        n = self._check_io_u8(x, out)
+        self._graph_bufs = (x, out)  # the graph holds these pointers
+        check(load().ore_model_graph_capture_u8(self.h, ctypes.c_void_p(x.data_ptr()), int(n),
+                                                ctypes.c_void_p(out.data_ptr())), self.ctx.h)
+        return out
 
     def read_value(self, name: str) -> np.ndarray:
         dims = (ctypes.c_int64 * 4)()
