@@ -177,6 +177,16 @@ ore_status ore_reshape(const ore_tensor* x, const int64_t* shape, int32_t n_shap
 #define ORE_PRE_REVERSE_CHANNELS 1
 ore_status ore_preprocess_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t h, int64_t w, int64_t c,
                              const float* scale, const float* shift, int32_t flags, ore_tensor* y);
+/* Row-wise top-k (extension; no reference counterpart -- the reference prints the full output tensor): the
+ * k best elements of every row of x, in one launch (ore_topk.hip).  Rows are x->dims[0], the row length D
+ * the product of the remaining dims (as for ore_softmax_f32); x->nstride >= D is honoured.  values and
+ * indices are contiguous DEVICE arrays [rows, k], 1 <= k <= min(D, 64).  Output j of a row is the element
+ * ranked j in the order "larger value first; among equal values the lower index first", where -0.0 and
+ * +0.0 are equal and every NaN ranks after every number (-inf included), NaNs among themselves by index:
+ * exactly np.argsort(-x, axis=1, kind="stable")[:, :k].  values[r,j] is a bit copy of x[r, indices[r,j]]
+ * (a zero keeps its sign, a NaN its payload).  rows == 0 is ORE_OK and launches nothing; a null argument
+ * or a k out of range is ORE_ERR_INVALID, checked before any device call. */
+ore_status ore_topk_f32(ore_ctx* ctx, const ore_tensor* x, int32_t k, float* values, int32_t* indices);
 
 /* ------------------------------------------------------------------ graph walker (inference()) */
 /* Parse an ONNX ModelProto (bytes), upload every initializer to HBM once, plan the value
@@ -346,6 +356,29 @@ ore_status ore_model_graph_launch(ore_model* m);
 ore_status ore_model_set_input_norm(ore_model* m, const float* scale, const float* shift, int32_t c, int32_t flags);
 ore_status ore_model_run_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
 ore_status ore_model_graph_capture_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
+/* Top-k output (extension, see ore_topk_f32): the classify entries run the graph as ore_model_run /
+ * ore_model_run_u8 do, chunks included, but keep the [n, output elems] rows in a model-owned buffer and
+ * write only the k best per image: d_scores float32 [n,k] and d_classes int32 [n,k], both contiguous
+ * DEVICE arrays, in ore_topk_f32's order.
+ *  ore_model_set_topk: k for the entries below, 1 <= k <= min(output elems, 64); default 1.  Also
+ *    allocates the rows buffer.
+ *  The rows buffer holds run_batch images' outputs (1 MB at 256 x 1000) and lives until
+ *    ore_model_destroy.  It is allocated by ore_model_set_topk, a _capture_classify entry or the first
+ *    classify call -- never inside a stream capture: a caller capturing ore_model_classify into a graph
+ *    of its own calls ore_model_set_topk first (ORE_ERR_INVALID otherwise).
+ *  ore_model_classify / _classify_u8: per chunk, one pass of the graph, then one top-k launch over the
+ *    chunk's rows.  The selection comes after the pass's last timing event and is not an exec step:
+ *    ore_model_step_count / _step_info / _step_tile / _step_times and ore_model_autotune do not see it.
+ *    ore_model_read_value afterwards behaves as after ore_model_run.  n == 0 is ORE_OK.
+ *  ore_model_graph_capture_classify / _classify_u8: as ore_model_graph_capture / _capture_u8 with the
+ *    selection inside the graph: ore_model_graph_launch converts (u8), runs and selects. */
+ore_status ore_model_set_topk(ore_model* m, int32_t k);
+ore_status ore_model_classify(ore_model* m, const float* d_input, int64_t n, float* d_scores, int32_t* d_classes);
+ore_status ore_model_classify_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_scores, int32_t* d_classes);
+ore_status ore_model_graph_capture_classify(ore_model* m, const float* d_input, int64_t n, float* d_scores,
+                                            int32_t* d_classes);
+ore_status ore_model_graph_capture_classify_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_scores,
+                                               int32_t* d_classes);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);
 int32_t ore_model_step_count(ore_model* m);
 ore_status ore_model_step_info(ore_model* m, int32_t i, const char** op, const char** name, double* flops,

@@ -445,5 +445,9 @@ struct PreprocParams {
   float scale[4], shift[4];
 };
 void launch_preproc_u8(const PreprocParams& p, hipStream_t s);
+// row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
+// contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
+void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,
+                 hipStream_t s);
 
 }  // namespace ore

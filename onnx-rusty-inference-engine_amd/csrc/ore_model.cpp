@@ -182,6 +182,11 @@ struct ore_model {
   size_t stage_bytes = 0;
   float in_scale[4] = {1.f, 1.f, 1.f, 1.f}, in_shift[4] = {0.f, 0.f, 0.f, 0.f};
   int32_t in_flags = 0;
+  // top-k output (ore_model_classify): the f32 rows buffer of run_batch images' outputs the graph writes
+  // and the selection reads, and the k of ore_model_set_topk
+  float* rows = nullptr;
+  size_t rows_bytes = 0;
+  int32_t topk = 1;
 };
 
 namespace {
@@ -1901,6 +1906,7 @@ ore_status ore_model_destroy(ore_model* m) {
   for (auto& kv : m->fire_packs) (void)hipFree(kv.second);
   if (m->xcvt) (void)hipFree(m->xcvt);
   if (m->stage) (void)hipFree(m->stage);
+  if (m->rows) (void)hipFree(m->rows);
   delete m;
   return ORE_OK;
 }
@@ -1926,8 +1932,10 @@ ore_status ore_model_output_elems(ore_model* m, int64_t* elems) {
   return ORE_OK;
 }
 
-// one pass of the graph over n <= run_batch images; ev: this pass's timing events (exec_steps + 1)
-static ore_status run_pass(ore_model* m, const float* d_input, int64_t n, float* d_output, hipEvent_t* ev) {
+// one pass of the graph over n <= run_batch images; ev: this pass's timing events (exec_steps + 1).  With
+// copy_out false an output value that lives in the arena stays there (the caller reads it through ref_of).
+static ore_status run_pass(ore_model* m, const float* d_input, int64_t n, float* d_output, hipEvent_t* ev,
+                           bool copy_out = true) {
   ore_ctx* ctx = m->ctx;
   m->cur_in = d_input;
   m->cur_out = d_output;
@@ -1955,7 +1963,7 @@ static ore_status run_pass(ore_model* m, const float* d_input, int64_t n, float*
     if (st) return st;
   }
   if (m->timing) ORE_HIP_CHECK(ctx, hipEventRecord(ev[m->exec_steps.size()], ctx->stream));
-  if (!m->out_bound) {
+  if (!m->out_bound && copy_out) {
     const Ref r = ref_of(m, m->output_value);
     const int64_t pe = ov.per_image();
     if (r.nstride == pe) {
@@ -1991,6 +1999,29 @@ static ore_status ensure_stage(ore_model* m) {
   return ORE_OK;
 }
 
+// the rows buffer of the classify entries, sized for run_batch images' outputs (plan() may have changed it);
+// never allocated inside a stream capture
+static ore_status ensure_rows(ore_model* m) {
+  ore_ctx* ctx = m->ctx;
+  const size_t need = size_t(m->values[m->output_value].per_image()) * size_t(m->run_batch) * 4;
+  if (m->rows && m->rows_bytes >= need) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return set_error(ctx, ORE_ERR_INVALID, "the top-k rows buffer cannot be allocated inside a stream capture: call "
+                                           "ore_model_set_topk first");
+  ORE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // an earlier run may still read the old buffer
+  if (m->rows) (void)hipFree(m->rows);
+  m->rows = nullptr;
+  m->rows_bytes = 0;
+  if (hipMalloc(&m->rows, need) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_error(ctx, ORE_ERR_OOM, "top-k rows buffer (%zu bytes) allocation failed", need);
+  }
+  m->rows_bytes = need;
+  return ORE_OK;
+}
+
 // argument checks of the run / capture entries; d_input is the float32 or the uint8 batch
 static ore_status check_run_args(ore_model* m, const void* d_input, int64_t n, float* d_output) {
   if (!m || !d_input || !d_output) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
@@ -1999,9 +2030,19 @@ static ore_status check_run_args(ore_model* m, const void* d_input, int64_t n, f
   return ORE_OK;
 }
 
-// ore_model_run and ore_model_run_u8: the graph over n images, in chunks of at most run_batch.  With d_u8 the
-// input is the uint8 NHWC batch: each chunk is converted into the staging buffer (ensure_stage), then run.
-static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output) {
+// the classify entries' checks: check_run_args with two outputs
+static ore_status check_classify_args(ore_model* m, const void* d_input, int64_t n, float* d_scores, int32_t* d_classes) {
+  if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+  return check_run_args(m, d_input, n, d_scores);
+}
+
+// ore_model_run, ore_model_run_u8 and the classify entries: the graph over n images, in chunks of at most
+// run_batch.  With d_u8 the input is the uint8 NHWC batch: each chunk is converted into the staging buffer
+// (ensure_stage), then run.  With d_classes each chunk's output stays on the model's side (the rows buffer of
+// ensure_rows, or the arena where the output value lives there) and its m->topk best per image go to rows
+// [i0, i0 + nc) of d_output (the scores) and d_classes, both [n, topk].
+static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output,
+                             int32_t* d_classes = nullptr) {
   ore_ctx* ctx = m->ctx;
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const Value& iv = m->values[m->input_value];
@@ -2043,9 +2084,14 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
       launch_preproc_u8(pre, ctx->stream);
       ORE_HIP_CHECK(ctx, hipGetLastError());
     }
-    if (ore_status st = run_pass(m, x, nc, d_output + i0 * out_img,
-                                 m->timing ? m->events.data() + size_t(c) * nev : nullptr))
+    if (ore_status st = run_pass(m, x, nc, d_classes ? m->rows : d_output + i0 * out_img,
+                                 m->timing ? m->events.data() + size_t(c) * nev : nullptr, !d_classes))
       return st;
+    if (d_classes) {  // after the pass's last timing event: not an exec step
+      const Ref r = ref_of(m, m->output_value);
+      launch_topk(r.p, r.nstride, nc, int(out_img), m->topk, d_output + i0 * m->topk, d_classes + i0 * m->topk, ctx->stream);
+      ORE_HIP_CHECK(ctx, hipGetLastError());
+    }
   }
   return ORE_OK;
 }
@@ -2077,6 +2123,31 @@ ore_status ore_model_run_u8(ore_model* m, const uint8_t* d_input, int64_t n, flo
   if (n == 0) return ORE_OK;
   if (ore_status st = ensure_stage(m)) return st;
   return run_chunks(m, nullptr, d_input, n, d_output);
+}
+
+ore_status ore_model_set_topk(ore_model* m, int32_t k) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  const int64_t kmax = std::min<int64_t>(m->values[m->output_value].per_image(), 64);
+  if (k < 1 || k > kmax)
+    return set_error(m->ctx, ORE_ERR_INVALID, "top-k k = %d outside 1..%lld (min(output elems, 64))", int(k), (long long)kmax);
+  if (ore_status st = ensure_rows(m)) return st;
+  m->topk = k;
+  return ORE_OK;
+}
+
+ore_status ore_model_classify(ore_model* m, const float* d_input, int64_t n, float* d_scores, int32_t* d_classes) {
+  if (ore_status st = check_classify_args(m, d_input, n, d_scores, d_classes)) return st;
+  if (n == 0) return ORE_OK;
+  if (ore_status st = ensure_rows(m)) return st;
+  return run_chunks(m, d_input, nullptr, n, d_scores, d_classes);
+}
+
+ore_status ore_model_classify_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_scores, int32_t* d_classes) {
+  if (ore_status st = check_classify_args(m, d_input, n, d_scores, d_classes)) return st;
+  if (n == 0) return ORE_OK;
+  if (ore_status st = ensure_stage(m)) return st;
+  if (ore_status st = ensure_rows(m)) return st;
+  return run_chunks(m, nullptr, d_input, n, d_scores, d_classes);
 }
 
 ore_status ore_model_read_value(ore_model* m, const char* name, float* host_dst, size_t cap, int64_t dims[4],
@@ -2255,8 +2326,9 @@ ore_status ore_model_set_streams(ore_model* m, int32_t streams) {
   return ORE_OK;
 }
 
-// ore_model_graph_capture and ore_model_graph_capture_u8: one run_chunks(d_input, d_u8, n, d_output) as a HIP graph
-static ore_status capture_run(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output) {
+// the graph capture entries: one run_chunks(d_input, d_u8, n, d_output, d_classes) as a HIP graph
+static ore_status capture_run(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output,
+                              int32_t* d_classes = nullptr) {
   ore_ctx* ctx = m->ctx;
   if (m->timing) return set_error(ctx, ORE_ERR_INVALID, "disable step timing before capturing a graph");
   if (!ctx->stream) return set_error(ctx, ORE_ERR_INVALID, "graph capture needs a non-null context stream");
@@ -2270,8 +2342,10 @@ static ore_status capture_run(ore_model* m, const float* d_input, const uint8_t*
   }
   if (d_u8)  // allocated outside the capture
     if (ore_status st = ensure_stage(m)) return st;
+  if (d_classes)
+    if (ore_status st = ensure_rows(m)) return st;
   ORE_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  ore_status st = run_chunks(m, d_input, d_u8, n, d_output);
+  ore_status st = run_chunks(m, d_input, d_u8, n, d_output, d_classes);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
   if (st) {
@@ -2292,6 +2366,18 @@ ore_status ore_model_graph_capture(ore_model* m, const float* d_input, int64_t n
 ore_status ore_model_graph_capture_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output) {
   if (ore_status st = check_run_args(m, d_input, n, d_output)) return st;
   return capture_run(m, nullptr, d_input, n, d_output);
+}
+
+ore_status ore_model_graph_capture_classify(ore_model* m, const float* d_input, int64_t n, float* d_scores,
+                                            int32_t* d_classes) {
+  if (ore_status st = check_classify_args(m, d_input, n, d_scores, d_classes)) return st;
+  return capture_run(m, d_input, nullptr, n, d_scores, d_classes);
+}
+
+ore_status ore_model_graph_capture_classify_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_scores,
+                                               int32_t* d_classes) {
+  if (ore_status st = check_classify_args(m, d_input, n, d_scores, d_classes)) return st;
+  return capture_run(m, nullptr, d_input, n, d_scores, d_classes);
 }
 
 ore_status ore_model_graph_launch(ore_model* m) {

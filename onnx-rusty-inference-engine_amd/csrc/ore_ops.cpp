@@ -795,6 +795,25 @@ ore_status ore_softmax_f32(ore_ctx* ctx, const ore_tensor* x, ore_tensor* y) {
   return ORE_OK;
 }
 
+ore_status ore_topk_f32(ore_ctx* ctx, const ore_tensor* x, int32_t k, float* values, int32_t* indices) {
+  // the context last: what can be judged without one is (a null context still gets the message)
+  if (!x || !x->data || !values || !indices) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (x->ndim < 1 || x->ndim > 4) return set_error(ctx, ORE_ERR_INVALID, "top-k input of %d dims", int(x->ndim));
+  const int64_t rows = x->dims[0];
+  int64_t D = 1;
+  for (int i = 1; i < x->ndim; ++i) D *= x->dims[i];
+  if (rows < 0 || D <= 0 || !fits_i32(D) || nstride_of(x) < D) return set_error(ctx, ORE_ERR_INVALID, "top-k row length");
+  if (k < 1 || k > std::min<int64_t>(D, 64))
+    return set_error(ctx, ORE_ERR_INVALID, "top-k k = %d outside 1..%lld (min(row length, 64))", int(k),
+                     (long long)std::min<int64_t>(D, 64));
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (rows == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_topk(x->data, nstride_of(x), rows, int(D), int(k), values, indices, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
 ore_status ore_matmul_f32(ore_ctx* ctx, const ore_tensor* a, const ore_tensor* b, ore_tensor* y) {
   if (!ctx || !a || !b || !y) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (a->ndim != 2 || b->ndim != 2 || y->ndim != 2 || a->dims[1] != b->dims[0] || y->dims[0] != a->dims[0] ||

@@ -7,6 +7,6 @@ from ._lib import (CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD, FUSE_ALIAS, FUSE_ALL, F
                    ABI_VERSION, PRE_REVERSE_CHANNELS,
                    load)
 from .engine import (Context, Model, add, concatenation, conv_out_shape, convolution, drop_out,  # noqa: F401
-                     global_average_pool, inference, max_pool, mul, pool_out_shape, preprocess_u8, relu, reshape, softmax)
+                     global_average_pool, inference, max_pool, mul, pool_out_shape, preprocess_u8, relu, reshape, softmax, topk)
 
 __version__ = "0.1.0"

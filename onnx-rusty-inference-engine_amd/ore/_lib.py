@@ -37,6 +37,8 @@ EXPORTED = [
     "ore_conv_out_shape", "ore_pool_out_shape", "ore_conv2d_f32", "ore_maxpool2d_f32", "ore_relu_f32",
     "ore_add_f32", "ore_softmax_f32", "ore_matmul_f32", "ore_gap_f32", "ore_concat_f32", "ore_dropout_f32",
     "ore_reshape", "ore_preprocess_u8", "ore_model_set_input_norm", "ore_model_run_u8", "ore_model_graph_capture_u8",
+    "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
+    "ore_model_graph_capture_classify", "ore_model_graph_capture_classify_u8",
     "ore_model_parse", "ore_model_load", "ore_model_load_ex", "ore_model_destroy", "ore_model_set_fusion", "ore_model_input_dims",
     "ore_model_output_elems", "ore_model_run", "ore_model_read_value", "ore_model_autotune",
     "ore_model_step_tile", "ore_model_set_step_tile", "ore_model_step_mfma_flops", "ore_model_set_streams",
@@ -113,6 +115,12 @@ def load():
         "ore_model_set_input_norm": (i32, [vp, F32P, F32P, i32, i32]),
         "ore_model_run_u8": (i32, [vp, vp, i64, vp]),
         "ore_model_graph_capture_u8": (i32, [vp, vp, i64, vp]),
+        "ore_topk_f32": (i32, [vp, T, i32, vp, vp]),
+        "ore_model_set_topk": (i32, [vp, i32]),
+        "ore_model_classify": (i32, [vp, vp, i64, vp, vp]),
+        "ore_model_classify_u8": (i32, [vp, vp, i64, vp, vp]),
+        "ore_model_graph_capture_classify": (i32, [vp, vp, i64, vp, vp]),
+        "ore_model_graph_capture_classify_u8": (i32, [vp, vp, i64, vp, vp]),
         "ore_model_parse": (i32, [ctypes.c_char_p, ctypes.c_size_t]),
         "ore_model_load": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, ctypes.POINTER(vp)]),
         "ore_model_load_ex": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, i32, ctypes.POINTER(vp)]),

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, OreError, PoolAttrs, Tensor, check, load
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "topk", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -269,6 +269,25 @@ def preprocess_u8(ctx: Context, x, scale=None, shift=None, reverse_channels: boo
     return y
 
 
+def topk(ctx: Context, x, k: int):
+    """ore_topk_f32 (extension): the k best elements of every row of x [rows, ...] (the row is the flattened
+    rest), as (values float32 [rows, k], indices int32 [rows, k]).  Larger first, equal values by lower index,
+    NaNs last: np.argsort(-x, axis=1, kind="stable")[:, :k].  1 <= k <= min(row length, 64)."""
+    torch = _torch()
+    d = _desc(x)
+    rows = int(x.shape[0])
+    D = 1
+    for s in x.shape[1:]:
+        D *= int(s)
+    if not 1 <= int(k) <= min(D, 64):
+        raise OreError(1, f"k = {k} outside 1..{min(D, 64)} (min(row length, 64))")
+    values = torch.empty((rows, int(k)), dtype=torch.float32, device=x.device)
+    indices = torch.empty((rows, int(k)), dtype=torch.int32, device=x.device)
+    check(load().ore_topk_f32(ctx.h, ctypes.byref(d), int(k), ctypes.c_void_p(values.data_ptr()),
+                              ctypes.c_void_p(indices.data_ptr())), ctx.h)
+    return values, indices
+
+
 # ------------------------------------------------------------------------------ graph walker
 class Model:
     """ore_model: the device-resident walker over one ONNX graph."""
@@ -299,6 +318,7 @@ class Model:
         e = ctypes.c_int64()
         check(load().ore_model_output_elems(self.h, ctypes.byref(e)), ctx.h)
         self.output_elems = e.value
+        self.topk = 1  # k of the classify entries (set_topk)
 
     def set_fusion(self, flags: int):
         check(load().ore_model_set_fusion(self.h, int(flags)), self.ctx.h)
@@ -383,6 +403,92 @@ class Model:
         check(load().ore_model_graph_capture_u8(self.h, ctypes.c_void_p(x.data_ptr()), int(n),
                                                 ctypes.c_void_p(out.data_ptr())), self.ctx.h)
         return out
+
+    def set_topk(self, k: int):
+        """ore_model_set_topk: how many classes per image classify* / capture_classify* keep,
+        1 <= k <= min(output_elems, 64); default 1."""
+        kmax = min(int(self.output_elems), 64)
+        if not 1 <= int(k) <= kmax:
+            raise OreError(1, f"k = {k} outside 1..{kmax} (min(output elems, 64))")
+        check(load().ore_model_set_topk(self.h, int(k)), self.ctx.h)
+        self.topk = int(k)
+
+    def _check_classify_in(self, x, u8: bool):
+        """The input checks of run_into (float32 [n, C, H, W]) or run_u8_into (uint8 [n, H, W, C]); returns n."""
+        torch = _torch()
+        if u8:
+            _check_u8(x, self.ctx.device)
+            n, h, w, c = (int(d) for d in x.shape)
+            if (c, h, w) != tuple(self.input_dims):
+                raise OreError(1, f"input dims (H, W, C) = {(h, w, c)} != model (C, H, W) = {self.input_dims}")
+        else:
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+                raise OreError(1, "x: expected a float32 CUDA tensor")
+            if x.device.index != self.ctx.device:
+                raise OreError(1, f"x: on cuda:{x.device.index}, the context is on cuda:{self.ctx.device}")
+            if not x.is_contiguous():
+                raise OreError(1, "x: expected a contiguous tensor")
+            n = int(x.shape[0])
+            if tuple(x.shape[1:]) != tuple(self.input_dims):
+                raise OreError(1, f"input dims {tuple(x.shape[1:])} != model {self.input_dims}")
+        if n > self.max_batch:
+            raise OreError(1, f"batch {n} exceeds max_batch {self.max_batch}")
+        return n
+
+    def _check_classify_out(self, n: int, scores, classes):
+        """The walker writes scores and classes through raw device pointers: contiguous CUDA tensors on this
+        context's device, float32 and int32, both [n, topk]."""
+        torch = _torch()
+        for name, t, dt, dn in (("scores", scores, torch.float32, "float32"), ("classes", classes, torch.int32, "int32")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+                raise OreError(1, f"{name}: expected a {dn} CUDA tensor")
+            if t.device.index != self.ctx.device:
+                raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{self.ctx.device}")
+            if not t.is_contiguous():
+                raise OreError(1, f"{name}: expected a contiguous tensor")
+            if tuple(t.shape) != (n, self.topk):
+                raise OreError(1, f"{name}: shape {tuple(t.shape)}, {n} images at k = {self.topk} need {(n, self.topk)}")
+
+    def _classify(self, entry, x, scores, classes, u8: bool):
+        n = self._check_classify_in(x, u8)
+        self._check_classify_out(n, scores, classes)
+        check(entry(self.h, ctypes.c_void_p(x.data_ptr()), int(n), ctypes.c_void_p(scores.data_ptr()),
+                    ctypes.c_void_p(classes.data_ptr())), self.ctx.h)
+        return scores, classes
+
+    def _classify_bufs(self, x, u8: bool):
+        torch = _torch()
+        n = self._check_classify_in(x, u8)
+        return (torch.empty((n, self.topk), dtype=torch.float32, device=x.device),
+                torch.empty((n, self.topk), dtype=torch.int32, device=x.device))
+
+    def classify_into(self, x, scores, classes):
+        """ore_model_classify: run_into that keeps the rows on the device and writes only the topk best
+        classes per image: scores float32 [n, topk] and classes int32 [n, topk], in topk()'s order
+        (asynchronous on the context stream)."""
+        return self._classify(load().ore_model_classify, x, scores, classes, False)
+
+    def classify(self, x):
+        return self.classify_into(x, *self._classify_bufs(x, False))
+
+    def classify_u8_into(self, x, scores, classes):
+        """ore_model_classify_u8: classify_into on a uint8 [n, H, W, C] batch (see run_u8_into)."""
+        return self._classify(load().ore_model_classify_u8, x, scores, classes, True)
+
+    def classify_u8(self, x):
+        return self.classify_u8_into(x, *self._classify_bufs(x, True))
+
+    def capture_classify(self, x, scores, classes):
+        """ore_model_graph_capture_classify: capture classify_into(x, scores, classes) as a HIP graph;
+        replay() runs and selects on whatever x holds then and refills scores and classes."""
+        self._graph_bufs = (x, scores, classes)  # the graph holds these pointers
+        return self._classify(load().ore_model_graph_capture_classify, x, scores, classes, False)
+
+    def capture_classify_u8(self, x, scores, classes):
+        """ore_model_graph_capture_classify_u8: as capture_classify on a uint8 batch, the conversion
+        included (see capture_u8)."""
+        self._graph_bufs = (x, scores, classes)
+        return self._classify(load().ore_model_graph_capture_classify_u8, x, scores, classes, True)
 
     def read_value(self, name: str) -> np.ndarray:
         dims = (ctypes.c_int64 * 4)()

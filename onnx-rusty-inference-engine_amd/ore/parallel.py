@@ -61,3 +61,16 @@ def run_sharded(run_fn: Callable, x_global, group=None):
     s, e = shard_bounds(x_global.shape[0], world, rank)
     local = run_fn(x_global[s:e])
     return gather_rows(local, x_global.shape[0], group)
+
+
+def classify_sharded(classify_fn: Callable, x_global, group=None):
+    """Run `classify_fn(x_slice) -> (scores [n_slice, k] float32, classes [n_slice, k] int32)` on this
+    rank's slice of x_global and return the gathered ([n_total, k], [n_total, k]) on every rank: n * k * 8
+    bytes per rank and step instead of run_sharded's n * D * 4.  Classes stay per-image class ids."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    n_total = x_global.shape[0]
+    s, e = shard_bounds(n_total, world, rank)
+    scores, classes = classify_fn(x_global[s:e])
+    return gather_rows(scores, n_total, group), gather_rows(classes, n_total, group)
