@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "ore_kernels.h"
+#include "ore_wino_geom.h"
 
 namespace ore {
 
@@ -492,8 +493,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino16_kernel(ConvParams p) {
 // Each position is the same c-ordered fma chain and the transforms the same add order as tiles 0-3:
 // bit-identical to them.
 constexpr int WM_KC = 8;      // input channels per K chunk (2 k-steps of 4)
-constexpr int WM_TILES = 64;  // 2x2 tiles per workgroup (16 per wave)
-constexpr int WM_CH = 32;     // output channels per workgroup
 constexpr int WM_ZL = 8;      // zero floats at the start of a staged channel (rows outside the image)
 
 __device__ __forceinline__ void wm_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, int voffset, int soffset) {
@@ -503,21 +502,10 @@ __device__ __forceinline__ void wm_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned l
 // geometry of the LDS kernel (host-computed)
 struct WmGeom {
   int TW, TPI;            // tiles per row / per image
-  float rTW, rTPI, rNMG;  // 1 / TW, 1 / TPI, 1 / nmg (wm_div)
+  float rTW, rTPI;        // 1 / TW, 1 / TPI (wm_div: wm_groups checks the tile and workgroup counts)
   int CS;                 // LDS floats per staged channel: zero block + the longest run set + slack (= 32 mod 64)
-  int ntg;                // tile groups of WM_TILES
-  int mbs;                // 32-channel m-blocks per workgroup (its m-group)
-  int nmg;                // m-groups per tile group = ceil(mtiles / mbs)
+  WmGroups gr;            // workgroup -> (tile group, m-blocks), ore_wino_geom.h
 };
-
-// n / d for 0 <= n < 2^22 (wm_geom checks the workgroup and tile counts) from a float reciprocal rd = 1 / d:
-// the float quotient is within (n / d) 2^-23 < 1 / (2 d) of n / d, so the truncation is the quotient or one
-// below, fixed by the remainder
-__device__ __forceinline__ int wm_div(int n, int d, float rd) {
-  int q = (int)((float)n * rd);
-  q += n - q * d >= d ? 1 : 0;
-  return q;
-}
 
 // rows of image `img` staged for the tile group [t0, t1]: [rs, re], clamped to the image
 __host__ __device__ __forceinline__ void wm_rows(int img, int img0, int ty0, int img1, int ty1, int H, int* rs, int* re) {
@@ -549,20 +537,28 @@ static int wm_group_floats(long long t0, long long T, int TPI, int TW, int H, in
 // (Measured and rejected, round 6: 8-wave workgroups of 128 tiles, one per CU, whose two waves per SIMD share one
 // staged copy of each chunk -- half the DMA pieces per wave, but both partners of a SIMD then meet at every
 // barrier: fire8 297 -> 342 us, profiles/r06_wino_ablations.txt.)
+// Round 7: a launch mixes m-groups of mbs blocks with single-block workgroups at the end of every XCD's range
+// (ore_wino_geom.h), and a chunk issues the next stage's U pieces between its two k-steps instead of in one burst
+// with the window pieces at its top (profiles/r07_wino_dma_groups.txt).  Both only regroup work or reorder issue.
+
+// The stores every epilogue issues per wave, whatever the plane: fragments x channel pairs x halves x tile rows.
+// A PRE chunk waits for the DMAs issued ahead of them by this count (vmcnt is in issue order)
+constexpr int WM_EPI_FRAGS = 2, WM_EPI_PAIRS = 2, WM_EPI_HALVES = 2, WM_EPI_ROWS = 2;
+constexpr int WM_EPI_STORES = WM_EPI_FRAGS * WM_EPI_PAIRS * WM_EPI_HALVES * WM_EPI_ROWS;
+static_assert(WM_EPI_STORES <= 63, "s_waitcnt vmcnt is a 6-bit count");
+
 template <int NDMA, bool RELU>  // NDMA: 256-float DMA pieces per staged channel (ceil(longest run set / 256))
 __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom g) {
   constexpr int NW = 4, TILES = WM_TILES;
   extern __shared__ __attribute__((aligned(16))) float wm_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // block -> (tile group, m-group), the m-groups of a tile group consecutive (one XCD: they share the staged
-  // rows in L2)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, rr8 = nwg & 7;
-  const int wgid = (xcd < rr8 ? xcd * (q8 + 1) : rr8 * (q8 + 1) + (xcd - rr8) * q8) + (bid >> 3);
-  // (integer divisions by reciprocals: the wave-uniform ones back to scalars by readfirstlane)
-  const int tgi = __builtin_amdgcn_readfirstlane(wm_div(wgid, g.nmg, g.rNMG)), mg = wgid - tgi * g.nmg;
-  const int mb0 = mg * g.mbs, mb1 = min(p.mtiles, mb0 + g.mbs);
+  // block -> (tile group, m-blocks): wm_wg_map (integer divisions by reciprocals: the wave-uniform ones back to
+  // scalars by readfirstlane)
+  const WmWg wg = wm_wg_map(g.gr, (int)blockIdx.x);
+  const int tgi = __builtin_amdgcn_readfirstlane(wg.tg);
+  const int mb0 = __builtin_amdgcn_readfirstlane(wg.mb0), mb1 = __builtin_amdgcn_readfirstlane(wg.mb1);
+  if (mb0 >= mb1) return;  // a spare workgroup of a shorter XCD range (block-uniform, before any barrier)
   const int mw0 = mb0 * WM_CH, nch = (mb1 - mb0) * WM_CH;  // the workgroup's channels [mw0, mw0 + nch)
   const int T = p.N * g.TPI;
   const int t0 = tgi * TILES, t1 = min(T, t0 + TILES) - 1;
@@ -634,23 +630,35 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
   const int uoff = (uq * p.Mp + (lane & 31)) * 16;  // the block's first channel goes in the scalar offset
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)wm_lds;
   const int nchunks = p.C / WM_KC;  // even (C % 16 == 0): chunk 0 of every block uses stage 0
-  // chunk kc's windows and U of channels [m0, m0 + 32) -> stage st
-  auto stage = [&](int kc, int m0, int st) __attribute__((always_inline)) {
-    const unsigned sb = lds0 + (unsigned)(st * SS) * 4;
+  // chunk kc's windows and U of channels [m0, m0 + 32) -> stage st; a wave's share is NDMA window pieces of each
+  // of its two channels (stage_win) and four U pieces (stage_u)
+  // (a piece's LDS address and scalar offset are a per-wave base plus multiples of CS, x_ps or Mp.  The bases pass
+  // through an empty asm at every use: left to itself the compiler hoists every piece's address and strength-
+  // reduces every piece's offset over the chunks, some thirty scalars more than there are scalar registers; the
+  // overflow went to vector registers and from there to scratch, and each reload in the MFMA stream waited for
+  // the DMAs in flight)
+  const int xps4 = p.x_ps * 4;
+  const int w_lds = (int)lds0 + (wave * g.CS + WM_ZL) * 4, w_so = wave * xps4 - 4 * (wave & 1);  // odd channels: one float early (>= 0)
+  const int u_lds = (int)lds0 + (WM_KC * g.CS + (wave >> 1) * 512 + (wave & 1) * 256) * 4, u_so = (wave >> 1) * 64 * p.Mp;
+  auto stage_win = [&](int kc, int st) __attribute__((always_inline)) {
+    int bw = w_lds + st * SS * 4, sw = kc * WM_KC * xps4 + w_so;
+    asm volatile("" : "+s"(bw), "+s"(sw));
 #pragma unroll
-    for (int h = 0; h < 8 / NW; ++h) {
-      const int cc = wave + NW * h;
-      const int so = (kc * WM_KC + cc) * p.x_ps * 4 - 4 * (cc & 1);  // odd channels: one float early (>= 0)
+    for (int h = 0; h < 8 / NW; ++h)  // channel wave + NW h
 #pragma unroll
       for (int gi = 0; gi < NDMA; ++gi)
-        if (voff[gi] >= 0) wm_dma16(xr, sb + (cc * g.CS + WM_ZL + 256 * gi) * 4, voff[gi], so);
-    }
+        if (voff[gi] >= 0) wm_dma16(xr, (unsigned)(bw + h * NW * g.CS * 4 + 1024 * gi), voff[gi], sw + h * NW * xps4);
+  };
+  auto stage_u = [&](int kc, int m0, int st) __attribute__((always_inline)) {
+    int bu = u_lds + st * SS * 4, su = (kc * WM_KC * 4 * p.Mp + m0) * 16 + u_so;
+    asm volatile("" : "+s"(bu), "+s"(su));
 #pragma unroll
-    for (int v = 0; v < 16 / NW; ++v) {
-      const int d = wave + NW * v, cc = d >> 1;
-      wm_dma16(ur, sb + (WM_KC * g.CS + (cc * 4 + 2 * (d & 1)) * 128) * 4, uoff,
-               ((kc * WM_KC + cc) * 4 * p.Mp + m0) * 16);
-    }
+    for (int v = 0; v < 16 / NW; ++v)  // U piece d = wave + NW v: channel d >> 1, quads 2 (d & 1), 2 (d & 1) + 1
+      wm_dma16(ur, (unsigned)(bu + v * (NW / 2) * 2048), uoff, su + v * (NW / 2) * 64 * p.Mp);
+  };
+  auto stage = [&](int kc, int m0, int st) __attribute__((always_inline)) {
+    stage_win(kc, st);
+    stage_u(kc, m0, st);
   };
 
   // accumulators: no zeroing -- each block's first k-step takes C = 0 (an inline operand of the MFMA; 128
@@ -679,19 +687,18 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
     wg_input_transform_pk(d, v);
   };
   // one chunk (two k-steps of 4 channels) of the block at m0; FIRST: chunk 0, its first k-step starts the
-  // accumulators.  It first stages the next job: chunk kc + 1 of this block, or chunk 0 of the next block
-  // (more), or nothing
+  // accumulators.  With `next` it stages the next job (chunk nkc of the block at nm0: this block's next chunk or
+  // the next block's chunk 0): the window pieces at its top, ahead of the LDS reads, and the U pieces in the
+  // VALU-only transform between its two k-steps (profiles/r07_wino_dma_groups.txt; the workgroup's last chunk has
+  // no next job -- a runtime flag: a second instance of the chunk for it cost 140 spilled registers).
   // PRE: chunk 0 of a block after the first, whose next job (chunk 1) was staged before the previous block's
   // epilogue (see the block loop)
-  auto chunk = [&](int kc, int m0, bool more, auto first, auto stc, auto prec) __attribute__((always_inline)) {
+  auto chunk = [&](int kc, int m0, bool next, int nkc, int nm0, auto first, auto stc, auto prec) __attribute__((always_inline)) {
     constexpr bool FIRST = decltype(first)::value;
     constexpr int st = decltype(stc)::value;  // kc & 1, a constant: the stage's LDS bases are loop-invariant
     constexpr bool PRE = decltype(prec)::value;
     if constexpr (!PRE) {
-      if (kc + 1 < nchunks)
-        stage(kc + 1, m0, st ^ 1);
-      else if (more)
-        stage(0, m0 + WM_CH, st ^ 1);
+      if (next) stage_win(nkc, st ^ 1);
     }
     const int sto0 = st * SS * 4, sto1 = sto0 + 4 * g.CS * 4;  // k-step 1: channels 4 .. 7 of the chunk
     wg_floatx4 ua[2][4];
@@ -717,6 +724,10 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
       for (int f = 0; f < 2; ++f) ua[f][q] = load_u(sto0 + 4 * 512 * 4, f, q);
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (!PRE) {
+      if (next) stage_u(nkc, nm0, st ^ 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     xform(d1, v);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -727,9 +738,9 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
           acc[4 * q + j][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[f][q][j], v[2 * q + (j >> 1)][j & 1], acc[4 * q + j][f], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     // this wave's DMAs of the next job have landed (vmcnt counts DMAs and stores in issue order: after an
-    // epilogue, whose >= 16 stores followed them, the stores need not have completed)
+    // epilogue, whose WM_EPI_STORES stores followed them, the stores need not have completed)
     if constexpr (PRE)
-      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WM_EPI_STORES) : "memory");
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // ... every wave's, and every wave is done reading stage st
@@ -754,8 +765,8 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
   const bool fast = __builtin_amdgcn_ballot_w64(w.tok && !w.c1ok) == 0;
   const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, (short)0, 0x7FFFFFF0, 0x00020000);
   typedef int wg_i2 __attribute__((ext_vector_type(2)));
-  // (an epilogue issues 16 8-B stores per wave, 32 stores with the right-edge ones: the vmcnt(16) of the
-  // next chunk relies on >= 16)
+  // (an epilogue issues WM_EPI_STORES 8-B stores per wave, twice as many with the right-edge ones: the
+  // vmcnt(WM_EPI_STORES) of the next chunk relies on at least that many)
   // the output transform and bias of channels (e, e + 1) on packed f32 (acc[xi][f] holds e = 0 .. 3 in
   // consecutive registers), the same adds in the same order as wg_store_t, then the stores; MOK: channel
   // checks (a partial last block)
@@ -767,16 +778,16 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
     for (int f = 0; f < 2; ++f)
       bv[f] = *reinterpret_cast<const wg_floatx4*>(wm_lds + 2 * SS + (m0 - mw0) + 16 * f + 4 * lk);
 #pragma unroll
-    for (int f = 0; f < 2; ++f)
+    for (int f = 0; f < WM_EPI_FRAGS; ++f)
 #pragma unroll
-      for (int ep = 0; ep < 4; ep += 2) {
+      for (int ep = 0; ep < 2 * WM_EPI_PAIRS; ep += 2) {
         wg_f2 mx[16], y[4];
 #pragma unroll
         for (int xi = 0; xi < 16; ++xi) mx[xi] = ep == 0 ? acc[xi][f].xy : acc[xi][f].zw;
         wg_output_transform_pk(mx, y);
         const wg_f2 b2 = {bv[f][ep], bv[f][ep + 1]};
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < WM_EPI_HALVES; ++h) {
           float o[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
@@ -790,6 +801,9 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
             const bool mok = c + 4 * lk < p.M;
             a0 = mok ? a0 : oob; a1 = mok ? a1 : oob; e0 = mok ? e0 : oob; e1 = mok ? e1 : oob;
           }
+          // WM_EPI_ROWS unconditional stores per (fragment, channel pair, half): the count a PRE chunk waits by
+          static_assert(WM_EPI_ROWS == 2 && WM_EPI_FRAGS == 2 && WM_EPI_PAIRS == 2 && WM_EPI_HALVES == 2,
+                        "WM_EPI_STORES must equal the stores this epilogue always issues");
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(wg_i2, (wg_f2){o[0], o[1]}), yr, a0, soff, 0);
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(wg_i2, (wg_f2){o[2], o[3]}), yr, a1, soff, 0);
           if (!fast) {  // tiles at the right edge of an odd-width plane: their first column only
@@ -810,15 +824,16 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
     const int m0 = mb * WM_CH;
     const bool more = mb + 1 < mb1;
     if (mb == mb0)
-      chunk(0, m0, more, std::true_type{}, st0{}, pre0{});
+      chunk(0, m0, true, 1, m0, std::true_type{}, st0{}, pre0{});
     else
-      chunk(0, m0, more, std::true_type{}, st0{}, pre1{});
+      chunk(0, m0, false, 1, m0, std::true_type{}, st0{}, pre1{});
     int kc = 1;
     for (; kc + 1 < nchunks; kc += 2) {  // chunk pairs: odd, even
-      chunk(kc, m0, more, std::false_type{}, st1{}, pre0{});
-      chunk(kc + 1, m0, more, std::false_type{}, st0{}, pre0{});
+      chunk(kc, m0, true, kc + 1, m0, std::false_type{}, st1{}, pre0{});
+      chunk(kc + 1, m0, true, kc + 2, m0, std::false_type{}, st0{}, pre0{});
     }
-    chunk(kc, m0, more, std::false_type{}, st1{}, pre0{});  // the last, odd chunk (nchunks is even)
+    // the last, odd chunk (nchunks is even) stages the next block's chunk 0
+    chunk(kc, m0, more, 0, m0 + WM_CH, std::false_type{}, st1{}, pre0{});
     if (more) stage(1, m0 + WM_CH, 1);  // the next block's chunk 1
     if (m0 + WM_CH <= p.M)
       epilogue(m0, std::false_type{});
@@ -827,10 +842,19 @@ __global__ __launch_bounds__(256, 2) void conv_winol_kernel(ConvParams p, WmGeom
   }
 }
 
-// workgroups the m-grouping keeps at least (4 per resident slot of a 256-CU part at two per CU): the blocks of
-// a tile group are shared out only as far as the launch stays this wide
-constexpr long long WM_MIN_WG = 2048;
-constexpr int WM_MAX_MBS = 8;
+// the device's CU count (wm_groups balances the launch over them), looked up once per device
+static int wm_device_cus() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::atomic<int>& c = cus[dev & 63];
+  int v = c.load(std::memory_order_relaxed);
+  if (v <= 0) {
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    c.store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
 
 // the LDS kernel's geometry; false when the layer does not fit it
 static bool wm_geom(const ConvParams& p, WmGeom* g, size_t* lds, int* ndma) {
@@ -842,24 +866,15 @@ static bool wm_geom(const ConvParams& p, WmGeom* g, size_t* lds, int* ndma) {
   g->rTW = 1.0f / (float)g->TW;
   g->rTPI = 1.0f / (float)g->TPI;
   const long long T = (long long)p.N * g->TPI;
-  if (T >= (1LL << 22)) return false;  // wm_div's range (4M tiles: 5,700 images at 54 x 54)
-  g->ntg = (int)((T + tiles - 1) / tiles);
-  // m-blocks per workgroup: the largest divisor of the block count that keeps >= WM_MIN_WG workgroups
-  const int mtiles = (p.M + WM_CH - 1) / WM_CH;
-  g->mbs = 1;
-  for (int b = 2; b <= std::min(mtiles, WM_MAX_MBS); ++b)
-    if (mtiles % b == 0 && (long long)g->ntg * (mtiles / b) >= WM_MIN_WG) g->mbs = b;
-  g->nmg = (mtiles + g->mbs - 1) / g->mbs;
-  g->rNMG = 1.0f / (float)g->nmg;
-  if ((long long)g->ntg * g->nmg >= (1LL << 22)) return false;  // wm_div's range for the workgroup id
+  if (!wm_groups(T, p.M, wm_device_cus(), &g->gr)) return false;
   // group starts repeat modulo TPI (period TPI / gcd(tiles, TPI)): every case is among the first TPI
   int tmax = 0;
-  const long long ng = std::min<long long>(g->ntg, g->TPI);
+  const long long ng = std::min<long long>(g->gr.ntg, g->TPI);
   for (long long gi = 0; gi < ng; ++gi)
     tmax = std::max(tmax, wm_group_floats(gi * tiles, T, g->TPI, g->TW, p.H, p.W, tiles));
   *ndma = (tmax + 255) / 256;
   g->CS = (WM_ZL + tmax + 5 + 31) / 64 * 64 + 32;  // + 1: odd channels' shift, + 4: the last window's overrun
-  *lds = (size_t)2 * WM_KC * (g->CS + 512) * 4 + (size_t)g->mbs * WM_CH * 4;  // two stages + the biases
+  *lds = (size_t)2 * WM_KC * (g->CS + 512) * 4 + (size_t)g->gr.mbs * WM_CH * 4;  // two stages + a large workgroup's biases
   return *ndma <= 8 && *lds <= 160 * 1024;
 }
 
@@ -871,7 +886,7 @@ static void launch_wm_r(const ConvParams& p0, const WmGeom& g, size_t lds, hipSt
     static std::atomic<unsigned long long> raised{0};
     ore_raise_lds_once(raised, reinterpret_cast<const void*>(&conv_winol_kernel<NDMA, RELU>), 160 * 1024);
   }
-  hipLaunchKernelGGL((conv_winol_kernel<NDMA, RELU>), dim3((unsigned)(g.ntg * g.nmg)), dim3(256), lds, s, p, g);
+  hipLaunchKernelGGL((conv_winol_kernel<NDMA, RELU>), dim3((unsigned)g.gr.grid), dim3(256), lds, s, p, g);
 }
 
 template <int NDMA>
