@@ -1,5 +1,5 @@
-// Host-ASan / UBSan driver for the planner (csrc/ore_model.cpp: ore_model_load_ex, plan(), the fusion
-// passes, the arena and the walker's host side), run on the GPU box (the planner needs a HIP device;
+// Host-ASan / UBSan driver for the planner (csrc/ore_model.cpp: ore_model_load_ex; csrc/ore_plan.cpp: plan(),
+// the fusion passes, the arena; and the walker's host side), run on the GPU box (the planner needs a HIP device;
 // device code is built normally).  Through the C ABI only (include/ore.h):
 //   model_fuzz MNIST.onnx SQUEEZENET.onnx ITERATIONS
 // 1. MNIST-8 and SqueezeNet-1.0 load (f32 at batch 1, 4 and 700 -- 700 > run_batch of the default
