@@ -206,7 +206,14 @@ ore_status ore_model_parse(const void* onnx_bytes, size_t len);
  * Relu / Concat / Dropout are f16, Conv accumulates in f32 on the f16 matrix cores (bias and Relu
  * in f32, rounded once), GlobalAveragePool sums f16 inputs in f32, and Softmax, Add and MatMul
  * stay f32 (Add / MatMul / Softmax on an f16 value is rejected).  The model input and
- * graph.output[0] stay f32 (an f16 graph output is rejected). */
+ * graph.output[0] stay f32 (an f16 graph output is rejected).
+ * One conv layer is y = RNE_f16(relu?(sum_k f16(x_k) f16(w_k) [f32 accumulate] + b_f32)): the operands are
+ * rounded to nearest even, their products are exact in f32, and tests/test_f16_parity_gpu.py holds every
+ * output to the correctly rounded f16 of a value within 2e-6 * (sum |w x| + |b|) of the float64 sum
+ * (measured accumulation error: at most 5.4e-8 of that magnitude).  Outputs past 65504 in magnitude
+ * are +-inf: the kernels do a plain (_Float16) cast and no clamp.  f16 subnormals are kept -- as
+ * weights, as activations read by the matrix cores and as outputs (gradual underflow, nothing is
+ * flushed; measured on gfx950). */
 #define ORE_LOAD_F16 1
 /* ORE_LOAD_NO_WINOGRAD: an f32 model runs its 3x3 / stride-1 / pad-1 convs (SqueezeNet's
  * expand3x3) on the direct kernels only, every output in the reference's k order.  By default (f32
