@@ -464,19 +464,18 @@ static void launch_conv_epool_cfg(const ConvParams& p0, hipStream_t s) {
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, 1, 4, BK, BGATHER, 1, 1>), grid, block, 0, s, p);
 }
 
-void launch_conv_epool(const ConvParams& p, hipStream_t s) {
+int launch_conv_epool(const ConvParams& p, hipStream_t s) {
   int v = p.ep_variant;
   if (p.sq1) {  // the fused squeeze: the band walker (variant 8) or the window kernel
     if (v == EPOOL_BAND_VARIANT && p.wc1 && conv_band_pool_f32_eligible(p, p.sq1)) {
       launch_conv_band_pool_f32(p, p.wc1, *p.sq1, s);
-      last_conv_tile = EPOOL_BAND_TILE;
-    } else if (p.wc1 && conv_win_pool_f32_eligible(p, p.sq1)) {
-      launch_conv_win_pool_f32(p, p.wc1, p.sq1, s);
-      last_conv_tile = EPOOL_WIN_TILE;
-    } else {
-      last_conv_tile = -2;  // declined: the walker reports an error
+      return EPOOL_BAND_TILE;
     }
-    return;
+    if (p.wc1 && conv_win_pool_f32_eligible(p, p.sq1)) {
+      launch_conv_win_pool_f32(p, p.wc1, p.sq1, s);
+      return EPOOL_WIN_TILE;
+    }
+    return -2;  // declined: the walker reports an error
   }
   // auto: a walker block owns a whole image (x its m tile), so below ~one block per CU (batch < 128
   // for conv1) the patch kernel's many small tiles fill the chip better
@@ -486,17 +485,14 @@ void launch_conv_epool(const ConvParams& p, hipStream_t s) {
   if (v == EPOOL_WIN_VARIANT) {
     if (p.wc1 && conv_win_pool_f32_eligible(p)) {
       launch_conv_win_pool_f32(p, p.wc1, nullptr, s);
-      last_conv_tile = EPOOL_WIN_TILE;
-      return;
+      return EPOOL_WIN_TILE;
     }
     v = 1;
   }
   if (v >= 2 && conv_pool_stream_eligible(p, v)) {
     launch_conv_pool_stream(p, v, s);
-    last_conv_tile = EPOOL_TILE_BASE + v;
-    return;
+    return EPOOL_TILE_BASE + v;
   }
-  last_conv_tile = EPOOL_TILE_BASE + 1;
   // rows per tile: 96 when it divides the channel count (conv1's 96), else 128, or 32 for M <= 32
   if (p.M <= 32)
     launch_conv_epool_cfg<32>(p, s);
@@ -504,6 +500,7 @@ void launch_conv_epool(const ConvParams& p, hipStream_t s) {
     launch_conv_epool_cfg<96>(p, s);
   else
     launch_conv_epool_cfg<128>(p, s);
+  return EPOOL_TILE_BASE + 1;
 }
 
 // Block tiles, chosen per layer to minimise the padded output channels (MFMA work on rows
@@ -525,7 +522,6 @@ static const int CFG_BM[4] = {128, 96, 64, 32};
 
 ConvPlan plan_conv(int M, int C, int H, int W, int kh, int kw, int sh, int sw, int pt, int pl, int Ho, int Wo,
                    bool is1x1, bool f16, int xmode, bool wino, int forced) {
-  (void)pt;
   ConvPlan pln{};
   if (wino && !f16 && conv_wino_geometry(C, kh, kw, sh, sw, pt, pl, H, W, Ho, Wo)) {
     pln.wino = 1;
@@ -573,29 +569,24 @@ void launch_pack(const float* w, bool kmajor_src, int M, int C, int kh, int kw, 
   launch_pack_weights(w, kmajor_src, M, C * kh * kw, pln.Mp, wp, s);
 }
 
-thread_local int last_conv_tile = -1;
-
-void launch_conv(const ConvParams& p, const ConvPlan& pln, hipStream_t s) {
-  last_conv_tile = pln.cfg;
+int launch_conv(const ConvParams& p, const ConvPlan& pln, hipStream_t s) {
   if (pln.wino) {  // the caller (run_conv) keeps x_bytes within the buffer range
-    int t = pln.cfg - WINO_TILE_BASE;  // the caller (run_conv) checked conv_wino_eligible
-    last_conv_tile = WINO_TILE_BASE + t;
+    const int t = pln.cfg - WINO_TILE_BASE;  // the caller (run_conv) checked conv_wino_eligible
     launch_conv_wino(p, t, s);
-    return;
+    return pln.cfg;
   }
   if (pln.f16) {
     launch_conv_f16(p, pln.cfg, pln.xmode, s);
-    return;
+    return pln.cfg;
   }
   if (pln.cfg >= CONV_TILE_STREAM) {
     if (conv_stream_eligible(p, pln.cfg)) {
       launch_conv_stream(p, pln.cfg, s);
-      return;
+      return pln.cfg;
     }
-    ConvPlan q = pln;  // not a stream geometry: the LDS-staged kernel
+    ConvPlan q = pln;  // not a stream geometry: the LDS-staged kernel, reported as tile 0
     q.cfg = 0;
-    launch_conv(p, q, s);
-    return;
+    return launch_conv(p, q, s);
   }
   switch (pln.cfg) {
     case 0: launch_conv_cfg<128, 128, 2, 2>(p, s); break;
@@ -603,6 +594,7 @@ void launch_conv(const ConvParams& p, const ConvPlan& pln, hipStream_t s) {
     case 2: launch_conv_cfg<64, 128, 2, 2>(p, s); break;
     default: launch_conv_cfg<32, 256, 1, 4>(p, s); break;
   }
+  return pln.cfg;
 }
 
 }  // namespace ore

@@ -87,64 +87,30 @@ struct Window {
 ore_status resolve_window(ore_ctx* ctx, int auto_pad, const int64_t* pads, int n_pads, int64_t H, int64_t W,
                           int64_t kh, int64_t kw, int64_t sh, int64_t sw, Window* out);
 
-// ---------------------------------------------------------------- launches over resolved geometry
-// Kernel plan of a conv (or MatMul as a 1x1 conv) over resolved geometry.
-ConvPlan conv_plan(int64_t M, int64_t C, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
-                   const Window& win, bool f16 = false, int xmode = 0, bool wino = false,
-                   int forced = -1);
-// wp: weights packed by launch_pack for plan `pln`
-// ktab: gather table (launch_ktab) for non-1x1 geometry on the gather kernel
-ore_status run_conv(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                    int64_t x_nstride, const float* wp, const int2* ktab, int64_t M, int64_t kh, int64_t kw,
-                    const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu, float* y,
-                    int64_t y_nstride, int64_t x_ps = 0, int64_t y_ps = 0,  // plane strides, 0 = dense
-                    int x_es = 4);  // input element bytes (f32 plans only)
-// the MaxPool fused into an f16 conv's epilogue (ORE_FUSE_CONV_POOL; 3x3 / stride 2)
-struct F16Epool {
-  int64_t kh, kw, sh, sw;
-  Window win;  // the pool's window over the conv output
+// ---------------------------------------------------------------- runners over resolved geometry
+// The layer between a planned Step (or a per-op entry) and the kernels' launch_* entry points: each
+// run_* checks its limits, fills the kernel's parameter struct and launches, in image chunks where
+// the batch's extent needs it (ore_chunk.h).
+
+// An activation as a runner takes it: storage of es-byte elements, pointer to image 0, elements
+// between images, and the channel-plane stride (NCHW) or pixel stride (NHWC); ps 0 = dense.
+struct Ref { float* p; int64_t nstride; int64_t ps; int es; };
+// ps resolved, once per layout: a plane of `plane` elements (NCHW), a pixel of C channels (NHWC)
+inline int64_t plane_stride(const Ref& r, int64_t plane) { return r.ps ? r.ps : plane; }
+inline int64_t pixel_stride(const Ref& r, int64_t C) { return r.ps ? r.ps : C; }
+
+// a conv (or MatMul as a 1x1 conv) over x [C][H][W] per image
+struct ConvGeom {
+  int64_t C, H, W, M, kh, kw, sh, sw;
+  Window win;
+  bool relu;
 };
-// f16 first conv + pooled epilogue straight from the f32 NCHW input (ore_conv1_f16.hip) when its
-// geometry allows; *ran = false (and ORE_OK) otherwise, for the two-launch path.
-ore_status run_conv_pair_pool_f16(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t H,
-                                  int64_t W, int64_t x_nstride, int64_t x_ps, const void* wp, int64_t M, int64_t kh,
-                                  int64_t kw, const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu,
-                                  void* y, int64_t y_nstride, int64_t y_ps, const F16Epool& ep, bool* ran,
-                                  const C1Squeeze* sq = nullptr);
-// f16 plan (f16 models): y is NHWC f16 with pixel stride y_ps; x is the f32 NCHW model input
-// (F16_X_NCHW32, plane stride x_ps) or NHWC f16 with pixel stride x_ps.  ktab per plan.xmode.
-// ep: the following MaxPool in the epilogue (y is then the pooled NHWC output)
-ore_status run_conv_f16(ore_ctx* ctx, const ConvPlan& pln, const void* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                        int64_t x_nstride, int64_t x_ps, const void* wp, const int2* ktab, int64_t M, int64_t kh,
-                        int64_t kw, const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu, void* y,
-                        int64_t y_nstride, int64_t y_ps, const F16Epool* ep = nullptr);
-// Conv (+ Relu) and the MaxPool (pkh x pkw, strides psh/psw, window pwin over the conv's Ho x Wo
-// output) in one launch: y is the pooled output (image stride y_nstride, plane stride y_ps)
-ore_status run_conv_epool(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                          int64_t x_nstride, int64_t x_ps, const float* wp, const int2* ktab, int64_t M, int64_t kh,
-                          int64_t kw, const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu,
-                          int64_t pkh, int64_t pkw, int64_t psh, int64_t psw, const Window& pwin, float* y,
-                          int64_t y_nstride, int64_t y_ps, const float* wc1 = nullptr,
-                          const C1SqueezeF32* sq1 = nullptr);
-// a fire module fused with the next squeeze (ORE_FUSE_FIRE, ore_fire.hip): x = S [C][H][W] (plane
-// stride x_ps), w1 / w3 in launch_fire_pack layout, ws the squeeze's launch_pack layout (row stride
-// Msp); y = S' [Ms][H][W] (plane stride y_ps, the column count per image)
-ore_status run_fire(ore_ctx* ctx, const float* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t x_nstride,
-                    int64_t x_ps, const float* w1, const float* b1, int64_t E1, const float* w3, const float* b3,
-                    int64_t E3, const float* ws, int64_t Msp, const float* bs, int64_t Ms, float* y, int64_t y_nstride,
-                    int64_t y_ps, const Window* pool = nullptr);
-// the f16 fused fire module (ore_fire_f16.hip): x = S, y = S' NHWC f16 (pixel strides x_cs / y_cs,
-// image strides in elements); w1 / w3 / ws in launch_fire_pack_f16 layout; pool: a 3x3 / stride-2
-// MaxPool (window over the H x W conv plane) between the Concat and the squeeze, y on its plane
-ore_status run_fire_f16(ore_ctx* ctx, const void* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t x_nstride,
-                        int64_t x_cs, const void* w1, const float* b1, int64_t E1, const void* w3, const float* b3,
-                        int64_t E3, const void* ws, const float* bs, int64_t Ms, void* y, int64_t y_nstride,
-                        int64_t y_cs, const Window* pool = nullptr);
-// pooled-epilogue tiling of a conv output (Ho x Wo) and its pool (3x3 / stride 2 only): *tr x *tc
-// tiles of 6 x 9 pooled outputs per image; returns the work factor tiles * CONV_EPOOL_BN / (Ho * Wo)
-// (the conv columns computed, recomputed overlap and padding included), 0 for other pools
-double epool_tile(int64_t Ho, int64_t Wo, int64_t pkh, int64_t pkw, int64_t psh, int64_t psw, const Window& pwin,
-                  int* tr, int* tc);
+// a MaxPool's kernel, strides and resolved window: a pool of its own (run_maxpool*), the pool in a conv's
+// epilogue (win over the conv output) or the pool in front of a 1x1 conv (run_conv_pool)
+struct PoolGeom {
+  int64_t kh, kw, sh, sw;
+  Window win;
+};
 // the pooled squeeze's recomputed expand1x1 (walker pass pool_expand): x's first E1 channels are
 // relu(w1 s + b1) of s [C1][pH][pW] (plane stride s_ps, image stride s_nstride), w1 K-major [k][w1_Mp]
 struct PoolExpand {
@@ -154,30 +120,82 @@ struct PoolExpand {
   int C1, E1, w1_Mp;
   int64_t s_ps, s_nstride;
 };
-// 1x1 conv over the 3x3 / stride-2 MaxPool (window pwin) of x [C][pH][pW] (plane stride x_ps) on
-// pool_conv1x1_f32_kernel: the pooled tensor is never materialised (walker pass fuse_pool_squeeze)
-ore_status run_conv_pool(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t pH,
-                         int64_t pW, int64_t x_nstride, int64_t x_ps, const Window& pwin, int64_t psh, int64_t psw,
-                         const float* wp, int64_t M, const float* bias, bool relu, float* y, int64_t y_nstride,
-                         int64_t y_ps, int x_es, const PoolExpand* pe = nullptr);
+// what a conv kernel reads besides x.  wp: weights packed by launch_pack for the plan (f16 plans: f16
+// storage); ktab: the gather table (launch_ktab / launch_ktab_nhwc) where the kernel gathers
+struct ConvOperands {
+  const float* wp;
+  const int2* ktab;
+  const float* bias;
+  // the fused forms' extras, null without them
+  const float* wc1 = nullptr;         // run_conv_epool: the weights again, for the window / band kernels (launch_pack_c1_f32)
+  const C1SqueezeF32* sq1 = nullptr;  // run_conv_epool: the next 1x1 conv fused in; y is then unused (p null)
+  const C1Squeeze* sq16 = nullptr;    // run_conv_pair_pool_f16: the same
+  const PoolExpand* pe = nullptr;     // run_conv_pool
+};
+// a conv runner's status and the tile id its last launch ran (-1: nothing launched, or a kernel without one)
+struct ConvRun {
+  ore_status st;
+  int tile;
+  ConvRun(ore_status s, int t = -1) : st(s), tile(t) {}
+};
+
+// Kernel plan of a conv (or MatMul as a 1x1 conv) over resolved geometry.
+ConvPlan conv_plan(int64_t M, int64_t C, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+                   const Window& win, bool f16 = false, int xmode = 0, bool wino = false, int forced = -1);
+// f32 plans, NCHW x and y
+ConvRun run_conv(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                 const ConvOperands& w);
+// f16 first conv + pooled epilogue straight from the f32 NCHW input (ore_conv1_f16.hip) when its
+// geometry allows; tile -1 (and ORE_OK) otherwise, for the two-launch path.  y: the pooled NHWC output
+ConvRun run_conv_pair_pool_f16(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N,
+                               const ConvGeom& g, const ConvOperands& w, const PoolGeom& ep);
+// f16 plan (f16 models): y is NHWC f16; x is the f32 NCHW model input (F16_X_NCHW32) or NHWC f16.
+// ktab per plan.xmode.  ep: the following MaxPool in the epilogue (y is then the pooled NHWC output;
+// that kernel has no tile id)
+ConvRun run_conv_f16(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                     const ConvOperands& w, const PoolGeom* ep = nullptr);
+// Conv (+ Relu) and the MaxPool ep (over the conv's Ho x Wo output) in one launch, f32: y is the pooled output
+ConvRun run_conv_epool(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                       const ConvOperands& w, const PoolGeom& ep);
+// the operands of a fire module fused with the next squeeze: S of C channels, e1 = Relu(W1 S + b1) (E1
+// channels), e3 = Relu(W3 * S + b3) (E3), S' = Relu(Ws [e1; e3] + bs) (Ms; 0: no squeeze, f16 only).
+// f32 (run_fire): w1 / w3 in launch_fire_pack layout, ws the squeeze's launch_pack layout of row stride
+// Msp; f16 (run_fire_f16): all three in launch_fire_pack_f16 layout
+struct FireOperands {
+  int64_t C, E1, E3, Ms, Msp;
+  const void *w1, *w3, *ws;
+  const float *b1, *b3, *bs;
+};
+// a fire module fused with the next squeeze (ORE_FUSE_FIRE, ore_fire.hip): x = S [C][H][W], y = S'
+// [Ms][H][W] (its plane stride is the column count per image); pool: a 3x3 / stride-2 MaxPool (window
+// over the H x W conv plane) between the Concat and the squeeze, y on its plane
+ore_status run_fire(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int64_t H, int64_t W, const FireOperands& f,
+                    const Window* pool = nullptr);
+// the f16 fused fire module (ore_fire_f16.hip): x = S, y = S' NHWC f16
+ore_status run_fire_f16(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int64_t H, int64_t W,
+                        const FireOperands& f, const Window* pool = nullptr);
+// pooled-epilogue tiling of a conv output (Ho x Wo) and its pool (3x3 / stride 2 only): *tr x *tc
+// tiles of 6 x 9 pooled outputs per image; returns the work factor tiles * CONV_EPOOL_BN / (Ho * Wo)
+// (the conv columns computed, recomputed overlap and padding included), 0 for other pools
+double epool_tile(int64_t Ho, int64_t Wo, int64_t pkh, int64_t pkw, int64_t psh, int64_t psw, const Window& pwin,
+                  int* tr, int* tc);
+// 1x1 conv over the MaxPool `pool` (3x3 / stride 2) of x [C][H][W] on pool_conv1x1_f32_kernel: the pooled
+// tensor is never materialised (walker pass fuse_pool_squeeze); g: the conv over x's planes, w.pe optional
+ore_status run_conv_pool(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                         const ConvOperands& w, const PoolGeom& pool);
 // packs w (and the gather table for an input of H x W) into the context scratch buffer;
 // returns the packed weights (or null with the error set), *ktab receives the table
 float* pack_to_scratch(ore_ctx* ctx, const ConvPlan& pln, const float* w, bool kmajor_src, int64_t M, int64_t C,
                        int64_t kh, int64_t kw, int64_t H, int64_t W, const int2** ktab);
 // bytes of packed weights + gather table for one conv
 size_t packed_bytes(const ConvPlan& pln);
-ore_status run_maxpool(ore_ctx* ctx, const float* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                       int64_t x_nstride, int64_t kh, int64_t kw, const Window& win, int64_t sh, int64_t sw,
-                       float* y, int64_t y_nstride, int64_t x_ps = 0, int64_t y_ps = 0,
-                       int es = 4);  // element bytes of x and y; ctx->pool_variant selects a kernel
+// x [C][H][W]: f32 NCHW (ctx->pool_variant selects a kernel) or, of 2-byte elements, NHWC f16 (f16 models)
+ore_status run_maxpool(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int64_t C, int64_t H, int64_t W,
+                       const PoolGeom& pool);
 // the geometry and normalisation of a uint8 [.,h,w,c] -> f32 NCHW conversion (ore_preprocess_u8 and the
 // model's _u8 entries): checks c, h, w and flags, and resolves the channel reversal into p->plane;
 // scale / shift: host arrays of c floats or null (1 / 0).  x, y, N and y_nstride are the caller's to set.
 ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const float* scale, const float* shift,
                           int32_t flags, PreprocParams* p);
-// MaxPool over NHWC f16 (f16 models); x_cs / y_cs: pixel strides
-ore_status run_maxpool_nhwc(ore_ctx* ctx, const void* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t x_nstride,
-                            int64_t x_cs, int64_t kh, int64_t kw, const Window& win, int64_t sh, int64_t sw, void* y,
-                            int64_t y_nstride, int64_t y_cs);
 
 }  // namespace ore

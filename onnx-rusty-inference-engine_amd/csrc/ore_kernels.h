@@ -1,5 +1,5 @@
 // Internal kernel launch interface (device pointers, resolved integer geometry).  The public
-// C ABI (include/ore.h) sits on top of this in ore_api.cpp.
+// C ABI (include/ore.h) sits on top of this in ore_ops.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -336,16 +336,19 @@ size_t conv_packed_bytes(const ConvPlan& pln);
 // packs ONNX weights [M][C][kh][kw] (or MatMul [K][M]) in the layout the plan's kernel reads
 void launch_pack(const float* w, bool kmajor_src, int M, int C, int kh, int kw, const ConvPlan& pln, float* wp,
                  hipStream_t s);
-void launch_conv(const ConvParams& p, const ConvPlan& pln, hipStream_t s);
-// Conv (+ Relu) with the following MaxPool in its epilogue (ConvParams ep_* set; f32)
-void launch_conv_epool(const ConvParams& p, hipStream_t s);
+// returns the tile id it ran: pln.cfg, or 0 for a streaming tile on a geometry that kernel does not take
+// (the LDS-staged kernel runs instead; ore_model_autotune skips candidates that fell back)
+int launch_conv(const ConvParams& p, const ConvPlan& pln, hipStream_t s);
+// Conv (+ Relu) with the following MaxPool in its epilogue (ConvParams ep_* set; f32); returns the tile id
+// it ran, or a negative value when the fused squeeze (p.sq1) fits neither of its kernels (nothing launched)
+int launch_conv_epool(const ConvParams& p, hipStream_t s);
 // Stride-2 Conv + Relu + 3x3 / stride-2 MaxPool walking the conv plane row-major with the pooled rows
 // in an LDS ring (ore_conv_pool.hip; conv1 + pool1): launch_conv_epool takes it when eligible.
 // variants (ConvParams::ep_variant): 1 = the patch kernel, 2 = walk 48 channels x 64 quads per block,
 // 3 = walk 96 channels x 128 quads, 4 = walk 64 x 64, 5 = 4 over 3 bands of pooled rows; 0 = the first
 // eligible of 3, 4, 2, 1 at batch >= 128, else 1.  A model sets the variant per step (autotune,
-// ore_model_set_step_tile with EPOOL_TILE_BASE + variant).  launch_conv_epool leaves last_conv_tile =
-// EPOOL_TILE_BASE + the variant run.
+// ore_model_set_step_tile with EPOOL_TILE_BASE + variant).  launch_conv_epool returns EPOOL_TILE_BASE +
+// the variant run.
 constexpr int EPOOL_TILE_BASE = 21;
 // variant 7 (ore_conv1_f32.hip): the first conv (7x7 / stride 2, C in {1, 3, 4}, 64 < M <= 128) with
 // its input window in LDS, weights packed by launch_pack_c1_f32 (ConvPlan::wc1); reported as tile
@@ -399,9 +402,6 @@ constexpr int CONV_TILE_STREAM = 12;
 constexpr int CONV_TILE_SP = 46, CONV_TILES_SP = 3;
 bool conv_stream_eligible(const ConvParams& p, int tile);
 void launch_conv_stream(const ConvParams& p, int tile, hipStream_t s);
-// the tile launch_conv actually ran last on this thread (a 1x1 tile on an ineligible geometry runs
-// tile 0); ore_model_autotune skips candidates that fell back
-extern thread_local int last_conv_tile;
 constexpr int CONV_TILES_F16 = 4;
 // 3x3 / stride-1 / pad-1 f32 conv by Winograd F(2x2, 3x3) on the f32 MFMA (ore_conv_wino.hip).  Tiles
 // WINO_TILE_BASE + 0..3 = 32 ch x 32 tiles (32x32x2 MFMA, ring 4 / 2), 32 x 16, 16 x 32 (16x16x4);

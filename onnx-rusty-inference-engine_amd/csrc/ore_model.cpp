@@ -391,111 +391,104 @@ struct MappedArena {
   }
 };
 
-ore_status launch_step(ore_model* m, const Step& s, int64_t n) {
+ConvGeom conv_geom(const Step& s) { return {s.C, s.H, s.W, s.M, s.kh, s.kw, s.sh, s.sw, s.win, s.relu}; }
+
+// an S_CONV step on the kernel its plan and fusions name
+ConvRun launch_conv_step(ore_model* m, const Step& s, int64_t n) {
+  ore_ctx* ctx = m->ctx;
+  const Ref x = ref_of(m, s.in0), y = ref_of(m, s.out);
+  const ConvGeom g = conv_geom(s);
+  ConvOperands w{s.wp, s.ktab, s.in2 >= 0 ? m->values[s.in2].cptr : nullptr, s.wc1};
+  const PoolGeom ep{s.ep.kh, s.ep.kw, s.ep.sh, s.ep.sw, s.ep.win};
+  // with the next 1x1 conv fused in (s.sq), out is that conv's output and the pooled conv's own is never stored
+  const Ref yc = s.sq.on ? Ref{nullptr, y.nstride, 0, y.es} : y;
+  // the one-launch f16 first conv + pool from the f32 input (plan.epv 1: the two-launch patch path)
+  if (s.plan.f16 && s.plan.xmode == F16_X_NHWC_PAIR && s.ep.on && (s.sq.on || s.plan.epv != 1)) {
+    const C1Squeeze sq{s.sq.w, s.sq.b, int(s.sq.M), y.p, y.nstride, int(pixel_stride(y, s.sq.M))};
+    if (s.sq.on) w.sq16 = &sq;
+    const ConvRun r = run_conv_pair_pool_f16(ctx, s.plan, x, yc, n, g, w, ep);
+    if (r.st != ORE_OK || r.tile >= 0) return r;  // ran: C1_POOL_F16_TILE or C1_BAND_F16_TILE
+    if (s.sq.on) return err(m, ORE_ERR_INVALID, "internal: the fused first conv + squeeze declined its launch");
+  }
+  if (s.plan.f16 && s.plan.xmode == F16_X_NHWC_PAIR) {
+    // convert the f32 NCHW input to NHWC f16 (4 channels per pixel), then gather
+    const int cs = 4;
+    launch_nchw_to_nhwc(x.p, m->xcvt, int(n), int(s.C), int(s.H * s.W), x.nstride, int(plane_stride(x, s.H * s.W)), cs,
+                        ctx->stream);
+    ORE_HIP_CHECK(ctx, hipGetLastError());
+    const Ref xc{static_cast<float*>(m->xcvt), s.H * s.W * cs, cs, 2};
+    ConvRun r = run_conv_f16(ctx, s.plan, xc, y, n, g, w, s.ep.on ? &ep : nullptr);
+    if (s.ep.on) r.tile = EPOOL_TILE_BASE + 1;  // "epool patch": conv_f16's pooled epilogue
+    return r;
+  }
+  if (s.plan.f16 && s.gap) {
+    const Conv1x1GapF16 q{x.p, s.wp, w.bias, y.p, int(n), int(s.C), int(s.H * s.W), int(s.M), s.plan.Mp,
+                          int((s.C + 31) / 32 * 32), int(pixel_stride(x, s.C)), s.relu ? 1 : 0, x.nstride, y.nstride};
+    if (!conv1x1_gap_f16_eligible(q)) return err(m, ORE_ERR_INVALID, "internal: conv + GAP on an unsupported layout");
+    launch_conv1x1_gap_f16(q, ctx->stream);
+    ORE_HIP_CHECK(ctx, hipGetLastError());
+    return {ORE_OK, CONV_GAP_F16_TILE};
+  }
+  if (s.gap) {  // f32: conv1x1_gap_f32_kernel
+    const Conv1x1GapF32 q{x.p, s.wc1, w.bias, y.p, int(n), int(s.C), int(s.H * s.W), int(s.M),
+                          int(plane_stride(x, s.H * s.W)), s.relu ? 1 : 0, x.nstride, y.nstride};
+    if (!conv1x1_gap_f32_eligible(q)) return err(m, ORE_ERR_INVALID, "internal: conv + GAP on an unsupported layout");
+    if (n > 0) launch_conv1x1_gap_f32(q, ctx->stream);
+    ORE_HIP_CHECK(ctx, hipGetLastError());
+    return {ORE_OK, CONV_GAP_F32_TILE};
+  }
+  if (s.plan.f16) return run_conv_f16(ctx, s.plan, x, y, n, g, w, s.ep.on ? &ep : nullptr);
+  if (s.ep.on) {
+    const MappedArena mapped(m);
+    const C1SqueezeF32 sq1{static_cast<const float*>(s.sq.w), s.sq.b, int(s.sq.M), y.p, y.nstride,
+                           int(plane_stride(y, s.ep.win.Ho * s.ep.win.Wo))};
+    if (s.sq.on) w.sq1 = &sq1;
+    return run_conv_epool(ctx, s.plan, x, yc, n, g, w, ep);
+  }
+  if (s.pin.on) {
+    const Step::PoolIn& pin = s.pin;
+    PoolExpand pe{};
+    if (pin.e1.on) {
+      const Ref sv = ref_of(m, s.in3);
+      pe = {sv.p, pin.e1.w, pin.e1.b, int(pin.e1.C), int(pin.e1.E), pin.e1.Mp, plane_stride(sv, pin.H * pin.W), sv.nstride};
+      w.pe = &pe;
+    }
+    const ConvGeom gp{s.C, pin.H, pin.W, s.M, 1, 1, 1, 1, s.win, s.relu};  // the 1x1 conv over x, the pool's input
+    return run_conv_pool(ctx, s.plan, x, y, n, gp, w, PoolGeom{3, 3, pin.sh, pin.sw, pin.win});
+  }
+  const MappedArena mapped(m);
+  return run_conv(ctx, s.plan, x, y, n, g, w);
+}
+
+// records the tile a conv or MatMul step ran
+ore_status ran(Step& s, const ConvRun& r) {
+  s.ran_tile = r.tile;
+  return r.st;
+}
+
+ore_status launch_step(ore_model* m, Step& s, int64_t n) {
   ore_ctx* ctx = m->ctx;
   const Ref y = ref_of(m, s.out);
   switch (s.kind) {
-    case S_CONV: {
-      const Ref x = ref_of(m, s.in0);
-      const float* bias = s.in2 >= 0 ? m->values[s.in2].cptr : nullptr;
-      const F16Epool ep{s.ep.kh, s.ep.kw, s.ep.sh, s.ep.sw, s.ep.win};
-      // the one-launch f16 first conv + pool from the f32 input (plan.epv 1: the two-launch patch path)
-      if (s.plan.f16 && s.plan.xmode == F16_X_NHWC_PAIR && s.ep.on && (s.sq.on || s.plan.epv != 1)) {
-        bool ran = false;
-        const C1Squeeze sq{s.sq.w, s.sq.b, int(s.sq.M), y.p, y.nstride, int(y.ps ? y.ps : s.sq.M)};
-        const ore_status st = run_conv_pair_pool_f16(ctx, s.plan, x.p, n, s.C, s.H, s.W, x.nstride, x.ps, s.wp, s.M, s.kh,
-                                                     s.kw, bias, s.win, s.sh, s.sw, s.relu, s.sq.on ? nullptr : y.p,
-                                                     y.nstride, s.sq.on ? s.M : y.ps, ep, &ran, s.sq.on ? &sq : nullptr);
-        if (ran) s.ran_tile = last_conv_tile;  // C1_POOL_F16_TILE or C1_BAND_F16_TILE
-        if (st != ORE_OK || ran) return st;
-        s.ran_tile = -1;
-        if (s.sq.on) return err(m, ORE_ERR_INVALID, "internal: the fused first conv + squeeze declined its launch");
-      }
-      if (s.plan.f16 && s.plan.xmode == F16_X_NHWC_PAIR) {
-        // convert the f32 NCHW input to NHWC f16 (4 channels per pixel), then gather
-        const int cs = 4;
-        launch_nchw_to_nhwc(x.p, m->xcvt, int(n), int(s.C), int(s.H * s.W), x.nstride, int(x.ps ? x.ps : s.H * s.W), cs,
-                            ctx->stream);
-        ORE_HIP_CHECK(ctx, hipGetLastError());
-        const ore_status r = run_conv_f16(ctx, s.plan, m->xcvt, n, s.C, s.H, s.W, s.H * s.W * cs, cs, s.wp, s.ktab, s.M,
-                                          s.kh, s.kw, bias, s.win, s.sh, s.sw, s.relu, y.p, y.nstride, y.ps,
-                                          s.ep.on ? &ep : nullptr);
-        if (s.ep.on) s.ran_tile = last_conv_tile = EPOOL_TILE_BASE + 1;  // "epool patch": conv_f16's pooled epilogue
-        return r;
-      }
-      if (s.plan.f16 && s.gap) {
-        const Conv1x1GapF16 q{x.p, s.wp, bias, y.p, int(n), int(s.C), int(s.H * s.W), int(s.M), s.plan.Mp,
-                              int((s.C + 31) / 32 * 32), int(x.ps), s.relu ? 1 : 0, x.nstride, y.nstride};
-        if (!conv1x1_gap_f16_eligible(q)) return err(m, ORE_ERR_INVALID, "internal: conv + GAP on an unsupported layout");
-        launch_conv1x1_gap_f16(q, ctx->stream);
-        ORE_HIP_CHECK(ctx, hipGetLastError());
-        s.ran_tile = last_conv_tile = CONV_GAP_F16_TILE;
-        return ORE_OK;
-      }
-      if (s.gap) {  // f32: conv1x1_gap_f32_kernel
-        const Conv1x1GapF32 q{x.p, s.wc1, bias, y.p, int(n), int(s.C), int(s.H * s.W), int(s.M),
-                              int(x.ps ? x.ps : s.H * s.W), s.relu ? 1 : 0, x.nstride, y.nstride};
-        if (!conv1x1_gap_f32_eligible(q)) return err(m, ORE_ERR_INVALID, "internal: conv + GAP on an unsupported layout");
-        if (n > 0) launch_conv1x1_gap_f32(q, ctx->stream);
-        ORE_HIP_CHECK(ctx, hipGetLastError());
-        s.ran_tile = last_conv_tile = CONV_GAP_F32_TILE;
-        return ORE_OK;
-      }
-      if (s.plan.f16)
-        return run_conv_f16(ctx, s.plan, x.p, n, s.C, s.H, s.W, x.nstride, x.ps, s.wp, s.ktab, s.M, s.kh, s.kw, bias,
-                            s.win, s.sh, s.sw, s.relu, y.p, y.nstride, y.ps, s.ep.on ? &ep : nullptr);
-      if (s.ep.on) {
-        const MappedArena mapped(m);
-        const int64_t pplane = s.ep.win.Ho * s.ep.win.Wo;
-        const C1SqueezeF32 sq1{static_cast<const float*>(s.sq.w), s.sq.b, int(s.sq.M), y.p, y.nstride,
-                               int(y.ps ? y.ps : pplane)};
-        const ore_status r = run_conv_epool(ctx, s.plan, x.p, n, s.C, s.H, s.W, x.nstride, x.ps, s.wp, s.ktab, s.M, s.kh,
-                                            s.kw, bias, s.win, s.sh, s.sw, s.relu, s.ep.kh, s.ep.kw, s.ep.sh, s.ep.sw,
-                                            s.ep.win, s.sq.on ? nullptr : y.p, y.nstride, s.sq.on ? pplane : y.ps, s.wc1,
-                                            s.sq.on ? &sq1 : nullptr);
-        s.ran_tile = last_conv_tile;
-        return r;
-      }
-      if (s.pin.on) {
-        PoolExpand pe{};
-        const Step::PoolIn& pin = s.pin;
-        if (pin.e1.on) {
-          const Ref sv = ref_of(m, s.in3);
-          pe = {sv.p, pin.e1.w, pin.e1.b, int(pin.e1.C), int(pin.e1.E), pin.e1.Mp, sv.ps ? sv.ps : pin.H * pin.W, sv.nstride};
-        }
-        return run_conv_pool(ctx, s.plan, x.p, n, s.C, pin.H, pin.W, x.nstride, x.ps, pin.win, pin.sh, pin.sw, s.wp, s.M, bias,
-                             s.relu, y.p, y.nstride, y.ps, x.es, pin.e1.on ? &pe : nullptr);
-      }
-      const MappedArena mapped(m);
-      return run_conv(ctx, s.plan, x.p, n, s.C, s.H, s.W, x.nstride, s.wp, s.ktab, s.M, s.kh, s.kw, bias, s.win, s.sh, s.sw,
-                      s.relu, y.p, y.nstride, x.ps, y.ps, x.es);
-    }
+    case S_CONV: return ran(s, launch_conv_step(m, s, n));
     case S_FIRE: {
       const Ref x = ref_of(m, s.in0);
-      if (s.fire.f16)
-        return run_fire_f16(ctx, x.p, n, s.fire.C, s.fire.pool ? s.fire.H : s.H, s.fire.pool ? s.fire.W : s.W,
-                            x.nstride, x.ps ? x.ps : s.fire.C, s.fire.w1, s.fire.b1, s.fire.E1, s.fire.w3, s.fire.b3,
-                            s.fire.E3, s.fire.ws16, s.in2 >= 0 ? m->values[s.in2].cptr : nullptr, s.M, y.p,
-                            y.nstride, y.ps ? y.ps : (s.M ? s.M : s.fire.E1 + s.fire.E3),
-                            s.fire.pool ? &s.fire.pwin : nullptr);
+      const Step::Fire& f = s.fire;
+      const FireOperands fo{f.C, f.E1, f.E3, s.M, s.plan.Mp, f.w1, f.w3, f.f16 ? f.ws16 : s.wp,
+                            f.b1, f.b3, s.in2 >= 0 ? m->values[s.in2].cptr : nullptr};
+      const Window* pool = f.pool ? &f.pwin : nullptr;
+      if (f.f16) return run_fire_f16(ctx, x, y, n, f.H, f.W, fo, pool);
       const MappedArena mapped(m);
-      const int64_t fH = s.fire.pool ? s.fire.H : s.H, fW = s.fire.pool ? s.fire.W : s.W;
-      return run_fire(ctx, x.p, n, s.fire.C, fH, fW, x.nstride, x.ps ? x.ps : fH * fW, s.fire.w1, s.fire.b1, s.fire.E1,
-                      s.fire.w3, s.fire.b3, s.fire.E3, s.wp, s.plan.Mp, m->values[s.in2].cptr, s.M, y.p, y.nstride,
-                      y.ps ? y.ps : s.H * s.W, s.fire.pool ? &s.fire.pwin : nullptr);
+      return run_fire(ctx, x, y, n, f.H, f.W, fo, pool);
     }
-    case S_MATMUL: {
+    case S_MATMUL: {  // a 1x1 conv over rows: 2-D operands, whatever planes the storage they alias has
       const Ref x = ref_of(m, s.in0);
-      return run_conv(ctx, s.plan, x.p, n, s.C, 1, 1, x.nstride, s.wp, s.ktab, s.M, 1, 1, nullptr, s.win, 1, 1, false, y.p,
-                      y.nstride);
+      return ran(s, run_conv(ctx, s.plan, Ref{x.p, x.nstride, 0, x.es}, Ref{y.p, y.nstride, 0, y.es}, n, conv_geom(s),
+                             ConvOperands{s.wp, s.ktab, nullptr}));
     }
     case S_MAXPOOL: {
       const Ref x = ref_of(m, s.in0);
-      if (x.es == 2)
-        return run_maxpool_nhwc(ctx, x.p, n, s.C, s.H, s.W, x.nstride, x.ps, s.kh, s.kw, s.win, s.sh, s.sw, y.p,
-                                y.nstride, y.ps);
-      return run_maxpool(ctx, x.p, n, s.C, s.H, s.W, x.nstride, s.kh, s.kw, s.win, s.sh, s.sw, y.p, y.nstride, x.ps,
-                         y.ps, x.es);
+      return run_maxpool(ctx, x, y, n, s.C, s.H, s.W, PoolGeom{s.kh, s.kw, s.sh, s.sw, s.win});
     }
     default: break;
   }
@@ -1136,10 +1129,9 @@ ore_status ore_model_autotune(ore_model* m, const float* d_input, int64_t n, flo
     for (size_t ci = 0; ci < cands.size() && !st; ++ci) {
       const int c = cands[ci];
       set_tile(m, int(k), c);
-      last_conv_tile = -1;
       st = launch_step(m, s, n);  // warm-up
       if (st) break;
-      if (last_conv_tile != c) continue;  // fell back to another kernel: not a distinct candidate here
+      if (s.ran_tile != c) continue;  // fell back to another kernel: not a distinct candidate here
       if (hipEventRecord(e0, ctx->stream) != hipSuccess) { st = set_error(ctx, ORE_ERR_HIP, "event record"); break; }
       for (int r = 0; r < reps && !st; ++r) st = launch_step(m, s, n);
       if (st) break;

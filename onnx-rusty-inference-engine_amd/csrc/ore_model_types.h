@@ -80,7 +80,7 @@ struct Step {
     int64_t kh = 0, kw = 0, sh = 1, sw = 1;
     Window win;
   } ep;
-  mutable int ran_tile = -1;  // pooled conv: the kernel variant its last launch took (EPOOL_TILE_BASE + v)
+  int ran_tile = -1;  // S_CONV / S_MATMUL: the tile id its last launch ran (launch_step; -1: none, or a kernel without one)
   // S_FIRE (ORE_FUSE_FIRE): this squeeze conv also computes the fire module feeding it; in0 is the fire's
   // input S of C channels, the squeeze's K = E1 + E3.  M = 0: no squeeze, the Concat is the output.
   struct Fire {
@@ -214,9 +214,7 @@ inline int64_t slot_extent(const ore_model* m, const Value& v) {
   return ((v.image_stride() * m->run_batch * v.es) + 255) / 256 * 256;
 }
 
-// storage of a value for the current run: pointer to image 0 and per-image stride
-struct Ref { float* p; int64_t nstride; int64_t ps; int es; };  // p: storage of es-byte elements
-
+// storage of a value for the current run
 inline Ref ref_of(ore_model* m, int id) {
   const Value& v = m->values[id];
   if (v.is_const) return {v.cptr, 0, 0, 4};

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <cstdlib>
 
+#include "ore_chunk.h"
 #include "ore_internal.h"
 
 namespace {
@@ -83,6 +84,9 @@ static int64_t nstride_of(const ore_tensor* t) {
   return s;
 }
 
+// a per-op f32 tensor as the runners take it (dense planes)
+static Ref ref_of(const ore_tensor* t) { return {t->data, nstride_of(t), 0, 4}; }
+
 static int64_t numel(const ore_tensor* t) {
   int64_t s = 1;
   for (int i = 0; i < t->ndim; ++i) s *= t->dims[i];
@@ -98,19 +102,15 @@ static bool contiguous(const ore_tensor* t) {
 
 static bool fits_i32(int64_t v) { return v >= 0 && v < (int64_t(1) << 31); }
 
-// The kernels address activations through buffer resources (32-bit byte offsets, plus up to a few KB
-// read before x by the 3x3 tap loads): a batch whose input or output extent does not fit is launched
-// in image chunks that do.  Returns the images per chunk (0: one image alone is too large).
-constexpr int64_t CHUNK_LIMIT = (int64_t(1) << 31) - (int64_t(1) << 21);
-static int64_t image_chunk(int64_t N, int64_t x_nstride, int64_t x_img_bytes, int x_es, int64_t y_nstride,
-                           int64_t y_img_bytes, int y_es) {
-  auto fits = [&](int64_t nb) {
-    return (nb - 1) * x_nstride * x_es + x_img_bytes < CHUNK_LIMIT && (nb - 1) * y_nstride * y_es + y_img_bytes < CHUNK_LIMIT;
-  };
-  if (!fits(1)) return 0;
-  int64_t nb = N;
-  while (nb > 1 && !fits(nb)) nb = (nb + 1) / 2;
-  return nb;
+// mapped bytes before x: the rest of x's 4 KiB page, or the walker's arena lead where x lies inside the
+// context's mapped range.  The streaming 3x3 conv, the row-walking pooled conv and the f32 fire kernels
+// read a few of them, masked, instead of issuing negative buffer offsets.
+static int x_guard_bytes(const ore_ctx* ctx, const void* x) {
+  const char* xc = static_cast<const char*>(x);
+  int64_t g = int64_t(reinterpret_cast<uintptr_t>(x) & 4095);
+  if (ctx->mapped_lo && xc >= ctx->mapped_lo && xc < ctx->mapped_hi)
+    g = std::max<int64_t>(g, std::min<int64_t>(xc - ctx->mapped_lo, 1 << 20));
+  return int(g);
 }
 
 ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const float* scale, const float* shift,
@@ -169,57 +169,74 @@ float* pack_to_scratch(ore_ctx* ctx, const ConvPlan& pln, const float* w, bool k
   return ctx->scratch;
 }
 
-ore_status run_conv(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                    int64_t x_nstride, const float* wp, const int2* ktab, int64_t M, int64_t kh, int64_t kw,
-                    const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu, float* y,
-                    int64_t y_nstride, int64_t x_ps, int64_t y_ps, int x_es) {
-  if (N == 0) return ORE_OK;
-  if (pln.f16 || x_es != 4) return set_error(ctx, ORE_ERR_INVALID, "internal: run_conv takes f32 plans and inputs");
-  if (x_ps == 0) x_ps = H * W;
-  if (y_ps == 0) y_ps = win.Ho * win.Wo;
+// kh = kw = 1, stride 1, no padding, the output plane the input's
+static bool pointwise(const ConvGeom& g) {
+  return g.kh == 1 && g.kw == 1 && g.sh == 1 && g.sw == 1 && g.win.pt == 0 && g.win.pl == 0 && g.win.Ho == g.H &&
+         g.win.Wo == g.W;
+}
+
+// The ConvParams fields the four conv paths fill alike; x_ps / y_ps: the strides as the path's layouts
+// resolve them; ep: the pool of a pooled form.  false: not a pool the pooled epilogues take (epool_tile).
+// Each path then sets what is its own: P, Ntot, is1x1, vec_out, x_guard, and per chunk x_bytes.
+static bool conv_params(ConvParams* out, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                        const ConvOperands& w, int64_t x_ps, int64_t y_ps, const PoolGeom* ep) {
   ConvParams p{};
-  p.x = x; p.wp = wp; p.ktab = ktab; p.bias = bias; p.y = y;
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.M = int(M); p.kh = int(kh); p.kw = int(kw); p.sh = int(sh); p.sw = int(sw);
-  p.pt = int(win.pt); p.pl = int(win.pl);
-  p.Ho = int(win.Ho); p.Wo = int(win.Wo);
-  p.K = int(C * kh * kw);
-  p.P = int(win.Ho * win.Wo);
+  p.x = x.p; p.wp = w.wp; p.ktab = w.ktab; p.bias = w.bias; p.y = y.p;
+  p.N = int(N); p.C = int(g.C); p.H = int(g.H); p.W = int(g.W);
+  p.M = int(g.M); p.kh = int(g.kh); p.kw = int(g.kw); p.sh = int(g.sh); p.sw = int(g.sw);
+  p.pt = int(g.win.pt); p.pl = int(g.win.pl);
+  p.Ho = int(g.win.Ho); p.Wo = int(g.win.Wo);
+  // the GEMM's K: the f16 packings pad taps and channels per xmode
+  p.K = pln.f16 ? f16_conv_k(pln.xmode, int(g.C), int(g.kh), int(g.kw)) : int(g.C * g.kh * g.kw);
   p.x_ps = int(x_ps);
   p.y_ps = int(y_ps);
-  p.Ntot = N * y_ps;
-  p.x_nstride = x_nstride;
-  p.y_nstride = y_nstride;
-  p.relu = relu ? 1 : 0;
+  p.x_nstride = x.nstride;
+  p.y_nstride = y.nstride;
+  p.relu = g.relu ? 1 : 0;
   p.Mp = pln.Mp;
-  p.x_f32 = 1;
-  // 16-B epilogue stores of 4 floats
-  p.vec_out = (y_ps % 4 == 0 && y_nstride % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
-  p.is1x1 = (kh == 1 && kw == 1 && sh == 1 && sw == 1 && win.pt == 0 && win.pl == 0 && win.Ho == H && win.Wo == W &&
-             x_ps == y_ps);
-  {  // mapped bytes before x: the rest of x's 4 KiB page, or the walker's arena lead
-    const char* xc = reinterpret_cast<const char*>(x);
-    int64_t g = int64_t(reinterpret_cast<uintptr_t>(x) & 4095);
-    if (ctx->mapped_lo && xc >= ctx->mapped_lo && xc < ctx->mapped_hi) g = std::max<int64_t>(g, std::min<int64_t>(xc - ctx->mapped_lo, 1 << 20));
-    p.x_guard = int(g);
+  p.x_f32 = (!pln.f16 || pln.xmode == F16_X_NCHW32) ? 1 : 0;  // x is f32 NCHW; else NHWC f16
+  if (ep) {
+    if (epool_tile(g.win.Ho, g.win.Wo, ep->kh, ep->kw, ep->sh, ep->sw, ep->win, &p.ep_tr, &p.ep_tc) == 0.0) return false;
+    p.ep_pt = int(ep->win.pt); p.ep_pl = int(ep->win.pl); p.ep_Ho = int(ep->win.Ho); p.ep_Wo = int(ep->win.Wo);
   }
-  if (x_ps < H * W || y_ps < win.Ho * win.Wo) return set_error(ctx, ORE_ERR_INVALID, "plane stride below plane size");
-  if (!fits_i32(x_nstride * N + 256) || !fits_i32(y_nstride * N + 256) || !fits_i32(int64_t(pln.krows) * pln.Mp) ||
-      !fits_i32(p.Ntot + 256) || (p.Ntot + 127) / 128 * ((M + 31) / 32) >= (int64_t(1) << 31))
+  *out = p;
+  return true;
+}
+
+// columns of a pooled form: whole patches of conv outputs, ep_tr x ep_tc per image
+static int64_t epool_columns(const ConvParams& p, int64_t n) { return n * int64_t(p.ep_tr) * p.ep_tc * CONV_EPOOL_BN; }
+
+ConvRun run_conv(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                 const ConvOperands& w) {
+  if (N == 0) return ORE_OK;
+  if (pln.f16 || x.es != 4) return set_error(ctx, ORE_ERR_INVALID, "internal: run_conv takes f32 plans and inputs");
+  const int64_t x_ps = plane_stride(x, g.H * g.W), y_ps = plane_stride(y, g.win.Ho * g.win.Wo);
+  ConvParams p;
+  conv_params(&p, pln, x, y, N, g, w, x_ps, y_ps, nullptr);
+  p.P = int(g.win.Ho * g.win.Wo);
+  p.Ntot = N * y_ps;  // a column per element of y's (padded) planes
+  // 16-B epilogue stores of 4 floats
+  p.vec_out = (y_ps % 4 == 0 && y.nstride % 4 == 0 && (reinterpret_cast<uintptr_t>(y.p) & 15) == 0) ? 1 : 0;
+  p.is1x1 = pointwise(g) && x_ps == y_ps;  // the 1x1 kernels take column j of y from column j of x: equal plane strides
+  p.x_guard = x_guard_bytes(ctx, x.p);
+  if (x_ps < g.H * g.W || y_ps < g.win.Ho * g.win.Wo) return set_error(ctx, ORE_ERR_INVALID, "plane stride below plane size");
+  if (!fits_i32(x.nstride * N + 256) || !fits_i32(y.nstride * N + 256) || !fits_i32(int64_t(pln.krows) * pln.Mp) ||
+      !fits_i32(p.Ntot + 256) || (p.Ntot + 127) / 128 * ((g.M + 31) / 32) >= (int64_t(1) << 31))
     return set_error(ctx, ORE_ERR_INVALID, "conv geometry exceeds 32-bit indexing");
-  if (!pln.wino && !p.is1x1 && !ktab) return set_error(ctx, ORE_ERR_INVALID, "internal: gather table missing");
-  // image chunks whose x and y extents fit 32-bit byte offsets (the output may be a slice of a wider
-  // concat buffer, e.g. an expand3x3 writing channels 256..511 of 512)
-  const int64_t nb = image_chunk(N, x_nstride, C * x_ps * 4, 4, y_nstride, M * y_ps * 4, 4);
+  if (!pln.wino && !p.is1x1 && !w.ktab) return set_error(ctx, ORE_ERR_INVALID, "internal: gather table missing");
+  // the output may be a slice of a wider concat buffer (y.nstride above M * y_ps), e.g. an expand3x3
+  // writing channels 256..511 of 512
+  const ChunkSide xs{x.nstride, g.C * x_ps * 4, 4}, ys{y.nstride, g.M * y_ps * 4, 4};
+  const int64_t nb = image_chunk(N, xs, ys);
   if (nb == 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "conv: one image exceeds 2 GiB");
-  for (int64_t i0 = 0; i0 < N; i0 += nb) {
-    const int64_t nc = std::min(nb, N - i0);
+  int tile = -1;
+  for (Chunk c = chunk_at(0, N, nb); c.nc > 0; c = chunk_at(c.i0 + c.nc, N, nb)) {
     ConvParams q = p;
-    q.x = x + i0 * x_nstride;
-    q.y = y + i0 * y_nstride;
-    q.N = int(nc);
-    q.Ntot = nc * y_ps;
-    q.x_bytes = ((nc - 1) * x_nstride + C * x_ps) * 4;
+    q.x = x.p + c.i0 * x.nstride;
+    q.y = y.p + c.i0 * y.nstride;
+    q.N = int(c.nc);
+    q.Ntot = c.nc * y_ps;
+    q.x_bytes = xs.bytes(c.nc);
     ConvPlan qp = pln;
     if (pln.wino && !conv_wino_eligible(q, qp.cfg - WINO_TILE_BASE)) {  // the first tile that takes it
       int t = 0;
@@ -227,52 +244,47 @@ ore_status run_conv(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N
       if (t == WINO_TILES_N) return set_error(ctx, ORE_ERR_UNSUPPORTED, "Winograd conv: no tile takes this layout");
       qp.cfg = WINO_TILE_BASE + t;
     }
-    launch_conv(q, qp, ctx->stream);
+    tile = launch_conv(q, qp, ctx->stream);
     ORE_HIP_CHECK(ctx, hipGetLastError());
   }
-  return ORE_OK;
+  return {ORE_OK, tile};
 }
 
-ore_status run_fire(ore_ctx* ctx, const float* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t x_nstride,
-                    int64_t x_ps, const float* w1, const float* b1, int64_t E1, const float* w3, const float* b3,
-                    int64_t E3, const float* ws, int64_t Msp, const float* bs, int64_t Ms, float* y, int64_t y_nstride,
-                    int64_t y_ps, const Window* pool) {
+ore_status run_fire(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int64_t H, int64_t W, const FireOperands& f,
+                    const Window* pool) {
   if (N == 0) return ORE_OK;
+  const int64_t yplane = pool ? pool->Ho * pool->Wo : H * W;
+  const int64_t x_ps = plane_stride(x, H * W), y_ps = plane_stride(y, yplane);
   FireParams p{};
-  p.x = x; p.w1 = w1; p.b1 = b1; p.w3 = w3; p.b3 = b3; p.ws = ws; p.bs = bs; p.y = y;
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.E1 = int(E1); p.E3 = int(E3); p.Ms = int(Ms); p.Msp = int(Msp);
+  p.x = x.p; p.y = y.p;
+  p.w1 = static_cast<const float*>(f.w1); p.b1 = f.b1; p.w3 = static_cast<const float*>(f.w3); p.b3 = f.b3;
+  p.ws = static_cast<const float*>(f.ws); p.bs = f.bs;
+  p.N = int(N); p.C = int(f.C); p.H = int(H); p.W = int(W);
+  p.E1 = int(f.E1); p.E3 = int(f.E3); p.Ms = int(f.Ms); p.Msp = int(f.Msp);
   p.x_ps = int(x_ps); p.y_ps = int(y_ps);
-  p.x_nstride = x_nstride; p.y_nstride = y_nstride;
+  p.x_nstride = x.nstride; p.y_nstride = y.nstride;
   p.Ntot = N * y_ps;
   if (pool) {
     p.pool = 1;
     p.Hp = int(pool->Ho); p.Wp = int(pool->Wo); p.ppt = int(pool->pt); p.ppl = int(pool->pl);
     if (!fire_pool_plan(&p)) return set_error(ctx, ORE_ERR_INVALID, "internal: no band shape for the pooled fire module");
   }
-  {  // mapped bytes before x (as run_conv): the rest of x's page or the walker's arena lead
-    const char* xc = reinterpret_cast<const char*>(x);
-    int64_t g = int64_t(reinterpret_cast<uintptr_t>(x) & 4095);
-    if (ctx->mapped_lo && xc >= ctx->mapped_lo && xc < ctx->mapped_hi)
-      g = std::max<int64_t>(g, std::min<int64_t>(xc - ctx->mapped_lo, 1 << 20));
-    p.x_guard = int(g);
-  }
+  p.x_guard = x_guard_bytes(ctx, x.p);
   p.x_lead = int(((W + 1) * 4 + 15) & ~int64_t(15));
-  if (x_ps < H * W || y_ps < (pool ? pool->Ho * pool->Wo : H * W) || !fits_i32(x_nstride * N + 256) || !fits_i32(y_nstride * N + 256) ||
+  if (x_ps < H * W || y_ps < yplane || !fits_i32(x.nstride * N + 256) || !fits_i32(y.nstride * N + 256) ||
       !fits_i32(p.Ntot + 256))
     return set_error(ctx, ORE_ERR_INVALID, "fire geometry exceeds 32-bit indexing");
-  // the kernels address x through a buffer resource (32-bit byte offsets, plus the x_lead bytes before
-  // it): a batch whose input extent does not fit runs in image chunks that do
-  const int64_t nb = image_chunk(N, x_nstride, C * x_ps * 4, 4, y_nstride, Ms * y_ps * 4, 4);
+  // x is addressed through a buffer resource, x_lead bytes before it included
+  const ChunkSide xs{x.nstride, f.C * x_ps * 4, 4}, ys{y.nstride, f.Ms * y_ps * 4, 4};
+  const int64_t nb = image_chunk(N, xs, ys);
   if (nb == 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "fused fire module: one image exceeds 2 GiB");
-  for (int64_t i0 = 0; i0 < N; i0 += nb) {
-    const int64_t nc = std::min(nb, N - i0);
+  for (Chunk c = chunk_at(0, N, nb); c.nc > 0; c = chunk_at(c.i0 + c.nc, N, nb)) {
     FireParams q = p;
-    q.x = x + i0 * x_nstride;
-    q.y = y + i0 * y_nstride;
-    q.N = int(nc);
-    q.Ntot = nc * y_ps;
-    q.x_bytes = ((nc - 1) * x_nstride + C * x_ps) * 4;
+    q.x = x.p + c.i0 * x.nstride;
+    q.y = y.p + c.i0 * y.nstride;
+    q.N = int(c.nc);
+    q.Ntot = c.nc * y_ps;
+    q.x_bytes = xs.bytes(c.nc);
     if (!fire_eligible(q)) return set_error(ctx, ORE_ERR_INVALID, "internal: fused fire module on an unsupported layout");
     launch_fire(q, ctx->stream);
     ORE_HIP_CHECK(ctx, hipGetLastError());
@@ -280,19 +292,18 @@ ore_status run_fire(ore_ctx* ctx, const float* x, int64_t N, int64_t C, int64_t 
   return ORE_OK;
 }
 
-ore_status run_fire_f16(ore_ctx* ctx, const void* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t x_nstride,
-                        int64_t x_cs, const void* w1, const float* b1, int64_t E1, const void* w3, const float* b3,
-                        int64_t E3, const void* ws, const float* bs, int64_t Ms, void* y, int64_t y_nstride,
-                        int64_t y_cs, const Window* pool) {
+ore_status run_fire_f16(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int64_t H, int64_t W,
+                        const FireOperands& f, const Window* pool) {
   if (N == 0) return ORE_OK;
+  const int64_t x_cs = pixel_stride(x, f.C), y_cs = pixel_stride(y, f.Ms ? f.Ms : f.E1 + f.E3);
   if (!fits_i32(N) || !fits_i32(H * W) || !fits_i32(x_cs) || !fits_i32(y_cs))
     return set_error(ctx, ORE_ERR_INVALID, "fire geometry exceeds 32-bit indexing");
   FireF16Params p{};
-  p.x = x; p.w1 = w1; p.b1 = b1; p.w3 = w3; p.b3 = b3; p.ws = ws; p.bs = bs; p.y = y;
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.E1 = int(E1); p.E3 = int(E3); p.Ms = int(Ms); p.Msp = int((Ms + 31) / 32 * 32);
+  p.x = x.p; p.w1 = f.w1; p.b1 = f.b1; p.w3 = f.w3; p.b3 = f.b3; p.ws = f.ws; p.bs = f.bs; p.y = y.p;
+  p.N = int(N); p.C = int(f.C); p.H = int(H); p.W = int(W);
+  p.E1 = int(f.E1); p.E3 = int(f.E3); p.Ms = int(f.Ms); p.Msp = int((f.Ms + 31) / 32 * 32);
   p.x_cs = int(x_cs); p.y_cs = int(y_cs);
-  p.x_nstride = x_nstride; p.y_nstride = y_nstride;
+  p.x_nstride = x.nstride; p.y_nstride = y.nstride;
   if (pool) {
     p.pool = 1;
     p.Hp = int(pool->Ho); p.Wp = int(pool->Wo); p.ppt = int(pool->pt); p.ppl = int(pool->pl);
@@ -313,103 +324,77 @@ double epool_tile(int64_t Ho, int64_t Wo, int64_t pkh, int64_t pkw, int64_t psh,
   return double(int64_t(*tr) * *tc * CONV_EPOOL_BN) / double(Ho * Wo);
 }
 
-ore_status run_conv_epool(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                          int64_t x_nstride, int64_t x_ps, const float* wp, const int2* ktab, int64_t M, int64_t kh,
-                          int64_t kw, const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu,
-                          int64_t pkh, int64_t pkw, int64_t psh, int64_t psw, const Window& pwin, float* y,
-                          int64_t y_nstride, int64_t y_ps, const float* wc1, const C1SqueezeF32* sq1) {
+ConvRun run_conv_epool(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                       const ConvOperands& w, const PoolGeom& ep) {
   if (N == 0) return ORE_OK;
   if (pln.f16) return set_error(ctx, ORE_ERR_INVALID, "internal: the pooled epilogue is f32 gather only");
-  if (x_ps == 0) x_ps = H * W;
-  if (y_ps == 0) y_ps = pwin.Ho * pwin.Wo;
-  int tr = 0, tc = 0;
-  if (epool_tile(win.Ho, win.Wo, pkh, pkw, psh, psw, pwin, &tr, &tc) == 0.0)
+  const int64_t x_ps = plane_stride(x, g.H * g.W), y_ps = plane_stride(y, ep.win.Ho * ep.win.Wo);
+  ConvParams p;
+  if (!conv_params(&p, pln, x, y, N, g, w, x_ps, y_ps, &ep))
     return set_error(ctx, ORE_ERR_INVALID, "internal: the pooled epilogue takes 3x3 / stride-2 pools");
-  ConvParams p{};
-  p.x = x; p.wp = wp; p.ktab = ktab; p.bias = bias; p.y = y;
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.M = int(M); p.kh = int(kh); p.kw = int(kw); p.sh = int(sh); p.sw = int(sw);
-  p.pt = int(win.pt); p.pl = int(win.pl);
-  p.Ho = int(win.Ho); p.Wo = int(win.Wo);
-  p.K = int(C * kh * kw);
-  p.P = int(win.Ho * win.Wo);
-  p.x_ps = int(x_ps);
-  p.y_ps = int(y_ps);
-  p.x_nstride = x_nstride;
-  p.y_nstride = y_nstride;
-  p.relu = relu ? 1 : 0;
-  p.Mp = pln.Mp;
-  p.x_f32 = 1;
-  p.is1x1 = (kh == 1 && kw == 1 && sh == 1 && sw == 1 && win.pt == 0 && win.pl == 0 && win.Ho == H && win.Wo == W &&
-             x_ps == H * W);
-  p.ep_pt = int(pwin.pt); p.ep_pl = int(pwin.pl); p.ep_Ho = int(pwin.Ho); p.ep_Wo = int(pwin.Wo);
-  p.ep_tr = tr; p.ep_tc = tc;
+  p.P = int(g.win.Ho * g.win.Wo);
+  p.Ntot = epool_columns(p, N);
+  // vec_out stays 0: the pooled epilogues store single pooled values
+  p.is1x1 = pointwise(g) && x_ps == g.H * g.W;  // y is the pooled plane, never x's: dense input planes instead
+  p.x_guard = x_guard_bytes(ctx, x.p);
   p.ep_variant = pln.epv;
-  p.wc1 = wc1;
-  p.sq1 = sq1;
-  {  // mapped bytes before x (as run_conv): the row-walking 3x3 kernel reads a few of them, masked
-    const char* xc = reinterpret_cast<const char*>(x);
-    int64_t g = int64_t(reinterpret_cast<uintptr_t>(x) & 4095);
-    if (ctx->mapped_lo && xc >= ctx->mapped_lo && xc < ctx->mapped_hi)
-      g = std::max<int64_t>(g, std::min<int64_t>(xc - ctx->mapped_lo, 1 << 20));
-    p.x_guard = int(g);
-  }
-  p.Ntot = N * int64_t(p.ep_tr) * p.ep_tc * CONV_EPOOL_BN;
-  if (x_ps < H * W || y_ps < pwin.Ho * pwin.Wo) return set_error(ctx, ORE_ERR_INVALID, "plane stride below plane size");
-  if (!fits_i32(x_nstride * N + 256) || !fits_i32(y_nstride * N + 256) || !fits_i32(int64_t(pln.krows) * pln.Mp) ||
-      !fits_i32(p.Ntot + 256) || N * p.ep_tr * p.ep_tc * ((M + 31) / 32) >= (int64_t(1) << 31))
+  p.wc1 = w.wc1;
+  p.sq1 = w.sq1;
+  if (x_ps < g.H * g.W || y_ps < ep.win.Ho * ep.win.Wo) return set_error(ctx, ORE_ERR_INVALID, "plane stride below plane size");
+  if (!fits_i32(x.nstride * N + 256) || !fits_i32(y.nstride * N + 256) || !fits_i32(int64_t(pln.krows) * pln.Mp) ||
+      !fits_i32(p.Ntot + 256) || N * p.ep_tr * p.ep_tc * ((g.M + 31) / 32) >= (int64_t(1) << 31))
     return set_error(ctx, ORE_ERR_INVALID, "conv geometry exceeds 32-bit indexing");
-  if (!p.is1x1 && !ktab) return set_error(ctx, ORE_ERR_INVALID, "internal: gather table missing");
-  const int64_t y_img = sq1 ? (sq1->M * int64_t(sq1->y_ps)) * 4 : M * y_ps * 4;
-  const int64_t nb = image_chunk(N, x_nstride, C * x_ps * 4, 4, sq1 ? sq1->y_nstride : y_nstride, y_img, 4);
+  if (!p.is1x1 && !w.ktab) return set_error(ctx, ORE_ERR_INVALID, "internal: gather table missing");
+  // with the next 1x1 conv fused in, what the launch writes is that conv's output
+  const C1SqueezeF32* sq1 = w.sq1;
+  const ChunkSide xs{x.nstride, g.C * x_ps * 4, 4};
+  const ChunkSide ys = sq1 ? ChunkSide{sq1->y_nstride, sq1->M * int64_t(sq1->y_ps) * 4, 4} : ChunkSide{y.nstride, g.M * y_ps * 4, 4};
+  const int64_t nb = image_chunk(N, xs, ys);
   if (nb == 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "pooled conv: one image exceeds 2 GiB");
-  for (int64_t i0 = 0; i0 < N; i0 += nb) {
-    const int64_t nc = std::min(nb, N - i0);
+  int tile = -1;
+  for (Chunk c = chunk_at(0, N, nb); c.nc > 0; c = chunk_at(c.i0 + c.nc, N, nb)) {
     ConvParams q = p;
     C1SqueezeF32 sq{};
-    q.x = x + i0 * x_nstride;
-    if (y) q.y = y + i0 * y_nstride;
+    q.x = x.p + c.i0 * x.nstride;
+    if (y.p) q.y = y.p + c.i0 * y.nstride;
     if (sq1) {
       sq = *sq1;
-      sq.y = sq1->y + i0 * sq1->y_nstride;
+      sq.y = sq1->y + c.i0 * sq1->y_nstride;
       q.sq1 = &sq;
     }
-    q.N = int(nc);
-    q.Ntot = nc * int64_t(p.ep_tr) * p.ep_tc * CONV_EPOOL_BN;
-    q.x_bytes = ((nc - 1) * x_nstride + C * x_ps) * 4;
-    launch_conv_epool(q, ctx->stream);
+    q.N = int(c.nc);
+    q.Ntot = epool_columns(p, c.nc);
+    q.x_bytes = xs.bytes(c.nc);
+    tile = launch_conv_epool(q, ctx->stream);
     ORE_HIP_CHECK(ctx, hipGetLastError());
-    if (sq1 && last_conv_tile != EPOOL_WIN_TILE && last_conv_tile != EPOOL_BAND_TILE)
+    if (sq1 && tile < 0)
       return set_error(ctx, ORE_ERR_INVALID, "internal: the fused first conv + squeeze declined its launch");
   }
-  return ORE_OK;
+  return {ORE_OK, tile};
 }
 
-ore_status run_conv_pool(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t pH,
-                         int64_t pW, int64_t x_nstride, int64_t x_ps, const Window& pwin, int64_t psh, int64_t psw,
-                         const float* wp, int64_t M, const float* bias, bool relu, float* y, int64_t y_nstride,
-                         int64_t y_ps, int x_es, const PoolExpand* pe) {
+ore_status run_conv_pool(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                         const ConvOperands& w, const PoolGeom& pool) {
   if (N == 0) return ORE_OK;
-  if (x_ps == 0) x_ps = pH * pW;
-  const int64_t P = pwin.Ho * pwin.Wo;
-  if (y_ps == 0) y_ps = P;
-  if (pln.f16 || pln.wino || x_es != 4)
+  const Window& pwin = pool.win;
+  const int64_t x_ps = plane_stride(x, g.H * g.W), y_ps = plane_stride(y, pwin.Ho * pwin.Wo);
+  if (pln.f16 || pln.wino || x.es != 4)
     return set_error(ctx, ORE_ERR_INVALID, "internal: the pooled 1x1 conv is f32 direct only");
   // 3x3 / stride-2 pools (the window is implied by the walker's pass, kernel_shape 3x3):
   // pool_conv1x1_f32_kernel (LDS-staged rows, MFMA squeeze)
   PoolConvParams q{};
-  q.x = x; q.wp = wp; q.bias = bias; q.y = y;
-  q.N = int(N); q.C = int(C); q.H = int(pH); q.W = int(pW); q.Hp = int(pwin.Ho); q.Wp = int(pwin.Wo);
-  q.pt = int(pwin.pt); q.pl = int(pwin.pl); q.M = int(M); q.Mp = pln.Mp; q.Kp = pln.krows;
-  q.x_ps = int(x_ps); q.y_ps = int(y_ps); q.x_nstride = x_nstride; q.y_nstride = y_nstride;
-  q.relu = relu ? 1 : 0;
-  if (pe) {
+  q.x = x.p; q.wp = w.wp; q.bias = w.bias; q.y = y.p;
+  q.N = int(N); q.C = int(g.C); q.H = int(g.H); q.W = int(g.W); q.Hp = int(pwin.Ho); q.Wp = int(pwin.Wo);
+  q.pt = int(pwin.pt); q.pl = int(pwin.pl); q.M = int(g.M); q.Mp = pln.Mp; q.Kp = pln.krows;
+  q.x_ps = int(x_ps); q.y_ps = int(y_ps); q.x_nstride = x.nstride; q.y_nstride = y.nstride;
+  q.relu = g.relu ? 1 : 0;
+  if (const PoolExpand* pe = w.pe) {
     q.s = pe->s; q.w1 = pe->w1; q.b1 = pe->b1; q.C1 = pe->C1; q.E1 = pe->E1; q.w1_Mp = pe->w1_Mp;
     q.s_ps = int(pe->s_ps); q.s_nstride = pe->s_nstride;
     if (!fits_i32(pe->s_nstride * N + 256) || !fits_i32(pe->s_ps))
       return set_error(ctx, ORE_ERR_INVALID, "internal: recomputed expand input past 2 GiB");
   }
-  if (psh != 2 || psw != 2 || pwin.Ho <= 0 || !fits_i32(x_nstride * N + 256) || !fits_i32(y_nstride * N + 256) ||
+  if (pool.sh != 2 || pool.sw != 2 || pwin.Ho <= 0 || !fits_i32(x.nstride * N + 256) || !fits_i32(y.nstride * N + 256) ||
       !pool_conv1x1_f32_eligible(q))
     return set_error(ctx, ORE_ERR_INVALID, "internal: pooled 1x1 conv outside pool_conv1x1_f32_kernel's limits");
   launch_pool_conv1x1_f32(q, ctx->stream);
@@ -417,147 +402,110 @@ ore_status run_conv_pool(ore_ctx* ctx, const ConvPlan& pln, const float* x, int6
   return ORE_OK;
 }
 
-ore_status run_conv_pair_pool_f16(ore_ctx* ctx, const ConvPlan& pln, const float* x, int64_t N, int64_t C, int64_t H,
-                                  int64_t W, int64_t x_nstride, int64_t x_ps, const void* wp, int64_t M, int64_t kh,
-                                  int64_t kw, const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu,
-                                  void* y, int64_t y_nstride, int64_t y_ps, const F16Epool& ep, bool* ran,
-                                  const C1Squeeze* sq) {
-  *ran = false;
+ConvRun run_conv_pair_pool_f16(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N,
+                               const ConvGeom& g, const ConvOperands& w, const PoolGeom& ep) {
+  // every `return ORE_OK` before the launch is a quiet decline (tile -1): the caller takes the two-launch path
   if (N == 0 || !pln.f16 || pln.xmode != F16_X_NHWC_PAIR) return ORE_OK;
-  if (x_ps == 0) x_ps = H * W;
-  if (y_ps == 0) y_ps = M;
-  int tr = 0, tc = 0;
-  if (epool_tile(win.Ho, win.Wo, ep.kh, ep.kw, ep.sh, ep.sw, ep.win, &tr, &tc) == 0.0) return ORE_OK;
-  if (!fits_i32(N * int64_t(tr) * tc) || !fits_i32(C * x_ps) || !fits_i32(y_ps * ep.win.Ho * ep.win.Wo) || x_ps < H * W)
+  const int64_t x_ps = plane_stride(x, g.H * g.W), y_ps = pixel_stride(y, g.M);
+  ConvParams p;
+  if (!conv_params(&p, pln, x, y, N, g, w, x_ps, y_ps, &ep)) return ORE_OK;
+  if (!fits_i32(N * int64_t(p.ep_tr) * p.ep_tc) || !fits_i32(g.C * x_ps) || !fits_i32(y_ps * ep.win.Ho * ep.win.Wo) ||
+      x_ps < g.H * g.W)
     return ORE_OK;
-  ConvParams p{};
-  p.x = x; p.wp = static_cast<const float*>(wp); p.bias = bias; p.y = static_cast<float*>(y);
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.M = int(M); p.kh = int(kh); p.kw = int(kw); p.sh = int(sh); p.sw = int(sw);
-  p.pt = int(win.pt); p.pl = int(win.pl); p.Ho = int(win.Ho); p.Wo = int(win.Wo);
-  p.K = f16_conv_k(pln.xmode, int(C), int(kh), int(kw));
-  p.x_ps = int(x_ps); p.y_ps = int(y_ps);
-  p.x_nstride = x_nstride; p.y_nstride = y_nstride;
-  p.relu = relu ? 1 : 0;
-  p.Mp = pln.Mp;
-  p.ep_pt = int(ep.win.pt); p.ep_pl = int(ep.win.pl); p.ep_Ho = int(ep.win.Ho); p.ep_Wo = int(ep.win.Wo);
-  p.ep_tr = tr; p.ep_tc = tc;
+  // P, Ntot, vec_out, is1x1 stay 0: the persistent kernels walk pooled tiles, not GEMM columns, and
+  // gather the 7x7 taps themselves; no x_guard: an f16 model's input is not read through the arena
+  const C1Squeeze* sq = w.sq16;
   if (!conv_pair_pool_f16_eligible(p, sq)) return ORE_OK;
+  int tile;
   if (pln.epv == C1_BAND_F16_VARIANT && sq && conv_band_pool_f16_eligible(p, sq)) {  // the band walker (round 6)
     launch_conv_band_pool_f16(p, *sq, ctx->stream);
-    last_conv_tile = C1_BAND_F16_TILE;
+    tile = C1_BAND_F16_TILE;
   } else {
     launch_conv_pair_pool_f16(p, sq, ctx->stream);
-    last_conv_tile = C1_POOL_F16_TILE;
+    tile = C1_POOL_F16_TILE;
   }
   ORE_HIP_CHECK(ctx, hipGetLastError());
-  *ran = true;
-  return ORE_OK;
+  return {ORE_OK, tile};
 }
 
-ore_status run_conv_f16(ore_ctx* ctx, const ConvPlan& pln, const void* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                        int64_t x_nstride, int64_t x_ps, const void* wp, const int2* ktab, int64_t M, int64_t kh,
-                        int64_t kw, const float* bias, const Window& win, int64_t sh, int64_t sw, bool relu, void* y,
-                        int64_t y_nstride, int64_t y_ps, const F16Epool* ep) {
+ConvRun run_conv_f16(ore_ctx* ctx, const ConvPlan& pln, const Ref& x, const Ref& y, int64_t N, const ConvGeom& g,
+                     const ConvOperands& w, const PoolGeom* ep) {
   if (N == 0) return ORE_OK;
   if (!pln.f16) return set_error(ctx, ORE_ERR_INVALID, "internal: run_conv_f16 needs an f16 plan");
   const bool nchw = pln.xmode == F16_X_NCHW32;
-  if (x_ps == 0) x_ps = nchw ? H * W : C;
-  if (y_ps == 0) y_ps = M;
-  if (nchw ? x_ps < H * W : x_ps < C) return set_error(ctx, ORE_ERR_INVALID, "input stride below its extent");
-  if (y_ps < M) return set_error(ctx, ORE_ERR_INVALID, "output pixel stride below the channel count");
+  const int64_t x_ps = nchw ? plane_stride(x, g.H * g.W) : pixel_stride(x, g.C), y_ps = pixel_stride(y, g.M);
+  if (nchw ? x_ps < g.H * g.W : x_ps < g.C) return set_error(ctx, ORE_ERR_INVALID, "input stride below its extent");
+  if (y_ps < g.M) return set_error(ctx, ORE_ERR_INVALID, "output pixel stride below the channel count");
   if (pln.xmode == F16_X_NHWC_VEC &&
-      (C % 8 || x_ps % 8 || x_nstride % 8 || (reinterpret_cast<uintptr_t>(x) & 15)))
+      (g.C % 8 || x_ps % 8 || x.nstride % 8 || (reinterpret_cast<uintptr_t>(x.p) & 15)))
     return set_error(ctx, ORE_ERR_INVALID, "internal: 16-B NHWC gather needs C, strides %% 8 == 0 and an aligned input");
-  if (pln.xmode == F16_X_NHWC_PAIR && (C > 4 || x_ps != 4 || x_nstride % 4 || (reinterpret_cast<uintptr_t>(x) & 7)))
+  if (pln.xmode == F16_X_NHWC_PAIR && (g.C > 4 || x_ps != 4 || x.nstride % 4 || (reinterpret_cast<uintptr_t>(x.p) & 7)))
     return set_error(ctx, ORE_ERR_INVALID, "internal: the tap-pair gather needs an NHWC4 input");
-  if (!ktab) return set_error(ctx, ORE_ERR_INVALID, "internal: gather table missing");
-  ConvParams p{};
-  p.x = static_cast<const float*>(x); p.wp = static_cast<const float*>(wp); p.ktab = ktab; p.bias = bias;
-  p.y = static_cast<float*>(y);
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.M = int(M); p.kh = int(kh); p.kw = int(kw); p.sh = int(sh); p.sw = int(sw);
-  p.pt = int(win.pt); p.pl = int(win.pl);
-  p.Ho = int(win.Ho); p.Wo = int(win.Wo);
-  p.K = f16_conv_k(pln.xmode, int(C), int(kh), int(kw));
-  p.P = int(win.Ho * win.Wo);
-  p.x_ps = int(x_ps);
-  p.y_ps = int(y_ps);
-  p.Ntot = N * p.P;
-  p.x_nstride = x_nstride;
-  p.y_nstride = y_nstride;
-  p.relu = relu ? 1 : 0;
-  p.Mp = pln.Mp;
-  p.x_f32 = nchw ? 1 : 0;
-  p.vec_out = (M % 8 == 0 && y_ps % 8 == 0 && y_nstride % 8 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
-  if (ep) {  // pooled epilogue: y is the pool's NHWC output [pwin.Ho][pwin.Wo]
-    int tr = 0, tc = 0;
-    if (epool_tile(win.Ho, win.Wo, ep->kh, ep->kw, ep->sh, ep->sw, ep->win, &tr, &tc) == 0.0)
-      return set_error(ctx, ORE_ERR_INVALID, "internal: the pooled epilogue takes 3x3 / stride-2 pools");
-    p.ep_pt = int(ep->win.pt); p.ep_pl = int(ep->win.pl); p.ep_Ho = int(ep->win.Ho); p.ep_Wo = int(ep->win.Wo);
-    p.ep_tr = tr; p.ep_tc = tc;
-    p.Ntot = N * int64_t(tr) * tc * CONV_EPOOL_BN;
-  }
-  if (!fits_i32(x_nstride * N + 256) || !fits_i32(y_nstride * N + 256) || !fits_i32(int64_t(pln.krows) * pln.Mp) ||
-      !fits_i32(p.Ntot + 256) || (p.Ntot + 127) / 128 * ((M + 31) / 32) >= (int64_t(1) << 31))
+  if (!w.ktab) return set_error(ctx, ORE_ERR_INVALID, "internal: gather table missing");
+  ConvParams p;
+  if (!conv_params(&p, pln, x, y, N, g, w, x_ps, y_ps, ep))  // y is then the pool's NHWC output [ep->win.Ho][ep->win.Wo]
+    return set_error(ctx, ORE_ERR_INVALID, "internal: the pooled epilogue takes 3x3 / stride-2 pools");
+  p.P = int(g.win.Ho * g.win.Wo);
+  p.Ntot = ep ? epool_columns(p, N) : N * p.P;  // NHWC output: columns dense over the Ho x Wo pixels
+  // 16-B epilogue stores of 8 halves along the channels
+  p.vec_out = (g.M % 8 == 0 && y_ps % 8 == 0 && y.nstride % 8 == 0 && (reinterpret_cast<uintptr_t>(y.p) & 15) == 0) ? 1 : 0;
+  // is1x1 stays 0: the f16 kernels always gather through ktab; no x_guard: they read nothing before x
+  if (!fits_i32(x.nstride * N + 256) || !fits_i32(y.nstride * N + 256) || !fits_i32(int64_t(pln.krows) * pln.Mp) ||
+      !fits_i32(p.Ntot + 256) || (p.Ntot + 127) / 128 * ((g.M + 31) / 32) >= (int64_t(1) << 31))
     return set_error(ctx, ORE_ERR_INVALID, "conv geometry exceeds 32-bit indexing");
-  // image chunks whose extents fit the kernels' 32-bit byte offsets (the NHWC_VEC kernel reads x
-  // through a buffer resource)
+  // the NHWC_VEC kernel reads x through a buffer resource
   const int xes = nchw ? 4 : 2;
-  const int64_t x_img = (nchw ? C * x_ps : H * W * x_ps) * xes;
-  const int64_t y_img = (ep ? ep->win.Ho * ep->win.Wo : win.Ho * win.Wo) * y_ps * 2;
-  const int64_t nb = image_chunk(N, x_nstride, x_img, xes, y_nstride, y_img, 2);
+  const ChunkSide xs{x.nstride, (nchw ? g.C * x_ps : g.H * g.W * x_ps) * xes, xes};
+  const ChunkSide ys{y.nstride, (ep ? ep->win.Ho * ep->win.Wo : g.win.Ho * g.win.Wo) * y_ps * 2, 2};
+  const int64_t nb = image_chunk(N, xs, ys);
   if (nb == 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "f16 conv: one image exceeds 2 GiB");
-  for (int64_t i0 = 0; i0 < N; i0 += nb) {
-    const int64_t nc = std::min(nb, N - i0);
+  int tile = -1;
+  for (Chunk c = chunk_at(0, N, nb); c.nc > 0; c = chunk_at(c.i0 + c.nc, N, nb)) {
     ConvParams q = p;
-    q.x = reinterpret_cast<const float*>(static_cast<const char*>(x) + i0 * x_nstride * xes);
-    q.y = reinterpret_cast<float*>(static_cast<char*>(y) + i0 * y_nstride * 2);
-    q.N = int(nc);
-    q.Ntot = ep ? nc * int64_t(p.ep_tr) * p.ep_tc * CONV_EPOOL_BN : nc * p.P;
-    q.x_bytes = (nc - 1) * x_nstride * xes + x_img;
+    q.x = reinterpret_cast<const float*>(reinterpret_cast<const char*>(x.p) + c.i0 * x.nstride * xes);
+    q.y = reinterpret_cast<float*>(reinterpret_cast<char*>(y.p) + c.i0 * y.nstride * 2);
+    q.N = int(c.nc);
+    q.Ntot = ep ? epool_columns(p, c.nc) : c.nc * p.P;
+    q.x_bytes = xs.bytes(c.nc);
     if (ep)
       launch_conv_f16_epool(q, pln.xmode, ctx->stream);
     else
-      launch_conv(q, pln, ctx->stream);
+      tile = launch_conv(q, pln, ctx->stream);
     ORE_HIP_CHECK(ctx, hipGetLastError());
   }
-  return ORE_OK;
+  return {ORE_OK, tile};
 }
 
-ore_status run_maxpool_nhwc(ore_ctx* ctx, const void* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t x_nstride,
-                            int64_t x_cs, int64_t kh, int64_t kw, const Window& win, int64_t sh, int64_t sw, void* y,
-                            int64_t y_nstride, int64_t y_cs) {
-  if (N == 0) return ORE_OK;
-  NhwcPoolParams p{};
-  p.x = static_cast<const _Float16*>(x); p.y = static_cast<_Float16*>(y);
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.kh = int(kh); p.kw = int(kw); p.sh = int(sh); p.sw = int(sw);
-  p.pt = int(win.pt); p.pl = int(win.pl);
-  p.Ho = int(win.Ho); p.Wo = int(win.Wo);
-  p.x_cs = int(x_cs ? x_cs : C); p.y_cs = int(y_cs ? y_cs : C);
-  p.x_nstride = x_nstride; p.y_nstride = y_nstride;
-  launch_maxpool_nhwc(p, ctx->stream);
-  ORE_HIP_CHECK(ctx, hipGetLastError());
-  return ORE_OK;
+// the PoolParams / NhwcPoolParams fields the two MaxPool layouts share
+template <class P>
+static void pool_params(P* p, int64_t N, int64_t C, int64_t H, int64_t W, const PoolGeom& g) {
+  p->N = int(N); p->C = int(C); p->H = int(H); p->W = int(W);
+  p->kh = int(g.kh); p->kw = int(g.kw); p->sh = int(g.sh); p->sw = int(g.sw);
+  p->pt = int(g.win.pt); p->pl = int(g.win.pl);
+  p->Ho = int(g.win.Ho); p->Wo = int(g.win.Wo);
 }
 
-ore_status run_maxpool(ore_ctx* ctx, const float* x, int64_t N, int64_t C, int64_t H, int64_t W,
-                       int64_t x_nstride, int64_t kh, int64_t kw, const Window& win, int64_t sh, int64_t sw,
-                       float* y, int64_t y_nstride, int64_t x_ps, int64_t y_ps, int es) {
+ore_status run_maxpool(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int64_t C, int64_t H, int64_t W,
+                       const PoolGeom& pool) {
   if (N == 0) return ORE_OK;
-  PoolParams p{};
-  p.es = es;
-  p.variant = ctx->pool_variant;
-  p.x_ps = int(x_ps ? x_ps : H * W);
-  p.y_ps = int(y_ps ? y_ps : win.Ho * win.Wo);
-  p.x = x; p.y = y;
-  p.N = int(N); p.C = int(C); p.H = int(H); p.W = int(W);
-  p.kh = int(kh); p.kw = int(kw); p.sh = int(sh); p.sw = int(sw);
-  p.pt = int(win.pt); p.pl = int(win.pl);
-  p.Ho = int(win.Ho); p.Wo = int(win.Wo);
-  p.x_nstride = x_nstride; p.y_nstride = y_nstride;
-  launch_maxpool(p, ctx->stream);
+  if (x.es == 2) {
+    NhwcPoolParams p{};
+    pool_params(&p, N, C, H, W, pool);
+    p.x = reinterpret_cast<const _Float16*>(x.p); p.y = reinterpret_cast<_Float16*>(y.p);
+    p.x_cs = int(pixel_stride(x, C)); p.y_cs = int(pixel_stride(y, C));
+    p.x_nstride = x.nstride; p.y_nstride = y.nstride;
+    launch_maxpool_nhwc(p, ctx->stream);
+  } else {
+    PoolParams p{};
+    pool_params(&p, N, C, H, W, pool);
+    p.es = x.es;
+    p.variant = ctx->pool_variant;
+    p.x_ps = int(plane_stride(x, H * W));
+    p.y_ps = int(plane_stride(y, pool.win.Ho * pool.win.Wo));
+    p.x = x.p; p.y = y.p;
+    p.x_nstride = x.nstride; p.y_nstride = y.nstride;
+    launch_maxpool(p, ctx->stream);
+  }
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }
@@ -726,15 +674,13 @@ ore_status ore_conv2d_f32(ore_ctx* ctx, const ore_tensor* x, const ore_tensor* w
                      (long long)x->dims[0], (long long)w->dims[0], (long long)win.Ho, (long long)win.Wo);
   if (x->dims[0] == 0) return ORE_OK;
   const int2* kt = nullptr;
-  const ConvPlan pln = conv_plan(w->dims[0], w->dims[1], x->dims[2], x->dims[3], w->dims[2], w->dims[3], a->strides[0],
-                                 a->strides[1], win, false, 0, ctx->conv_algo == ORE_CONV_ALGO_WINOGRAD,
-                                 ctx->conv_tile);
-  float* wp = pack_to_scratch(ctx, pln, w->data, false, w->dims[0], w->dims[1], w->dims[2], w->dims[3], x->dims[2],
-                              x->dims[3], &kt);
+  const ConvGeom g{x->dims[1], x->dims[2], x->dims[3], w->dims[0], w->dims[2], w->dims[3], a->strides[0], a->strides[1],
+                   win, a->fuse_relu != 0};
+  const ConvPlan pln = conv_plan(g.M, g.C, g.H, g.W, g.kh, g.kw, g.sh, g.sw, win, false, 0,
+                                 ctx->conv_algo == ORE_CONV_ALGO_WINOGRAD, ctx->conv_tile);
+  float* wp = pack_to_scratch(ctx, pln, w->data, false, g.M, g.C, g.kh, g.kw, g.H, g.W, &kt);
   if (!wp) return ORE_ERR_OOM;
-  return run_conv(ctx, pln, x->data, x->dims[0], x->dims[1], x->dims[2], x->dims[3], nstride_of(x), wp, kt, w->dims[0],
-                  w->dims[2], w->dims[3], bias ? bias->data : nullptr, win, a->strides[0], a->strides[1],
-                  a->fuse_relu != 0, y->data, nstride_of(y));
+  return run_conv(ctx, pln, ref_of(x), ref_of(y), x->dims[0], g, {wp, kt, bias ? bias->data : nullptr}).st;
 }
 
 ore_status ore_maxpool2d_f32(ore_ctx* ctx, const ore_tensor* x, const ore_pool_attrs* a, ore_tensor* y) {
@@ -746,8 +692,8 @@ ore_status ore_maxpool2d_f32(ore_ctx* ctx, const ore_tensor* x, const ore_pool_a
   if (st) return st;
   if (y->dims[0] != x->dims[0] || y->dims[1] != x->dims[1] || y->dims[2] != win.Ho || y->dims[3] != win.Wo)
     return set_error(ctx, ORE_ERR_INVALID, "MaxPool output dims mismatch");
-  return run_maxpool(ctx, x->data, x->dims[0], x->dims[1], x->dims[2], x->dims[3], nstride_of(x), a->kernel[0],
-                     a->kernel[1], win, a->strides[0], a->strides[1], y->data, nstride_of(y));
+  return run_maxpool(ctx, ref_of(x), ref_of(y), x->dims[0], x->dims[1], x->dims[2], x->dims[3],
+                     {a->kernel[0], a->kernel[1], a->strides[0], a->strides[1], win});
 }
 
 ore_status ore_relu_f32(ore_ctx* ctx, const ore_tensor* x, ore_tensor* y) {
@@ -830,8 +776,8 @@ ore_status ore_matmul_f32(ore_ctx* ctx, const ore_tensor* a, const ore_tensor* b
   const ConvPlan pln = conv_plan(b->dims[1], b->dims[0], 1, 1, 1, 1, 1, 1, win, false, 0, false, ctx->conv_tile);
   float* wp = pack_to_scratch(ctx, pln, b->data, true, b->dims[1], b->dims[0], 1, 1, 1, 1, &kt);
   if (!wp) return ORE_ERR_OOM;
-  return run_conv(ctx, pln, a->data, a->dims[0], a->dims[1], 1, 1, a->dims[1], wp, kt, b->dims[1], 1, 1, nullptr, win, 1, 1,
-                  false, y->data, y->dims[1]);
+  const ConvGeom g{a->dims[1], 1, 1, b->dims[1], 1, 1, 1, 1, win, false};
+  return run_conv(ctx, pln, ref_of(a), ref_of(y), a->dims[0], g, {wp, kt, nullptr}).st;
 }
 
 ore_status ore_gap_f32(ore_ctx* ctx, const ore_tensor* x, ore_tensor* y) {
