@@ -177,6 +177,36 @@ ore_status ore_reshape(const ore_tensor* x, const int64_t* shape, int32_t n_shap
 #define ORE_PRE_REVERSE_CHANNELS 1
 ore_status ore_preprocess_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t h, int64_t w, int64_t c,
                              const float* scale, const float* shift, int32_t flags, ore_tensor* y);
+/* Resize and crop in front of the conversion (extension, ore_resize.hip): the images are [n,hs,ws,c], of any
+ * size up to 16384 x 16384, and y is [n,c,H,W].  The geometry is four integers: the whole source image is
+ * resized to rh x rw (each 1..16384), and y is the H x W window of that resized image whose first sample is
+ * (top, left): 0 <= top, top + H <= rh, 0 <= left, left + W <= rw.  Resize(256) + CenterCrop(224) of a
+ * 375 x 500 image is {256, 341, 16, 58}; a plain resize {H, W, 0, 0}; a plain crop {hs, ws, top, left}.
+ * The filter is bilinear with half-pixel centres and no antialiasing (cv2.INTER_LINEAR;
+ * F.interpolate(mode="bilinear", align_corners=False, antialias=False)), stated in integers.  Per axis, for
+ * S source samples resized to D and resized index o (top + r for rows, left + q for columns):
+ *     num = max((2 o + 1) S - D, 0);  i0 = num div 2 D;  rem = num mod 2 D;
+ *     if (i0 >= S - 1) { i0 = S - 1; rem = 0; }   i1 = min(i0 + 1, S - 1);   t = fdiv_rn((float)rem, (float)(2 D))
+ * and per output element, with a, b the bytes at (y0, x0), (y0, x1) and c, d those at (y1, x0), (y1, x1) of
+ * source channel cs, converted to float32:
+ *     top = a + (b - a) tx;  bot = c + (d - c) tx;  v = top + (bot - top) ty;  y = v scale[ch] + shift[ch]
+ * where every -, * and + rounds on its own (never an FMA): numpy float32 arrays reproduce it bit for bit,
+ * and with rh, rw = hs, ws it is ore_preprocess_u8 of the cropped bytes exactly.
+ *  ore_resize_taps: one axis's table (i0, i1, t for the `count` resized indices from `origin`) into HOST
+ *    arrays; host only, it touches no device.  It is the map the kernels use (csrc/ore_resize_geom.h).
+ *  ore_preprocess_resize_u8: x, scale, shift, flags and y as for ore_preprocess_u8 (y may be a slice, of any
+ *    alignment); H, W are y->dims[2], y->dims[3].  One launch, one thread per output pixel.  The pointers and
+ *    the geometry are checked first and the context last, all before any device call (ORE_ERR_INVALID);
+ *    n == 0 is ORE_OK and launches nothing.  Every image of a call has the same size; rows are dense (no
+ *    row stride). */
+typedef struct ore_resize {
+  int64_t rh, rw, top, left;
+} ore_resize;
+ore_status ore_resize_taps(int64_t src, int64_t resized, int64_t origin, int64_t count, int32_t* i0, int32_t* i1,
+                           float* t);
+ore_status ore_preprocess_resize_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t hs, int64_t ws, int64_t c,
+                                    const ore_resize* g, const float* scale, const float* shift, int32_t flags,
+                                    ore_tensor* y);
 /* Row-wise top-k (extension; no reference counterpart -- the reference prints the full output tensor): the
  * k best elements of every row of x, in one launch (ore_topk.hip).  Rows are x->dims[0], the row length D
  * the product of the remaining dims (as for ore_softmax_f32); x->nstride >= D is honoured.  values and
@@ -359,8 +389,15 @@ ore_status ore_model_graph_launch(ore_model* m);
  *    _step_tile / _step_times do not see it, and ore_model_autotune stays float32-only (tune on a batch
  *    converted with ore_preprocess_u8).
  *  ore_model_graph_capture_u8: as ore_model_graph_capture, with the conversion inside the graph:
- *    ore_model_graph_launch converts and runs whatever d_input holds at that moment. */
+ *    ore_model_graph_launch converts and runs whatever d_input holds at that moment.
+ *  ore_model_set_input_resize: from then on every _u8 entry (run_u8, classify_u8 and their captures) takes
+ *    [n,hs,ws,C] images and resizes and crops them to the model's H x W with geometry g (see
+ *    ore_preprocess_resize_u8; checked here, ORE_ERR_INVALID) in the launch that converts; g == NULL
+ *    restores the direct conversion of [n,H,W,C].  scale, shift and flags stay those of
+ *    ore_model_set_input_norm; the staging buffer, the chunks (chunk i0 reads from image i0 of d_input) and
+ *    the step list are unchanged, and a captured graph keeps the geometry it was captured with. */
 ore_status ore_model_set_input_norm(ore_model* m, const float* scale, const float* shift, int32_t c, int32_t flags);
+ore_status ore_model_set_input_resize(ore_model* m, int64_t hs, int64_t ws, const ore_resize* g);
 ore_status ore_model_run_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
 ore_status ore_model_graph_capture_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
 /* Top-k output (extension, see ore_topk_f32): the classify entries run the graph as ore_model_run /

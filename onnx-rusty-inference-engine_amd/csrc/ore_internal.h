@@ -197,5 +197,10 @@ ore_status run_maxpool(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int6
 // scale / shift: host arrays of c floats or null (1 / 0).  x, y, N and y_nstride are the caller's to set.
 ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const float* scale, const float* shift,
                           int32_t flags, PreprocParams* p);
+// as preproc_params for the resizing conversion of [.,hs,ws,c] images to h x w (ore_preprocess_resize_u8 and
+// the model's _u8 entries after ore_model_set_input_resize): also checks the sizes against RESIZE_MAX and
+// that the crop lies inside the resized image
+ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
+                         const float* scale, const float* shift, int32_t flags, ResizeParams* p);
 
 }  // namespace ore

@@ -445,6 +445,21 @@ struct PreprocParams {
   float scale[4], shift[4];
 };
 void launch_preproc_u8(const PreprocParams& p, hipStream_t s);
+// uint8 NHWC -> bilinear resize + crop -> f32 NCHW with the same scale and shift (ore_resize.hip).  The source
+// image [Hs][Ws][C] is resized to Rh x Rw (taps: ore_resize_geom.h) and the H x W window at (top, left) of
+// that is written; plane / scale / shift are indexed by SOURCE channel as in PreprocParams.
+struct ResizeParams {
+  const unsigned char* x;  // [N][Hs][Ws][C]
+  float* y;                // [N][C][H][W] at an image stride of y_nstride elements
+  long long N;
+  long long y_nstride;
+  int Hs, Ws, C;           // all sizes <= RESIZE_MAX
+  int Rh, Rw, top, left;
+  int H, W;
+  int plane[4];
+  float scale[4], shift[4];
+};
+void launch_resize_u8(const ResizeParams& p, hipStream_t s);
 // row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,

@@ -915,7 +915,14 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const Value& iv = m->values[m->input_value];
   PreprocParams pre;
-  if (d_u8) {
+  ResizeParams rsz;  // instead of pre after ore_model_set_input_resize
+  if (d_u8 && m->in_resized) {
+    if (ore_status st = resize_params(ctx, m->in_hs, m->in_ws, iv.dims[1], iv.dims[2], iv.dims[3], &m->in_resize, m->in_scale,
+                                      m->in_shift, m->in_flags, &rsz))
+      return st;
+    rsz.y = m->stage;
+    rsz.y_nstride = iv.per_image();
+  } else if (d_u8) {
     if (ore_status st = preproc_params(ctx, iv.dims[2], iv.dims[3], iv.dims[1], m->in_scale, m->in_shift, m->in_flags, &pre))
       return st;
     pre.y = m->stage;
@@ -947,9 +954,15 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
     const int64_t nc = std::min(chunk, n - i0);
     const float* x = d_input ? d_input + i0 * in_img : m->stage;
     if (d_u8) {  // before the pass's first timing event: ore_model_step_times does not include it
-      pre.x = d_u8 + i0 * in_img;
-      pre.N = nc;
-      launch_preproc_u8(pre, ctx->stream);
+      if (m->in_resized) {  // the source images have their own size
+        rsz.x = d_u8 + i0 * m->in_hs * m->in_ws * iv.dims[1];
+        rsz.N = nc;
+        launch_resize_u8(rsz, ctx->stream);
+      } else {
+        pre.x = d_u8 + i0 * in_img;
+        pre.N = nc;
+        launch_preproc_u8(pre, ctx->stream);
+      }
       ORE_HIP_CHECK(ctx, hipGetLastError());
     }
     if (ore_status st = run_pass(m, x, nc, d_classes ? m->rows : d_output + i0 * out_img,
@@ -983,6 +996,23 @@ ore_status ore_model_set_input_norm(ore_model* m, const float* scale, const floa
     m->in_shift[i] = shift ? shift[i] : 0.0f;
   }
   m->in_flags = flags;
+  return ORE_OK;
+}
+
+ore_status ore_model_set_input_resize(ore_model* m, int64_t hs, int64_t ws, const ore_resize* g) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  if (!g) {  // back to the direct conversion of [n,H,W,C]
+    m->in_resized = false;
+    return ORE_OK;
+  }
+  const Value& iv = m->values[m->input_value];
+  ResizeParams rsz;
+  if (ore_status st = resize_params(m->ctx, hs, ws, iv.dims[1], iv.dims[2], iv.dims[3], g, m->in_scale, m->in_shift, m->in_flags, &rsz))
+    return st;
+  m->in_hs = hs;
+  m->in_ws = ws;
+  m->in_resize = *g;
+  m->in_resized = true;
   return ORE_OK;
 }
 

@@ -183,6 +183,10 @@ struct ore_model {
   size_t stage_bytes = 0;
   float in_scale[4] = {1.f, 1.f, 1.f, 1.f}, in_shift[4] = {0.f, 0.f, 0.f, 0.f};
   int32_t in_flags = 0;
+  // ore_model_set_input_resize: the _u8 entries take [n, in_hs, in_ws, C] and resize into the staging buffer
+  bool in_resized = false;
+  int64_t in_hs = 0, in_ws = 0;
+  ore_resize in_resize = {0, 0, 0, 0};
   // top-k output (ore_model_classify): the f32 rows buffer of run_batch images' outputs the graph writes
   // and the selection reads, and the k of ore_model_set_topk
   float* rows = nullptr;

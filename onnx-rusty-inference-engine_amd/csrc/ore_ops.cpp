@@ -9,6 +9,7 @@
 
 #include "ore_chunk.h"
 #include "ore_internal.h"
+#include "ore_resize_geom.h"
 
 namespace {
 thread_local std::string g_global_err;
@@ -130,6 +131,29 @@ ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const f
     p->plane[s] = ch;
     p->scale[s] = scale ? scale[ch] : 1.0f;
     p->shift[s] = shift ? shift[ch] : 0.0f;
+  }
+  return ORE_OK;
+}
+
+ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
+                         const float* scale, const float* shift, int32_t flags, ResizeParams* p) {
+  if (!g) return set_error(ctx, ORE_ERR_INVALID, "null resize geometry");
+  PreprocParams q;  // c, the flags, the reversal and the output size: the direct conversion's checks
+  if (ore_status st = preproc_params(ctx, h, w, c, scale, shift, flags, &q)) return st;
+  if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g->rh < 1 || g->rw < 1 || g->rh > RESIZE_MAX || g->rw > RESIZE_MAX)
+    return set_error(ctx, ORE_ERR_INVALID, "resize: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)hs,
+                     (long long)ws, (long long)g->rh, (long long)g->rw, RESIZE_MAX);
+  if (!resize_axis_ok(hs, g->rh, g->top, h) || !resize_axis_ok(ws, g->rw, g->left, w))
+    return set_error(ctx, ORE_ERR_INVALID, "resize: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
+                     (long long)h, (long long)w, (long long)g->top, (long long)g->left, (long long)g->rh, (long long)g->rw);
+  *p = ResizeParams{};
+  p->Hs = int(hs); p->Ws = int(ws); p->C = int(c);
+  p->Rh = int(g->rh); p->Rw = int(g->rw); p->top = int(g->top); p->left = int(g->left);
+  p->H = int(h); p->W = int(w);
+  for (int s = 0; s < int(c); ++s) {
+    p->plane[s] = q.plane[s];
+    p->scale[s] = q.scale[s];
+    p->shift[s] = q.shift[s];
   }
   return ORE_OK;
 }
@@ -835,6 +859,43 @@ ore_status ore_preprocess_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t 
   p.y_nstride = nstride_of(y);
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   launch_preproc_u8(p, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_resize_taps(int64_t src, int64_t resized, int64_t origin, int64_t count, int32_t* i0, int32_t* i1, float* t) {
+  if (!i0 || !i1 || !t) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  if (!resize_axis_ok(src, resized, origin, count))
+    return set_error(nullptr, ORE_ERR_INVALID, "resize taps: %lld samples resized to %lld (each 1..%d), [%lld, %lld + %lld) of them",
+                     (long long)src, (long long)resized, RESIZE_MAX, (long long)origin, (long long)origin, (long long)count);
+  for (int64_t k = 0; k < count; ++k) {
+    const ResizeTap r = resize_tap(int(src), int(resized), int(origin + k));
+    i0[k] = r.i0;
+    i1[k] = r.i1;
+    t[k] = r.t;
+  }
+  return ORE_OK;
+}
+
+ore_status ore_preprocess_resize_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t hs, int64_t ws, int64_t c,
+                                    const ore_resize* g, const float* scale, const float* shift, int32_t flags, ore_tensor* y) {
+  // the pointers, then the geometry, then the context: a host can exercise every check without a device
+  if (!x || !g || !y || !y->data) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n < 0) return set_error(ctx, ORE_ERR_INVALID, "negative batch %lld", (long long)n);
+  if (y->ndim != 4 || y->dims[0] != n || y->dims[1] != c)
+    return set_error(ctx, ORE_ERR_INVALID, "resize output must be [n,c,H,W] for the [n,hs,ws,c] input");
+  ResizeParams p;
+  if (ore_status st = resize_params(ctx, hs, ws, c, y->dims[2], y->dims[3], g, scale, shift, flags, &p)) return st;
+  if (nstride_of(y) < c * y->dims[2] * y->dims[3])
+    return set_error(ctx, ORE_ERR_INVALID, "resize output: image stride %lld below c*H*W", (long long)nstride_of(y));
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null context");
+  if (n == 0) return ORE_OK;
+  p.x = x;
+  p.y = y->data;
+  p.N = n;
+  p.y_nstride = nstride_of(y);
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_resize_u8(p, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

@@ -27,7 +27,7 @@ LOAD_NO_WINOGRAD = 4  # ore_model_load_ex flag: 3x3 stride-1 convs on the direct
 LOAD_RETIRED_MASK = 10  # ABI 1's LOAD_X3 / LOAD_X3_ALL: rejected (ORE_ERR_UNSUPPORTED) since ABI 2
 ABI_VERSION = 2  # ORE_ABI_VERSION this binding was written against
 CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD = 0, 1  # ore_ctx_set_conv_algo (per-op ore_conv2d_f32)
-PRE_REVERSE_CHANNELS = 1  # ore_preprocess_u8 / ore_model_set_input_norm flag: RGB <-> BGR
+PRE_REVERSE_CHANNELS = 1  # ore_preprocess_u8 / _resize_u8 / ore_model_set_input_norm flag: RGB <-> BGR
 PAD = {"NOTSET": 0, "NOT_SET": 0, "SAME_UPPER": 1, "SAME_LOWER": 2, "VALID": 3}
 
 # every symbol include/ore.h declares (checked by tests/test_abi.py on CPU)
@@ -37,6 +37,7 @@ EXPORTED = [
     "ore_conv_out_shape", "ore_pool_out_shape", "ore_conv2d_f32", "ore_maxpool2d_f32", "ore_relu_f32",
     "ore_add_f32", "ore_softmax_f32", "ore_matmul_f32", "ore_gap_f32", "ore_concat_f32", "ore_dropout_f32",
     "ore_reshape", "ore_preprocess_u8", "ore_model_set_input_norm", "ore_model_run_u8", "ore_model_graph_capture_u8",
+    "ore_resize_taps", "ore_preprocess_resize_u8", "ore_model_set_input_resize",
     "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
     "ore_model_graph_capture_classify", "ore_model_graph_capture_classify_u8",
     "ore_model_parse", "ore_model_load", "ore_model_load_ex", "ore_model_destroy", "ore_model_set_fusion", "ore_model_input_dims",
@@ -56,6 +57,11 @@ class OreError(RuntimeError):
 class Tensor(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("ndim", ctypes.c_int32), ("dims", ctypes.c_int64 * 4),
                 ("nstride", ctypes.c_int64)]
+
+
+class Resize(ctypes.Structure):
+    """ore_resize: the source image resized to rh x rw, of which the window at (top, left) is produced."""
+    _fields_ = [("rh", ctypes.c_int64), ("rw", ctypes.c_int64), ("top", ctypes.c_int64), ("left", ctypes.c_int64)]
 
 
 class ConvAttrs(ctypes.Structure):
@@ -115,6 +121,9 @@ def load():
         "ore_model_set_input_norm": (i32, [vp, F32P, F32P, i32, i32]),
         "ore_model_run_u8": (i32, [vp, vp, i64, vp]),
         "ore_model_graph_capture_u8": (i32, [vp, vp, i64, vp]),
+        "ore_resize_taps": (i32, [i64, i64, i64, i64, vp, vp, vp]),
+        "ore_preprocess_resize_u8": (i32, [vp, vp, i64, i64, i64, i64, ctypes.POINTER(Resize), F32P, F32P, i32, T]),
+        "ore_model_set_input_resize": (i32, [vp, i64, i64, ctypes.POINTER(Resize)]),
         "ore_topk_f32": (i32, [vp, T, i32, vp, vp]),
         "ore_model_set_topk": (i32, [vp, i32]),
         "ore_model_classify": (i32, [vp, vp, i64, vp, vp]),

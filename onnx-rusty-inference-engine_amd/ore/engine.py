@@ -16,10 +16,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, OreError, PoolAttrs, Tensor, check, load
+from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, OreError, PoolAttrs, Resize,
+                   Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "topk", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "resize_taps", "center_crop_geometry", "topk", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -269,6 +270,65 @@ def preprocess_u8(ctx: Context, x, scale=None, shift=None, reverse_channels: boo
     return y
 
 
+def resize_taps(src: int, resized: int, origin: int, count: int):
+    """ore_resize_taps (host only): the bilinear tap table of one axis of `src` samples resized to `resized`,
+    for the `count` resized indices from `origin`: (i0 int32, i1 int32, t float32), sample = s[i0] +
+    (s[i1] - s[i0]) * t.  The table the resize kernels use (half-pixel centres, no antialiasing)."""
+    n = min(max(int(count), 0), 16384)  # the library rejects anything outside 1..16384
+    i0, i1, t = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+    check(load().ore_resize_taps(int(src), int(resized), int(origin), int(count), i0.ctypes.data_as(ctypes.c_void_p),
+                                 i1.ctypes.data_as(ctypes.c_void_p), t.ctypes.data_as(ctypes.c_void_p)))
+    return i0, i1, t
+
+
+def center_crop_geometry(src_hw, short: int, out_hw):
+    """(resized_hw, origin) of "resize the short side to `short`, centre-crop `out_hw`" for a source of
+    `src_hw`, by this helper's own rule: the short side becomes `short`, the long side
+    (short * long) // short_src, and the crop starts at ((Rh - H) // 2, (Rw - W) // 2).  Libraries differ in
+    how they round both: a caller following another convention passes its four integers instead."""
+    hs, ws = (int(v) for v in src_hw)
+    h, w = (int(v) for v in out_hw)
+    short = int(short)
+    if min(hs, ws, h, w, short) < 1:
+        raise OreError(1, f"center_crop_geometry: sizes must be positive, got {tuple(src_hw)}, {short}, {tuple(out_hw)}")
+    if hs <= ws:
+        rh, rw = short, (short * ws) // hs
+    else:
+        rh, rw = (short * hs) // ws, short
+    if h > rh or w > rw:
+        raise OreError(1, f"center_crop_geometry: the {h} x {w} crop is larger than the {rh} x {rw} resized image")
+    return (rh, rw), ((rh - h) // 2, (rw - w) // 2)
+
+
+def _resize_arg(src_hw, out_hw, resized_hw, origin):
+    """The ore_resize of a [hs, ws] -> resized_hw (None: out_hw, a plain resize) -> out_hw window at origin."""
+    rh, rw = (int(v) for v in (out_hw if resized_hw is None else resized_hw))
+    top, left = (int(v) for v in origin)
+    return Resize(rh, rw, top, left)
+
+
+def preprocess_resize_u8(ctx: Context, x, out_hw, resized_hw=None, origin=(0, 0), scale=None, shift=None,
+                         reverse_channels: bool = False):
+    """ore_preprocess_resize_u8 (extension): uint8 [n, Hs, Ws, C] -> float32 [n, C, H, W] = out_hw: the images
+    bilinearly resized to resized_hw (None: out_hw), of which the window at `origin` is kept, then normalised
+    as preprocess_u8 does, in one launch."""
+    torch = _torch()
+    _check_u8(x, ctx.device)
+    n, hs, ws, c = (int(d) for d in x.shape)
+    if not 1 <= c <= 4:
+        raise OreError(1, f"x: {c} channels (1..4 supported)")
+    h, w = (int(v) for v in out_hw)
+    if h < 1 or w < 1:
+        raise OreError(1, f"out_hw: {(h, w)}")
+    g = _resize_arg((hs, ws), (h, w), resized_hw, origin)
+    y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    flags = PRE_REVERSE_CHANNELS if reverse_channels else 0
+    check(load().ore_preprocess_resize_u8(ctx.h, ctypes.c_void_p(x.data_ptr()), n, hs, ws, c, ctypes.byref(g),
+                                          _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift"), flags,
+                                          ctypes.byref(_desc(y))), ctx.h)
+    return y
+
+
 def topk(ctx: Context, x, k: int):
     """ore_topk_f32 (extension): the k best elements of every row of x [rows, ...] (the row is the flattened
     rest), as (values float32 [rows, k], indices int32 [rows, k]).  Larger first, equal values by lower index,
@@ -319,6 +379,7 @@ class Model:
         check(load().ore_model_output_elems(self.h, ctypes.byref(e)), ctx.h)
         self.output_elems = e.value
         self.topk = 1  # k of the classify entries (set_topk)
+        self.input_src_hw = None  # (Hs, Ws) the _u8 entries take after set_input_resize; None: the model's (H, W)
 
     def set_fusion(self, flags: int):
         check(load().ore_model_set_fusion(self.h, int(flags)), self.ctx.h)
@@ -362,6 +423,31 @@ class Model:
         sc, sh = _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift")
         check(load().ore_model_set_input_norm(self.h, sc, sh, c, flags), self.ctx.h)
 
+    def set_input_resize(self, src_hw, resized_hw=None, origin=(0, 0)):
+        """ore_model_set_input_resize: from now on run_u8 / classify_u8 / capture_u8 / capture_classify_u8 take
+        uint8 [n, Hs, Ws, C] batches with (Hs, Ws) = src_hw, resized to resized_hw (None: the model's H x W) and
+        cropped to the model's H x W at `origin` on the device (see preprocess_resize_u8), with the
+        normalisation of set_input_norm.  src_hw None: back to [n, H, W, C]."""
+        if src_hw is None:
+            check(load().ore_model_set_input_resize(self.h, 0, 0, None), self.ctx.h)
+            self.input_src_hw = None
+            return
+        hs, ws = (int(v) for v in src_hw)
+        g = _resize_arg((hs, ws), self.input_dims[1:], resized_hw, origin)
+        check(load().ore_model_set_input_resize(self.h, hs, ws, ctypes.byref(g)), self.ctx.h)
+        self.input_src_hw = (hs, ws)
+
+    def _check_u8_dims(self, x):
+        """x [n, Hs, Ws, C] against the model's C and the size the _u8 entries take: the model's (H, W), or the
+        source size of set_input_resize; returns n."""
+        n, h, w, c = (int(d) for d in x.shape)
+        src = getattr(self, "input_src_hw", None)
+        want = (int(self.input_dims[0]),) + (tuple(self.input_dims[1:]) if src is None else tuple(src))
+        if (c, h, w) != want:
+            what = "model (C, H, W)" if src is None else "(C,) + the source size of set_input_resize"
+            raise OreError(1, f"input dims (H, W, C) = {(h, w, c)} != {what} = {want}")
+        return n
+
     def _check_io_u8(self, x, out):
         """As _check_io for a uint8 input: x [n, H, W, C] matching the model's (C, H, W), n <= max_batch."""
         torch = _torch()
@@ -372,9 +458,7 @@ class Model:
             raise OreError(1, f"out: on cuda:{out.device.index}, the context is on cuda:{self.ctx.device}")
         if not out.is_contiguous():
             raise OreError(1, "out: expected a contiguous tensor")
-        n, h, w, c = (int(d) for d in x.shape)
-        if (c, h, w) != tuple(self.input_dims):
-            raise OreError(1, f"input dims (H, W, C) = {(h, w, c)} != model (C, H, W) = {self.input_dims}")
+        n = self._check_u8_dims(x)
         if n > self.max_batch:
             raise OreError(1, f"batch {n} exceeds max_batch {self.max_batch}")
         if out.numel() < n * self.output_elems:
@@ -418,9 +502,7 @@ class Model:
         torch = _torch()
         if u8:
             _check_u8(x, self.ctx.device)
-            n, h, w, c = (int(d) for d in x.shape)
-            if (c, h, w) != tuple(self.input_dims):
-                raise OreError(1, f"input dims (H, W, C) = {(h, w, c)} != model (C, H, W) = {self.input_dims}")
+            n = self._check_u8_dims(x)
         else:
             if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
                 raise OreError(1, "x: expected a float32 CUDA tensor")
