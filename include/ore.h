@@ -198,7 +198,7 @@ ore_status ore_preprocess_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t 
  *    alignment); H, W are y->dims[2], y->dims[3].  One launch, one thread per output pixel.  The pointers and
  *    the geometry are checked first and the context last, all before any device call (ORE_ERR_INVALID);
  *    n == 0 is ORE_OK and launches nothing.  Every image of a call has the same size; rows are dense (no
- *    row stride). */
+ *    row stride); an image list (below) lifts both. */
 typedef struct ore_resize {
   int64_t rh, rw, top, left;
 } ore_resize;
@@ -207,6 +207,47 @@ ore_status ore_resize_taps(int64_t src, int64_t resized, int64_t origin, int64_t
 ore_status ore_preprocess_resize_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t hs, int64_t ws, int64_t c,
                                     const ore_resize* g, const float* scale, const float* shift, int32_t flags,
                                     ore_tensor* y);
+/* Image lists (extension, resize_u8_list_kernel in ore_resize.hip): uint8 images of different sizes and row
+ * strides in one launch.  A descriptor names one image -- its pointer, size, row stride and its own geometry
+ * -- and image i of the result is, bit for bit, what ore_preprocess_resize_u8 gives for a dense copy of that
+ * image alone (n = 1, geometry imgs[i].g).  Two descriptors may name the same or overlapping bytes (two
+ * regions of interest of one frame).
+ *  ore_image_check: host only, it touches no device (as ore_resize_taps).  Every descriptor, for a c-channel
+ *    h x w output: data non-null; hs, ws, g.rh, g.rw each 1..16384 and the h x w crop at (g.top, g.left)
+ *    inside the resized image; row_stride 0 or >= ws*c; (hs-1)*row_stride + ws*c < 2^31 (offsets inside one
+ *    image stay below 2^31, only image bases are 64-bit).  The first failing descriptor gives ORE_ERR_INVALID,
+ *    a message with its index and the reason, and *bad_index (when non-null).  n == 0 is ORE_OK.  The
+ *    library cannot validate the DEVICE pointers: that data..data + (hs-1)*row_stride + ws*c is readable
+ *    device memory is the caller's to guarantee.
+ *  ore_image_list_create: a list for one context and one output shape (1 <= c <= 4; h, w >= 1): a device table
+ *    of `capacity` packed descriptors and a pinned host mirror, both allocated here.  Nothing is allocated
+ *    later, so every use of the list is legal inside a stream capture -- except ore_image_list_set.
+ *  ore_image_list_set: ore_image_check, then copy into the mirror, upload the table on the context's stream
+ *    and set the count to n.  On a failed check or n > capacity (ORE_ERR_INVALID) the list keeps its previous
+ *    content and count.  The upload is stream-ordered: work submitted earlier that reads the old table
+ *    finishes first, work submitted later sees the new table; imgs may be reused as soon as the call
+ *    returns (a set waits for the previous set's upload before it rewrites the mirror).  n == 0 empties the
+ *    list.  ORE_ERR_INVALID while the context's stream is capturing.
+ *  ore_image_list_destroy: after the work that reads the list has finished (ore_sync), and after any model
+ *    graph captured on it was re-captured or destroyed.
+ *  ore_preprocess_list_u8: scale, shift and flags as for ore_preprocess_u8; y is [count,c,h,w] of the list
+ *    and may be a slice of any alignment (nstride >= c*h*w, the gaps are not written).  The arguments are
+ *    checked first and the context last (l must belong to ctx), all before any device call; count == 0 is
+ *    ORE_OK and launches nothing. */
+typedef struct ore_image_u8 {
+  const uint8_t* data; /* DEVICE pointer to row 0, column 0, channel 0; any alignment */
+  int64_t hs, ws;      /* source size, each 1..16384 */
+  int64_t row_stride;  /* bytes from a row to the next, >= ws*c; 0 means dense (ws*c) */
+  ore_resize g;        /* this image's own {rh, rw, top, left}, as for ore_preprocess_resize_u8 */
+} ore_image_u8;        /* 64 bytes */
+typedef struct ore_image_list ore_image_list;
+ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int64_t* bad_index);
+ore_status ore_image_list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, ore_image_list** out);
+ore_status ore_image_list_destroy(ore_image_list* l);
+ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n);
+int64_t ore_image_list_count(ore_image_list* l);
+ore_status ore_preprocess_list_u8(ore_ctx* ctx, ore_image_list* l, const float* scale, const float* shift, int32_t flags,
+                                  ore_tensor* y);
 /* Row-wise top-k (extension; no reference counterpart -- the reference prints the full output tensor): the
  * k best elements of every row of x, in one launch (ore_topk.hip).  Rows are x->dims[0], the row length D
  * the product of the remaining dims (as for ore_softmax_f32); x->nstride >= D is honoured.  values and
@@ -423,6 +464,22 @@ ore_status ore_model_graph_capture_classify(ore_model* m, const float* d_input, 
                                             int32_t* d_classes);
 ore_status ore_model_graph_capture_classify_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_scores,
                                                int32_t* d_classes);
+/* Image-list input (extension, see ore_image_list_create): the _u8_list entries are the _u8 entries with an
+ * image list as the input; n is the list's count at the call (<= max_batch).  The list's (c, h, w) must equal
+ * the model's input dims and its context the model's (ORE_ERR_INVALID).  Scale, shift and flags are those of
+ * ore_model_set_input_norm; ore_model_set_input_resize is ignored by these entries and not changed by them
+ * (it governs the pointer entries only).  Chunks as ore_model_run_u8: chunk i0 converts descriptors
+ * [i0, i0 + nc) into the staging buffer, in front of the pass's first timing event; the conversion is not an
+ * exec step.  The staging and rows buffers are allocated where the _u8 entries allocate them, never inside
+ * a stream capture.
+ *  ore_model_graph_capture_u8_list / _classify_u8_list: the graph keeps the list and the count it was
+ *    captured with, and ore_model_graph_launch converts whatever the table holds at replay time:
+ *    ore_image_list_set with the same count followed by a launch runs new images of new sizes.  With another
+ *    count ore_model_graph_launch answers ORE_ERR_INVALID.  The list must outlive the graph. */
+ore_status ore_model_run_u8_list(ore_model* m, ore_image_list* l, float* d_output);
+ore_status ore_model_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes);
+ore_status ore_model_graph_capture_u8_list(ore_model* m, ore_image_list* l, float* d_output);
+ore_status ore_model_graph_capture_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);
 int32_t ore_model_step_count(ore_model* m);
 ore_status ore_model_step_info(ore_model* m, int32_t i, const char** op, const char** name, double* flops,

@@ -26,6 +26,17 @@ struct ore_ctx {
   int pool_variant = 0;  // ore_ctx_set_pool_variant: a forced MaxPool kernel (0: by layout)
 };
 
+// ore_image_list: a device table of `capacity` packed descriptors for one output shape and its pinned host
+// mirror, both allocated at creation; table[0, count) is what ore_image_list_set uploaded last
+struct ore_image_list {
+  ore_ctx* ctx = nullptr;
+  int64_t capacity = 0, count = 0;
+  int64_t c = 0, h = 0, w = 0;
+  ore::ResizeImage* table = nullptr;   // device
+  ore::ResizeImage* mirror = nullptr;  // pinned host: the source of the stream-ordered upload
+  hipEvent_t uploaded = nullptr;       // recorded after each upload; the next set waits on it before it rewrites the mirror
+};
+
 namespace ore {
 
 // ---------------------------------------------------------------- errors
@@ -202,5 +213,10 @@ ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const f
 // that the crop lies inside the resized image
 ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
                          const float* scale, const float* shift, int32_t flags, ResizeParams* p);
+// as preproc_params for the conversion of an image list (ore_preprocess_list_u8 and the model's _u8_list
+// entries): the list's output shape and table with the caller's normalisation; first 0, N the list's count.
+// y and y_nstride are the caller's to set.
+ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale, const float* shift, int32_t flags,
+                       ResizeListParams* p);
 
 }  // namespace ore

@@ -460,6 +460,26 @@ struct ResizeParams {
   float scale[4], shift[4];
 };
 void launch_resize_u8(const ResizeParams& p, hipStream_t s);
+// the same conversion over an image list (ore_image_list, resize_u8_list_kernel): every image has its own
+// base, size, row stride and geometry, packed by ore_image_list_set into a device table of these
+struct ResizeImage {
+  const unsigned char* x;  // row 0, column 0, channel 0; any alignment
+  int Hs, Ws;              // <= RESIZE_MAX
+  int row;                 // bytes between rows, >= Ws * C; (Hs - 1) * row + Ws * C < 2^31
+  int Rh, Rw, top, left;
+  int pad_;                // 40 bytes: an 8-byte multiple, so the pointers of a table stay aligned
+};
+struct ResizeListParams {
+  const ResizeImage* table;  // image i of the launch is table[first + i]
+  long long first;
+  float* y;                  // [N][C][H][W] at an image stride of y_nstride elements
+  long long N;
+  long long y_nstride;
+  int C, H, W;
+  int plane[4];
+  float scale[4], shift[4];
+};
+void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s);
 // row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,

@@ -908,15 +908,21 @@ static ore_status check_classify_args(ore_model* m, const void* d_input, int64_t
 // run_batch.  With d_u8 the input is the uint8 NHWC batch: each chunk is converted into the staging buffer
 // (ensure_stage), then run.  With d_classes each chunk's output stays on the model's side (the rows buffer of
 // ensure_rows, or the arena where the output value lives there) and its m->topk best per image go to rows
-// [i0, i0 + nc) of d_output (the scores) and d_classes, both [n, topk].
+// [i0, i0 + nc) of d_output (the scores) and d_classes, both [n, topk].  With lst the input is an image list
+// of n descriptors (check_list_args): chunk i0 converts descriptors [i0, i0 + nc) into the staging buffer.
 static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output,
-                             int32_t* d_classes = nullptr) {
+                             int32_t* d_classes = nullptr, ore_image_list* lst = nullptr) {
   ore_ctx* ctx = m->ctx;
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const Value& iv = m->values[m->input_value];
   PreprocParams pre;
   ResizeParams rsz;  // instead of pre after ore_model_set_input_resize
-  if (d_u8 && m->in_resized) {
+  ResizeListParams lsp;  // an image list: its own geometries, whatever ore_model_set_input_resize holds
+  if (lst) {
+    if (ore_status st = list_params(ctx, lst, m->in_scale, m->in_shift, m->in_flags, &lsp)) return st;
+    lsp.y = m->stage;
+    lsp.y_nstride = iv.per_image();
+  } else if (d_u8 && m->in_resized) {
     if (ore_status st = resize_params(ctx, m->in_hs, m->in_ws, iv.dims[1], iv.dims[2], iv.dims[3], &m->in_resize, m->in_scale,
                                       m->in_shift, m->in_flags, &rsz))
       return st;
@@ -953,7 +959,12 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
   for (int64_t c = 0, i0 = 0; c < nchunks; ++c, i0 += chunk) {
     const int64_t nc = std::min(chunk, n - i0);
     const float* x = d_input ? d_input + i0 * in_img : m->stage;
-    if (d_u8) {  // before the pass's first timing event: ore_model_step_times does not include it
+    if (lst) {  // as the uint8 batch below: in front of the pass's first timing event
+      lsp.first = i0;
+      lsp.N = nc;
+      launch_resize_u8_list(lsp, ctx->stream);
+      ORE_HIP_CHECK(ctx, hipGetLastError());
+    } else if (d_u8) {  // before the pass's first timing event: ore_model_step_times does not include it
       if (m->in_resized) {  // the source images have their own size
         rsz.x = d_u8 + i0 * m->in_hs * m->in_ws * iv.dims[1];
         rsz.N = nc;
@@ -1046,6 +1057,33 @@ ore_status ore_model_classify_u8(ore_model* m, const uint8_t* d_input, int64_t n
   if (ore_status st = ensure_stage(m)) return st;
   if (ore_status st = ensure_rows(m)) return st;
   return run_chunks(m, nullptr, d_input, n, d_scores, d_classes);
+}
+
+// the _u8_list entries' checks: check_run_args with the list as the input and its count as n
+static ore_status check_list_args(ore_model* m, ore_image_list* l, float* d_output) {
+  if (ore_status st = check_run_args(m, l, l ? l->count : 0, d_output)) return st;
+  const Value& iv = m->values[m->input_value];
+  if (l->ctx != m->ctx) return set_error(m->ctx, ORE_ERR_INVALID, "the image list belongs to another context than the model");
+  if (l->c != iv.dims[1] || l->h != iv.dims[2] || l->w != iv.dims[3])
+    return set_error(m->ctx, ORE_ERR_INVALID, "the image list produces %lld x %lld x %lld, the model input is %lld x %lld x %lld",
+                     (long long)l->c, (long long)l->h, (long long)l->w, (long long)iv.dims[1], (long long)iv.dims[2], (long long)iv.dims[3]);
+  return ORE_OK;
+}
+
+ore_status ore_model_run_u8_list(ore_model* m, ore_image_list* l, float* d_output) {
+  if (ore_status st = check_list_args(m, l, d_output)) return st;
+  if (l->count == 0) return ORE_OK;
+  if (ore_status st = ensure_stage(m)) return st;
+  return run_chunks(m, nullptr, nullptr, l->count, d_output, nullptr, l);
+}
+
+ore_status ore_model_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes) {
+  if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+  if (ore_status st = check_list_args(m, l, d_scores)) return st;
+  if (l->count == 0) return ORE_OK;
+  if (ore_status st = ensure_stage(m)) return st;
+  if (ore_status st = ensure_rows(m)) return st;
+  return run_chunks(m, nullptr, nullptr, l->count, d_scores, d_classes, l);
 }
 
 ore_status ore_model_read_value(ore_model* m, const char* name, float* host_dst, size_t cap, int64_t dims[4],
@@ -1221,24 +1259,25 @@ ore_status ore_model_set_streams(ore_model* m, int32_t streams) {
 
 // the graph capture entries: one run_chunks(d_input, d_u8, n, d_output, d_classes) as a HIP graph
 static ore_status capture_run(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output,
-                              int32_t* d_classes = nullptr) {
+                              int32_t* d_classes = nullptr, ore_image_list* lst = nullptr) {
   ore_ctx* ctx = m->ctx;
   if (m->timing) return set_error(ctx, ORE_ERR_INVALID, "disable step timing before capturing a graph");
   if (!ctx->stream) return set_error(ctx, ORE_ERR_INVALID, "graph capture needs a non-null context stream");
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (m->graph_exec) { (void)hipGraphExecDestroy(m->graph_exec); m->graph_exec = nullptr; }
   if (m->graph) { (void)hipGraphDestroy(m->graph); m->graph = nullptr; }
+  m->graph_list = nullptr;
   if (m->streams > 1 && !m->side) {  // created outside the capture
     ORE_HIP_CHECK(ctx, hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking));
     ORE_HIP_CHECK(ctx, hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
     ORE_HIP_CHECK(ctx, hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
   }
-  if (d_u8)  // allocated outside the capture
+  if (d_u8 || lst)  // allocated outside the capture
     if (ore_status st = ensure_stage(m)) return st;
   if (d_classes)
     if (ore_status st = ensure_rows(m)) return st;
   ORE_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  ore_status st = run_chunks(m, d_input, d_u8, n, d_output, d_classes);
+  ore_status st = run_chunks(m, d_input, d_u8, n, d_output, d_classes, lst);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
   if (st) {
@@ -1248,6 +1287,8 @@ static ore_status capture_run(ore_model* m, const float* d_input, const uint8_t*
   if (e != hipSuccess) return set_error(ctx, ORE_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
   m->graph = g;
   ORE_HIP_CHECK(ctx, hipGraphInstantiate(&m->graph_exec, m->graph, nullptr, nullptr, 0));
+  m->graph_list = lst;  // the graph reads lst's table at replay: descriptors [0, n)
+  m->graph_list_count = n;
   return ORE_OK;
 }
 
@@ -1273,9 +1314,23 @@ ore_status ore_model_graph_capture_classify_u8(ore_model* m, const uint8_t* d_in
   return capture_run(m, nullptr, d_input, n, d_scores, d_classes);
 }
 
+ore_status ore_model_graph_capture_u8_list(ore_model* m, ore_image_list* l, float* d_output) {
+  if (ore_status st = check_list_args(m, l, d_output)) return st;
+  return capture_run(m, nullptr, nullptr, l->count, d_output, nullptr, l);
+}
+
+ore_status ore_model_graph_capture_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes) {
+  if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+  if (ore_status st = check_list_args(m, l, d_scores)) return st;
+  return capture_run(m, nullptr, nullptr, l->count, d_scores, d_classes, l);
+}
+
 ore_status ore_model_graph_launch(ore_model* m) {
   if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
   if (!m->graph_exec) return set_error(m->ctx, ORE_ERR_INVALID, "no captured graph (ore_model_graph_capture)");
+  if (m->graph_list && m->graph_list->count != m->graph_list_count)
+    return set_error(m->ctx, ORE_ERR_INVALID, "the graph was captured on a list of %lld images, the list now holds %lld",
+                     (long long)m->graph_list_count, (long long)m->graph_list->count);
   ORE_HIP_CHECK(m->ctx, hipGraphLaunch(m->graph_exec, m->ctx->stream));
   return ORE_OK;
 }

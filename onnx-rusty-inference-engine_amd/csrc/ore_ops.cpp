@@ -135,6 +135,16 @@ ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const f
   return ORE_OK;
 }
 
+// the plane map, scale and shift preproc_params resolved, for the resizing conversions' parameter structs
+template <class P>
+static void copy_norm(const PreprocParams& q, P* p) {
+  for (int s = 0; s < q.C; ++s) {
+    p->plane[s] = q.plane[s];
+    p->scale[s] = q.scale[s];
+    p->shift[s] = q.shift[s];
+  }
+}
+
 ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
                          const float* scale, const float* shift, int32_t flags, ResizeParams* p) {
   if (!g) return set_error(ctx, ORE_ERR_INVALID, "null resize geometry");
@@ -150,11 +160,19 @@ ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_
   p->Hs = int(hs); p->Ws = int(ws); p->C = int(c);
   p->Rh = int(g->rh); p->Rw = int(g->rw); p->top = int(g->top); p->left = int(g->left);
   p->H = int(h); p->W = int(w);
-  for (int s = 0; s < int(c); ++s) {
-    p->plane[s] = q.plane[s];
-    p->scale[s] = q.scale[s];
-    p->shift[s] = q.shift[s];
-  }
+  copy_norm(q, p);
+  return ORE_OK;
+}
+
+ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale, const float* shift, int32_t flags,
+                       ResizeListParams* p) {
+  PreprocParams q;
+  if (ore_status st = preproc_params(ctx, l->h, l->w, l->c, scale, shift, flags, &q)) return st;
+  *p = ResizeListParams{};
+  p->table = l->table;
+  p->N = l->count;
+  p->C = int(l->c); p->H = int(l->h); p->W = int(l->w);
+  copy_norm(q, p);
   return ORE_OK;
 }
 
@@ -896,6 +914,133 @@ ore_status ore_preprocess_resize_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, i
   p.y_nstride = nstride_of(y);
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   launch_resize_u8(p, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int64_t* bad_index) {
+  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
+  PreprocParams q;  // c and the output size: the direct conversion's checks
+  if (ore_status st = preproc_params(nullptr, h, w, c, nullptr, nullptr, 0, &q)) return st;
+  if (n == 0) return ORE_OK;
+  if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  for (int64_t i = 0; i < n; ++i) {
+    const ore_image_u8& d = imgs[i];
+    const ore_resize& g = d.g;
+    const long long hs = d.hs, ws = d.ws, rs = d.row_stride;
+    ore_status st = ORE_OK;
+    if (!d.data)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null data pointer", (long long)i);
+    else if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
+                     ws, (long long)g.rh, (long long)g.rw, RESIZE_MAX);
+    else if (!resize_axis_ok(hs, g.rh, g.top, h) || !resize_axis_ok(ws, g.rw, g.left, w))
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
+                     (long long)i, (long long)h, (long long)w, (long long)g.top, (long long)g.left, (long long)g.rh, (long long)g.rw);
+    else if (rs != 0 && rs < ws * c)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: row stride %lld below ws*c = %lld", (long long)i, rs, ws * (long long)c);
+    else if (hs > 1 && (!fits_i32(rs) || !fits_i32((hs - 1) * (rs ? rs : ws * c) + ws * c)))  // a one-row image never steps a row
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hs, rs);
+    if (st) {
+      if (bad_index) *bad_index = i;
+      return st;
+    }
+  }
+  return ORE_OK;
+}
+
+ore_status ore_image_list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, ore_image_list** out) {
+  if (!ctx || !out) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  PreprocParams q;
+  if (ore_status st = preproc_params(ctx, h, w, c, nullptr, nullptr, 0, &q)) return st;
+  if (capacity < 1 || !fits_i32(capacity))
+    return set_error(ctx, ORE_ERR_INVALID, "image list capacity %lld (1..2^31-1)", (long long)capacity);
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ore_image_list* l = new ore_image_list();
+  l->ctx = ctx;
+  l->capacity = capacity;
+  l->c = c; l->h = h; l->w = w;
+  const size_t bytes = size_t(capacity) * sizeof(ResizeImage);
+  if (hipMalloc(reinterpret_cast<void**>(&l->table), bytes) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&l->mirror), bytes, hipHostMallocDefault) != hipSuccess ||
+      hipEventCreateWithFlags(&l->uploaded, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)ore_image_list_destroy(l);
+    return set_error(ctx, ORE_ERR_OOM, "image list of %lld descriptors (%zu bytes) allocation failed", (long long)capacity, bytes);
+  }
+  *out = l;
+  return ORE_OK;
+}
+
+ore_status ore_image_list_destroy(ore_image_list* l) {
+  if (!l) return ORE_OK;
+  (void)hipSetDevice(l->ctx->device);
+  if (l->uploaded) {  // a pending upload still reads the mirror; launches that read the table are the caller's to finish
+    (void)hipEventSynchronize(l->uploaded);
+    (void)hipEventDestroy(l->uploaded);
+  }
+  if (l->mirror) (void)hipHostFree(l->mirror);
+  if (l->table) (void)hipFree(l->table);
+  delete l;
+  return ORE_OK;
+}
+
+int64_t ore_image_list_count(ore_image_list* l) { return l ? l->count : 0; }
+
+ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n) {
+  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
+  ore_ctx* ctx = l->ctx;
+  int64_t bad = -1;
+  if (ore_image_check(imgs, n, l->c, l->h, l->w, &bad)) {
+    ctx->err = ore_last_error(nullptr);
+    return ORE_ERR_INVALID;
+  }
+  if (n > l->capacity)
+    return set_error(ctx, ORE_ERR_INVALID, "%lld images exceed the list's capacity %lld", (long long)n, (long long)l->capacity);
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set inside a stream capture: a captured graph reads the table at "
+                                           "replay, set it before or after the capture");
+  if (n == 0) {
+    l->count = 0;
+    return ORE_OK;
+  }
+  ORE_HIP_CHECK(ctx, hipEventSynchronize(l->uploaded));  // the previous upload has read the mirror
+  for (int64_t i = 0; i < n; ++i) {
+    const ore_image_u8& d = imgs[i];
+    ResizeImage& r = l->mirror[i];
+    r = ResizeImage{};
+    r.x = d.data;
+    r.Hs = int(d.hs); r.Ws = int(d.ws);
+    r.row = int(d.hs > 1 && d.row_stride ? d.row_stride : d.ws * l->c);  // dense where 0, and where no row is ever stepped
+    r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
+  }
+  // stream-ordered: launches submitted earlier read the old table, later ones the new
+  ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table, l->mirror, size_t(n) * sizeof(ResizeImage), hipMemcpyHostToDevice, ctx->stream));
+  ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
+  l->count = n;
+  return ORE_OK;
+}
+
+ore_status ore_preprocess_list_u8(ore_ctx* ctx, ore_image_list* l, const float* scale, const float* shift, int32_t flags,
+                                  ore_tensor* y) {
+  // the arguments first and the context last, as ore_preprocess_resize_u8
+  if (!l || !y || !y->data) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (y->ndim != 4 || y->dims[0] != l->count || y->dims[1] != l->c || y->dims[2] != l->h || y->dims[3] != l->w)
+    return set_error(ctx, ORE_ERR_INVALID, "list output must be [count,c,H,W] of the image list (%lld x %lld x %lld x %lld)",
+                     (long long)l->count, (long long)l->c, (long long)l->h, (long long)l->w);
+  ResizeListParams p;
+  if (ore_status st = list_params(ctx, l, scale, shift, flags, &p)) return st;
+  if (nstride_of(y) < l->c * l->h * l->w)
+    return set_error(ctx, ORE_ERR_INVALID, "list output: image stride %lld below c*H*W", (long long)nstride_of(y));
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null context");
+  if (l->ctx != ctx) return set_error(ctx, ORE_ERR_INVALID, "the image list belongs to another context");
+  if (l->count == 0) return ORE_OK;
+  p.y = y->data;
+  p.y_nstride = nstride_of(y);
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_resize_u8_list(p, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

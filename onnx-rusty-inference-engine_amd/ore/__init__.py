@@ -6,8 +6,8 @@ from ._lib import (CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD, FUSE_ALIAS, FUSE_ALL, F
                    FUSE_POOL_SQUEEZE, FUSE_CONV_GAP, FUSE_POOL_EXPAND, KEEP_VALUES, LIB_PATH, LOAD_F16, LOAD_NO_WINOGRAD, OreError,
                    ABI_VERSION, PRE_REVERSE_CHANNELS,
                    load)
-from .engine import (Context, Model, add, center_crop_geometry, concatenation, conv_out_shape, convolution, drop_out,  # noqa: F401
-                     global_average_pool, inference, max_pool, mul, pool_out_shape, preprocess_resize_u8,
+from .engine import (Context, ImageList, Model, add, center_crop_geometry, concatenation, conv_out_shape, convolution, drop_out,  # noqa: F401
+                     global_average_pool, inference, max_pool, mul, pool_out_shape, preprocess_list_u8, preprocess_resize_u8,
                      preprocess_u8, relu, reshape, resize_taps, softmax, topk)
 
 __version__ = "0.1.0"

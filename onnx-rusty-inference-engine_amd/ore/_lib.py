@@ -38,6 +38,9 @@ EXPORTED = [
     "ore_add_f32", "ore_softmax_f32", "ore_matmul_f32", "ore_gap_f32", "ore_concat_f32", "ore_dropout_f32",
     "ore_reshape", "ore_preprocess_u8", "ore_model_set_input_norm", "ore_model_run_u8", "ore_model_graph_capture_u8",
     "ore_resize_taps", "ore_preprocess_resize_u8", "ore_model_set_input_resize",
+    "ore_image_check", "ore_image_list_create", "ore_image_list_destroy", "ore_image_list_set", "ore_image_list_count",
+    "ore_preprocess_list_u8", "ore_model_run_u8_list", "ore_model_classify_u8_list", "ore_model_graph_capture_u8_list",
+    "ore_model_graph_capture_classify_u8_list",
     "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
     "ore_model_graph_capture_classify", "ore_model_graph_capture_classify_u8",
     "ore_model_parse", "ore_model_load", "ore_model_load_ex", "ore_model_destroy", "ore_model_set_fusion", "ore_model_input_dims",
@@ -62,6 +65,13 @@ class Tensor(ctypes.Structure):
 class Resize(ctypes.Structure):
     """ore_resize: the source image resized to rh x rw, of which the window at (top, left) is produced."""
     _fields_ = [("rh", ctypes.c_int64), ("rw", ctypes.c_int64), ("top", ctypes.c_int64), ("left", ctypes.c_int64)]
+
+
+class ImageU8(ctypes.Structure):
+    """ore_image_u8: one image of an image list: a DEVICE pointer, its size, the bytes from a row to the next
+    (0: dense) and its own geometry."""
+    _fields_ = [("data", ctypes.c_void_p), ("hs", ctypes.c_int64), ("ws", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+                ("g", Resize)]
 
 
 class ConvAttrs(ctypes.Structure):
@@ -124,6 +134,16 @@ def load():
         "ore_resize_taps": (i32, [i64, i64, i64, i64, vp, vp, vp]),
         "ore_preprocess_resize_u8": (i32, [vp, vp, i64, i64, i64, i64, ctypes.POINTER(Resize), F32P, F32P, i32, T]),
         "ore_model_set_input_resize": (i32, [vp, i64, i64, ctypes.POINTER(Resize)]),
+        "ore_image_check": (i32, [ctypes.POINTER(ImageU8), i64, i64, i64, i64, I64P]),
+        "ore_image_list_create": (i32, [vp, i64, i64, i64, i64, ctypes.POINTER(vp)]),
+        "ore_image_list_destroy": (i32, [vp]),
+        "ore_image_list_set": (i32, [vp, ctypes.POINTER(ImageU8), i64]),
+        "ore_image_list_count": (i64, [vp]),
+        "ore_preprocess_list_u8": (i32, [vp, vp, F32P, F32P, i32, T]),
+        "ore_model_run_u8_list": (i32, [vp, vp, vp]),
+        "ore_model_classify_u8_list": (i32, [vp, vp, vp, vp]),
+        "ore_model_graph_capture_u8_list": (i32, [vp, vp, vp]),
+        "ore_model_graph_capture_classify_u8_list": (i32, [vp, vp, vp, vp]),
         "ore_topk_f32": (i32, [vp, T, i32, vp, vp]),
         "ore_model_set_topk": (i32, [vp, i32]),
         "ore_model_classify": (i32, [vp, vp, i64, vp, vp]),

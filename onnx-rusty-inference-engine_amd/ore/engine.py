@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "resize_taps", "center_crop_geometry", "topk", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "preprocess_list_u8", "resize_taps", "center_crop_geometry", "topk", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -329,6 +329,114 @@ def preprocess_resize_u8(ctx: Context, x, out_hw, resized_hw=None, origin=(0, 0)
     return y
 
 
+def _check_image_u8(x, device: int, c: int, name: str):
+    """One image of an image list, handed to the library as a raw device pointer with a row stride: a
+    torch.uint8 CUDA tensor [Hs, Ws, C] on the context's device whose pixels are dense (stride(2) == 1,
+    stride(1) == C) and whose rows do not overlap (stride(0) >= Ws * C); a sliced view qualifies."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.uint8:
+        raise OreError(1, f"{name}: expected a uint8 CUDA tensor")
+    if x.device.index != device:
+        raise OreError(1, f"{name}: on cuda:{x.device.index}, the context is on cuda:{device}")
+    if x.dim() != 3:
+        raise OreError(1, f"{name}: expected [Hs, Ws, C], got {tuple(x.shape)}")
+    hs, ws, cc = (int(d) for d in x.shape)
+    if cc != c:
+        raise OreError(1, f"{name}: {cc} channels, the list takes {c}")
+    if hs < 1 or ws < 1:
+        raise OreError(1, f"{name}: empty image {tuple(x.shape)}")
+    if x.stride(2) != 1 or x.stride(1) != c or x.stride(0) < ws * c:
+        raise OreError(1, f"{name}: strides {tuple(x.stride())}: expected dense pixels (C, 1) and a row stride >= Ws * C")
+
+
+class ImageList:
+    """ore_image_list: up to `capacity` uint8 images of their own sizes and row strides, each resized and
+    cropped to out_hw by its own geometry in ONE launch (preprocess_list_u8, Model.run_u8_list, ...).  The
+    device table and its pinned mirror are allocated here; set() only fills and uploads them."""
+
+    def __init__(self, ctx: Context, capacity: int, out_hw, channels: int = 3):
+        h, w = (int(v) for v in out_hw)
+        self.ctx = ctx
+        self.capacity = int(capacity)
+        self.out_hw = (h, w)
+        self.channels = int(channels)
+        self._images = ()
+        self.h = None
+        hnd = ctypes.c_void_p()
+        check(load().ore_image_list_create(ctx.h, self.capacity, self.channels, h, w, ctypes.byref(hnd)), ctx.h)
+        self.h = hnd
+
+    def _descriptors(self, images, geometries, short):
+        """The host checks of set(): the ore_image_u8 array of `images`, before any library call."""
+        if geometries is not None and short is not None:
+            raise OreError(1, "set: pass geometries or short, not both")
+        images = list(images)
+        if len(images) > self.capacity:
+            raise OreError(1, f"set: {len(images)} images exceed the list's capacity {self.capacity}")
+        if geometries is not None and len(geometries) != len(images):
+            raise OreError(1, f"set: {len(geometries)} geometries for {len(images)} images")
+        arr = (_lib.ImageU8 * max(len(images), 1))()
+        for i, x in enumerate(images):
+            _check_image_u8(x, self.ctx.device, self.channels, f"images[{i}]")
+            hs, ws = int(x.shape[0]), int(x.shape[1])
+            if geometries is not None:
+                resized, origin = geometries[i]
+            elif short is not None:
+                resized, origin = center_crop_geometry((hs, ws), short, self.out_hw)
+            else:
+                resized, origin = None, (0, 0)
+            arr[i].data = x.data_ptr()
+            arr[i].hs, arr[i].ws = hs, ws
+            arr[i].row_stride = int(x.stride(0))
+            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin)
+        return images, arr
+
+    def set(self, images, geometries=None, short=None):
+        """ore_image_list_set: images is a sequence of uint8 CUDA tensors [Hs, Ws, C] (sliced views included:
+        that is where row strides come from).  Geometry per image: geometries[i] = (resized_hw, origin); or
+        short=S for center_crop_geometry(src_hw, S, out_hw); or neither, a plain resize to out_hw.  The upload
+        is ordered on the context's stream; a rejected set leaves the list as it was.  The list keeps
+        references to the tensors."""
+        images, arr = self._descriptors(images, geometries, short)
+        check(load().ore_image_list_set(self.h, arr, len(images)), self.ctx.h)
+        self._images = tuple(images)
+        return self
+
+    @property
+    def count(self) -> int:
+        return int(load().ore_image_list_count(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().ore_image_list_destroy(self.h)
+            self.h = None
+            self._images = ()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def preprocess_list_u8(ctx: Context, lst: ImageList, scale=None, shift=None, reverse_channels: bool = False):
+    """ore_preprocess_list_u8 (extension): the images of `lst` -> float32 [count, C, H, W], image i resized,
+    cropped and normalised exactly as preprocess_resize_u8 would a dense copy of it alone, in one launch."""
+    torch = _torch()
+    if not isinstance(lst, ImageList) or lst.h is None:
+        raise OreError(1, "lst: expected an open ImageList")
+    if lst.ctx is not ctx:
+        raise OreError(1, "lst: the image list belongs to another context")
+    c = lst.channels
+    y = torch.empty((lst.count, c) + lst.out_hw, dtype=torch.float32, device=f"cuda:{ctx.device}")
+    if y.shape[0] == 0:  # nothing to launch (and an empty tensor has no pointer to hand over)
+        return y
+    flags = PRE_REVERSE_CHANNELS if reverse_channels else 0
+    check(load().ore_preprocess_list_u8(ctx.h, lst.h, _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift"), flags,
+                                        ctypes.byref(_desc(y))), ctx.h)
+    return y
+
+
 def topk(ctx: Context, x, k: int):
     """ore_topk_f32 (extension): the k best elements of every row of x [rows, ...] (the row is the flattened
     rest), as (values float32 [rows, k], indices int32 [rows, k]).  Larger first, equal values by lower index,
@@ -448,16 +556,21 @@ class Model:
             raise OreError(1, f"input dims (H, W, C) = {(h, w, c)} != {what} = {want}")
         return n
 
-    def _check_io_u8(self, x, out):
-        """As _check_io for a uint8 input: x [n, H, W, C] matching the model's (C, H, W), n <= max_batch."""
+    def _check_out(self, out):
+        """The output of a _u8 / _u8_list entry, written through a raw device pointer: a contiguous float32
+        CUDA tensor on this context's device."""
         torch = _torch()
-        _check_u8(x, self.ctx.device)
         if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
             raise OreError(1, "out: expected a float32 CUDA tensor")
         if out.device.index != self.ctx.device:
             raise OreError(1, f"out: on cuda:{out.device.index}, the context is on cuda:{self.ctx.device}")
         if not out.is_contiguous():
             raise OreError(1, "out: expected a contiguous tensor")
+
+    def _check_io_u8(self, x, out):
+        """As _check_io for a uint8 input: x [n, H, W, C] matching the model's (C, H, W), n <= max_batch."""
+        _check_u8(x, self.ctx.device)
+        self._check_out(out)
         n = self._check_u8_dims(x)
         if n > self.max_batch:
             raise OreError(1, f"batch {n} exceeds max_batch {self.max_batch}")
@@ -571,6 +684,78 @@ class Model:
         included (see capture_u8)."""
         self._graph_bufs = (x, scores, classes)
         return self._classify(load().ore_model_graph_capture_classify_u8, x, scores, classes, True)
+
+    # ---- image-list input (ore_model_*_u8_list): the _u8 entries with an ImageList as the input
+    def _check_list(self, lst):
+        """An open ImageList of this model's context and input dims, holding at most max_batch images; returns
+        its count."""
+        if not isinstance(lst, ImageList) or lst.h is None:
+            raise OreError(1, "lst: expected an open ImageList")
+        if lst.ctx is not self.ctx:
+            raise OreError(1, "lst: the image list belongs to another context than the model")
+        if (lst.channels,) + tuple(lst.out_hw) != tuple(self.input_dims):
+            raise OreError(1, f"lst: the list produces (C, H, W) = {(lst.channels,) + tuple(lst.out_hw)}, the model "
+                              f"input is {tuple(self.input_dims)}")
+        n = lst.count
+        if n > self.max_batch:
+            raise OreError(1, f"batch {n} exceeds max_batch {self.max_batch}")
+        return n
+
+    def _check_list_out(self, n: int, out):
+        self._check_out(out)
+        if out.numel() < n * self.output_elems:
+            raise OreError(1, f"out holds {out.numel()} floats, {n} images need {n * self.output_elems}")
+
+    def run_u8_list_into(self, lst, out):
+        """ore_model_run_u8_list: run_u8_into on the images of an ImageList, each resized and cropped by its own
+        geometry (set_input_resize does not apply) with the normalisation of set_input_norm."""
+        n = self._check_list(lst)
+        self._check_list_out(n, out)
+        check(load().ore_model_run_u8_list(self.h, lst.h, ctypes.c_void_p(out.data_ptr())), self.ctx.h)
+        return out
+
+    def run_u8_list(self, lst):
+        torch = _torch()
+        n = self._check_list(lst)
+        out = torch.empty((n, self.output_elems), dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        if n == 0:
+            return out
+        return self.run_u8_list_into(lst, out)
+
+    def _classify_list(self, entry, lst, scores, classes):
+        n = self._check_list(lst)
+        self._check_classify_out(n, scores, classes)
+        check(entry(self.h, lst.h, ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(classes.data_ptr())), self.ctx.h)
+        return scores, classes
+
+    def classify_u8_list_into(self, lst, scores, classes):
+        """ore_model_classify_u8_list: classify_u8_into on the images of an ImageList."""
+        return self._classify_list(load().ore_model_classify_u8_list, lst, scores, classes)
+
+    def classify_u8_list(self, lst):
+        torch = _torch()
+        n = self._check_list(lst)
+        dev = f"cuda:{self.ctx.device}"
+        scores = torch.empty((n, self.topk), dtype=torch.float32, device=dev)
+        classes = torch.empty((n, self.topk), dtype=torch.int32, device=dev)
+        if n == 0:
+            return scores, classes
+        return self.classify_u8_list_into(lst, scores, classes)
+
+    def capture_u8_list(self, lst, out):
+        """ore_model_graph_capture_u8_list: capture run_u8_list_into(lst, out) as a HIP graph.  replay()
+        converts whatever the list's table holds then: lst.set(...) with the same count, then replay(), runs
+        new images of new sizes; with another count replay() raises.  The list must outlive the graph."""
+        n = self._check_list(lst)
+        self._check_list_out(n, out)
+        self._graph_bufs = (lst, out)  # the graph holds the table's and out's pointers
+        check(load().ore_model_graph_capture_u8_list(self.h, lst.h, ctypes.c_void_p(out.data_ptr())), self.ctx.h)
+        return out
+
+    def capture_classify_u8_list(self, lst, scores, classes):
+        """ore_model_graph_capture_classify_u8_list: as capture_u8_list with the selection inside the graph."""
+        self._graph_bufs = (lst, scores, classes)
+        return self._classify_list(load().ore_model_graph_capture_classify_u8_list, lst, scores, classes)
 
     def read_value(self, name: str) -> np.ndarray:
         dims = (ctypes.c_int64 * 4)()
