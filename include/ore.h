@@ -118,9 +118,15 @@ ore_status ore_ctx_set_conv_algo(ore_ctx* ctx, int32_t algo);
  *    persistent streaming 1x1); the retired ids 4-11 and 28-35 return ORE_ERR_UNSUPPORTED.
  *  ore_ctx_set_pool_variant: MaxPool kernel of ore_maxpool2d_f32 and of the walker's MaxPool steps:
  *    0 (default) = by layout, 2 one thread per output, 3 column strips, 4 plane-staged, 5
- *    chunk-staged (1 is retired: ORE_ERR_UNSUPPORTED). */
+ *    chunk-staged (1 is retired: ORE_ERR_UNSUPPORTED).
+ *  ore_ctx_set_resize_variant: kernel of the antialiased resize (ORE_FILTER_BILINEAR_AA) in every entry that
+ *    runs it on this context afterwards, captures included: 0 (default) = by geometry, 1 one thread per
+ *    output pixel.  That is the only kernel today (the band kernel that was variant 2 lost to it and was
+ *    removed), so both select it; anything else is ORE_ERR_INVALID.  The two bilinear
+ *    kernels are not affected. */
 ore_status ore_ctx_set_conv_tile(ore_ctx* ctx, int32_t tile);
 ore_status ore_ctx_set_pool_variant(ore_ctx* ctx, int32_t variant);
+ore_status ore_ctx_set_resize_variant(ore_ctx* ctx, int32_t variant);
 
 ore_status ore_malloc(ore_ctx* ctx, size_t bytes, void** dptr);
 ore_status ore_free(ore_ctx* ctx, void* dptr);
@@ -248,6 +254,50 @@ ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64
 int64_t ore_image_list_count(ore_image_list* l);
 ore_status ore_preprocess_list_u8(ore_ctx* ctx, ore_image_list* l, const float* scale, const float* shift, int32_t flags,
                                   ore_tensor* y);
+/* Antialiased resize (extension, the resize_aa_* kernels in ore_resize.hip): the filter of torchvision's Resize
+ * on tensors with antialias=True, of F.interpolate(mode="bilinear", antialias=True) and, up to its rounding to
+ * bytes, of PIL's BILINEAR.  The geometry is the same ore_resize; the filter is chosen per axis.  An axis with
+ * S <= D (it does not shrink) is computed exactly as above (i0, i1, t and the lerp).  An axis with S > D takes
+ * the triangle filter stretched by S / D, in integers: for resized index o, with c = (2 o + 1) S,
+ *     taps: every source index j of [0, S - 1] with |(2 j + 1) D - c| < 2 S   (a contiguous, never empty run)
+ *     u_j = 2 S - |(2 j + 1) D - c|;   U = the sum of u_j over the taps        (so the edges renormalise)
+ * and S <= 32 D is required of every shrinking axis (ORE_AA_MAX_RATIO; ORE_ERR_INVALID with a message naming
+ * the axis otherwise): a run is then at most 64 taps (ORE_AA_MAX_TAPS), u_j < 2^15, U <= 2^21 and the sum of
+ * u_j * byte < 2^29, and the work of one output pixel is bounded.  Per output element of source channel cs,
+ * with v_r, V the row weights and sum, u_j, U the column ones:
+ *   1. per tap row r:  columns shrink: g_r = (float)(sum_j u_j x[r,j,cs])   (exact integer sum, one rounding)
+ *                      else:           g_r = lerp(x[r,x0,cs], x[r,x1,cs], tx)
+ *   2. rows shrink:    acc = +0; for r ascending: acc = fadd_rn(acc, fmul_rn((float)v_r, g_r));
+ *                      w = fdiv_rn(acc, (float)V)
+ *      else:           w = lerp(g_y0, g_y1, ty)
+ *   3. columns shrink: w = fdiv_rn(w, (float)U)
+ *   4. y = fadd_rn(fmul_rn(w, scale[ch]), shift[ch])
+ * Every float operation rounds on its own (no FMA, IEEE division), so numpy float32 arrays reproduce it bit
+ * for bit; where neither axis shrinks it is the ORE_FILTER_BILINEAR result bit for bit.
+ *  ore_resize_aa_taps: one shrinking axis's table into HOST arrays (host only, as ore_resize_taps): first tap,
+ *    tap count and weight sum of the `count` resized indices from `origin`; weights, when non-null, is
+ *    [count][ORE_AA_MAX_TAPS], zero-padded.  ORE_ERR_INVALID when src <= resized (the axis does not shrink:
+ *    ore_resize_taps is its table) and when src > 32 resized.
+ *  ore_preprocess_resize_u8_ex: ore_preprocess_resize_u8 with the filter; the same order of checks (arguments
+ *    and geometry, the ratio rule included, then the context, all before any device call); an unknown filter
+ *    is ORE_ERR_INVALID.  ORE_FILTER_BILINEAR is ore_preprocess_resize_u8 itself.
+ *  ore_image_check_ex: ore_image_check plus, under ORE_FILTER_BILINEAR_AA, the ratio rule per descriptor.
+ *  ore_image_list_create_ex: the filter is a property of the list, fixed at creation like its output shape
+ *    (ore_image_list_filter reads it; ore_image_list_create makes a bilinear list).  ore_image_list_set checks
+ *    with it, and ore_preprocess_list_u8 and the model's _u8_list entries run it. */
+typedef enum { ORE_FILTER_BILINEAR = 0, ORE_FILTER_BILINEAR_AA = 1 } ore_resize_filter;
+#define ORE_AA_MAX_RATIO 32
+#define ORE_AA_MAX_TAPS 64
+ore_status ore_resize_aa_taps(int64_t src, int64_t resized, int64_t origin, int64_t count, int32_t* first,
+                              int32_t* ntaps, int32_t* sum, int32_t* weights);
+ore_status ore_preprocess_resize_u8_ex(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t hs, int64_t ws, int64_t c,
+                                       const ore_resize* g, int32_t filter, const float* scale, const float* shift,
+                                       int32_t flags, ore_tensor* y);
+ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int32_t filter,
+                              int64_t* bad_index);
+ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter,
+                                    ore_image_list** out);
+int32_t ore_image_list_filter(ore_image_list* l);
 /* Row-wise top-k (extension; no reference counterpart -- the reference prints the full output tensor): the
  * k best elements of every row of x, in one launch (ore_topk.hip).  Rows are x->dims[0], the row length D
  * the product of the remaining dims (as for ore_softmax_f32); x->nstride >= D is honoured.  values and
@@ -436,9 +486,13 @@ ore_status ore_model_graph_launch(ore_model* m);
  *    ore_preprocess_resize_u8; checked here, ORE_ERR_INVALID) in the launch that converts; g == NULL
  *    restores the direct conversion of [n,H,W,C].  scale, shift and flags stay those of
  *    ore_model_set_input_norm; the staging buffer, the chunks (chunk i0 reads from image i0 of d_input) and
- *    the step list are unchanged, and a captured graph keeps the geometry it was captured with. */
+ *    the step list are unchanged, and a captured graph keeps the geometry it was captured with.
+ *  ore_model_set_input_resize_ex: the same with an ore_resize_filter (ORE_FILTER_BILINEAR_AA: the antialiased
+ *    resize of ore_preprocess_resize_u8_ex, its ratio rule checked here); ore_model_set_input_resize means
+ *    ORE_FILTER_BILINEAR.  A captured graph keeps the filter it was captured with. */
 ore_status ore_model_set_input_norm(ore_model* m, const float* scale, const float* shift, int32_t c, int32_t flags);
 ore_status ore_model_set_input_resize(ore_model* m, int64_t hs, int64_t ws, const ore_resize* g);
+ore_status ore_model_set_input_resize_ex(ore_model* m, int64_t hs, int64_t ws, const ore_resize* g, int32_t filter);
 ore_status ore_model_run_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
 ore_status ore_model_graph_capture_u8(ore_model* m, const uint8_t* d_input, int64_t n, float* d_output);
 /* Top-k output (extension, see ore_topk_f32): the classify entries run the graph as ore_model_run /

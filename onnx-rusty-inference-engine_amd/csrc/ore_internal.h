@@ -24,6 +24,7 @@ struct ore_ctx {
   int conv_algo = 0;     // ore_ctx_set_conv_algo (per-op ore_conv2d_f32 only)
   int conv_tile = -1;    // ore_ctx_set_conv_tile: a forced tile id (-1: per-layer heuristic / autotune)
   int pool_variant = 0;  // ore_ctx_set_pool_variant: a forced MaxPool kernel (0: by layout)
+  int resize_variant = 0;  // ore_ctx_set_resize_variant: 0 by geometry, 1 thread per pixel -- one kernel today, so nothing reads it
 };
 
 // ore_image_list: a device table of `capacity` packed descriptors for one output shape and its pinned host
@@ -32,6 +33,7 @@ struct ore_image_list {
   ore_ctx* ctx = nullptr;
   int64_t capacity = 0, count = 0;
   int64_t c = 0, h = 0, w = 0;
+  int32_t filter = 0;                  // ore_resize_filter, fixed at creation
   ore::ResizeImage* table = nullptr;   // device
   ore::ResizeImage* mirror = nullptr;  // pinned host: the source of the stream-ordered upload
   hipEvent_t uploaded = nullptr;       // recorded after each upload; the next set waits on it before it rewrites the mirror
@@ -212,11 +214,14 @@ ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const f
 // the model's _u8 entries after ore_model_set_input_resize): also checks the sizes against RESIZE_MAX and
 // that the crop lies inside the resized image
 ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
-                         const float* scale, const float* shift, int32_t flags, ResizeParams* p);
+                         const float* scale, const float* shift, int32_t flags, ResizeParams* p,
+                         int32_t filter = ORE_FILTER_BILINEAR);
 // as preproc_params for the conversion of an image list (ore_preprocess_list_u8 and the model's _u8_list
 // entries): the list's output shape and table with the caller's normalisation; first 0, N the list's count.
 // y and y_nstride are the caller's to set.
 ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale, const float* shift, int32_t flags,
                        ResizeListParams* p);
+// the list conversion's launch under the list's filter (ore_preprocess_list_u8 and the model's _u8_list entries)
+void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& p);
 
 }  // namespace ore

@@ -480,6 +480,12 @@ struct ResizeListParams {
   float scale[4], shift[4];
 };
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s);
+// the same two conversions under ORE_FILTER_BILINEAR_AA: axes that shrink take the area-weighted filter of
+// ore_resize_geom.h (every such axis within RESIZE_AA_MAX_RATIO, checked by the caller), the others resize_tap.
+// One thread per output pixel (resize_aa_pixel_kernel and its list form); a dense launch in which nothing
+// shrinks goes to launch_resize_u8.
+void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s);
+void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s);
 // row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,

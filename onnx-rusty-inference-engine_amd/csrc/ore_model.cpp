@@ -924,7 +924,7 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
     lsp.y_nstride = iv.per_image();
   } else if (d_u8 && m->in_resized) {
     if (ore_status st = resize_params(ctx, m->in_hs, m->in_ws, iv.dims[1], iv.dims[2], iv.dims[3], &m->in_resize, m->in_scale,
-                                      m->in_shift, m->in_flags, &rsz))
+                                      m->in_shift, m->in_flags, &rsz, m->in_filter))
       return st;
     rsz.y = m->stage;
     rsz.y_nstride = iv.per_image();
@@ -962,13 +962,16 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
     if (lst) {  // as the uint8 batch below: in front of the pass's first timing event
       lsp.first = i0;
       lsp.N = nc;
-      launch_resize_u8_list(lsp, ctx->stream);
+      launch_list(ctx, lst, lsp);
       ORE_HIP_CHECK(ctx, hipGetLastError());
     } else if (d_u8) {  // before the pass's first timing event: ore_model_step_times does not include it
       if (m->in_resized) {  // the source images have their own size
         rsz.x = d_u8 + i0 * m->in_hs * m->in_ws * iv.dims[1];
         rsz.N = nc;
-        launch_resize_u8(rsz, ctx->stream);
+        if (m->in_filter == ORE_FILTER_BILINEAR_AA)
+          launch_resize_aa_u8(rsz, ctx->stream);
+        else
+          launch_resize_u8(rsz, ctx->stream);
       } else {
         pre.x = d_u8 + i0 * in_img;
         pre.N = nc;
@@ -1011,6 +1014,10 @@ ore_status ore_model_set_input_norm(ore_model* m, const float* scale, const floa
 }
 
 ore_status ore_model_set_input_resize(ore_model* m, int64_t hs, int64_t ws, const ore_resize* g) {
+  return ore_model_set_input_resize_ex(m, hs, ws, g, ORE_FILTER_BILINEAR);
+}
+
+ore_status ore_model_set_input_resize_ex(ore_model* m, int64_t hs, int64_t ws, const ore_resize* g, int32_t filter) {
   if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
   if (!g) {  // back to the direct conversion of [n,H,W,C]
     m->in_resized = false;
@@ -1018,11 +1025,13 @@ ore_status ore_model_set_input_resize(ore_model* m, int64_t hs, int64_t ws, cons
   }
   const Value& iv = m->values[m->input_value];
   ResizeParams rsz;
-  if (ore_status st = resize_params(m->ctx, hs, ws, iv.dims[1], iv.dims[2], iv.dims[3], g, m->in_scale, m->in_shift, m->in_flags, &rsz))
+  if (ore_status st = resize_params(m->ctx, hs, ws, iv.dims[1], iv.dims[2], iv.dims[3], g, m->in_scale, m->in_shift, m->in_flags, &rsz,
+                                    filter))
     return st;
   m->in_hs = hs;
   m->in_ws = ws;
   m->in_resize = *g;
+  m->in_filter = filter;
   m->in_resized = true;
   return ORE_OK;
 }

@@ -189,6 +189,7 @@ struct ore_model {
   bool in_resized = false;
   int64_t in_hs = 0, in_ws = 0;
   ore_resize in_resize = {0, 0, 0, 0};
+  int32_t in_filter = 0;  // ore_resize_filter of ore_model_set_input_resize_ex
   // top-k output (ore_model_classify): the f32 rows buffer of run_batch images' outputs the graph writes
   // and the selection reads, and the k of ore_model_set_topk
   float* rows = nullptr;

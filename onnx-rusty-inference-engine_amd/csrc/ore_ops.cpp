@@ -145,9 +145,18 @@ static void copy_norm(const PreprocParams& q, P* p) {
   }
 }
 
+// the axis on which ORE_FILTER_BILINEAR_AA would shrink by more than ORE_AA_MAX_RATIO, or null
+static const char* aa_bad_axis(int64_t hs, int64_t ws, const ore_resize& g) {
+  if (!resize_axis_aa_ok(hs, g.rh)) return "rows";
+  if (!resize_axis_aa_ok(ws, g.rw)) return "columns";
+  return nullptr;
+}
+
 ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
-                         const float* scale, const float* shift, int32_t flags, ResizeParams* p) {
+                         const float* scale, const float* shift, int32_t flags, ResizeParams* p, int32_t filter) {
   if (!g) return set_error(ctx, ORE_ERR_INVALID, "null resize geometry");
+  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+    return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   PreprocParams q;  // c, the flags, the reversal and the output size: the direct conversion's checks
   if (ore_status st = preproc_params(ctx, h, w, c, scale, shift, flags, &q)) return st;
   if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g->rh < 1 || g->rw < 1 || g->rh > RESIZE_MAX || g->rw > RESIZE_MAX)
@@ -156,6 +165,10 @@ ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_
   if (!resize_axis_ok(hs, g->rh, g->top, h) || !resize_axis_ok(ws, g->rw, g->left, w))
     return set_error(ctx, ORE_ERR_INVALID, "resize: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
                      (long long)h, (long long)w, (long long)g->top, (long long)g->left, (long long)g->rh, (long long)g->rw);
+  if (filter == ORE_FILTER_BILINEAR_AA)
+    if (const char* axis = aa_bad_axis(hs, ws, *g))
+      return set_error(ctx, ORE_ERR_INVALID, "resize: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
+                       ORE_AA_MAX_RATIO, axis, (long long)(axis[0] == 'r' ? hs : ws), (long long)(axis[0] == 'r' ? g->rh : g->rw));
   *p = ResizeParams{};
   p->Hs = int(hs); p->Ws = int(ws); p->C = int(c);
   p->Rh = int(g->rh); p->Rw = int(g->rw); p->top = int(g->top); p->left = int(g->left);
@@ -174,6 +187,13 @@ ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale
   p->C = int(l->c); p->H = int(l->h); p->W = int(l->w);
   copy_norm(q, p);
   return ORE_OK;
+}
+
+void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& p) {
+  if (l->filter == ORE_FILTER_BILINEAR_AA)
+    launch_resize_aa_u8_list(p, ctx->stream);
+  else
+    launch_resize_u8_list(p, ctx->stream);
 }
 
 ConvPlan conv_plan(int64_t M, int64_t C, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
@@ -621,6 +641,13 @@ ore_status ore_ctx_set_pool_variant(ore_ctx* ctx, int32_t variant) {
   return ORE_OK;
 }
 
+ore_status ore_ctx_set_resize_variant(ore_ctx* ctx, int32_t variant) {
+  if (!ctx) return set_error(nullptr, ORE_ERR_INVALID, "null context");
+  if (variant < 0 || variant > 1) return set_error(ctx, ORE_ERR_INVALID, "unknown resize variant %d", int(variant));
+  ctx->resize_variant = variant;
+  return ORE_OK;
+}
+
 ore_status ore_ctx_set_stream(ore_ctx* ctx, void* s) {
   if (!ctx) return set_error(nullptr, ORE_ERR_INVALID, "null ctx");
   ctx->stream = reinterpret_cast<hipStream_t>(s);
@@ -895,15 +922,45 @@ ore_status ore_resize_taps(int64_t src, int64_t resized, int64_t origin, int64_t
   return ORE_OK;
 }
 
+ore_status ore_resize_aa_taps(int64_t src, int64_t resized, int64_t origin, int64_t count, int32_t* first, int32_t* ntaps,
+                              int32_t* sum, int32_t* weights) {
+  if (!first || !ntaps || !sum) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  if (!resize_axis_ok(src, resized, origin, count))
+    return set_error(nullptr, ORE_ERR_INVALID, "resize taps: %lld samples resized to %lld (each 1..%d), [%lld, %lld + %lld) of them",
+                     (long long)src, (long long)resized, RESIZE_MAX, (long long)origin, (long long)origin, (long long)count);
+  if (!resize_axis_shrinks(src, resized))
+    return set_error(nullptr, ORE_ERR_INVALID, "resize taps: the axis does not shrink (%lld -> %lld): the antialiasing filter leaves "
+                                               "it to ore_resize_taps", (long long)src, (long long)resized);
+  if (!resize_axis_aa_ok(src, resized))
+    return set_error(nullptr, ORE_ERR_INVALID, "resize taps: the antialiasing filter shrinks an axis at most %d times, not %lld -> %lld",
+                     ORE_AA_MAX_RATIO, (long long)src, (long long)resized);
+  for (int64_t k = 0; k < count; ++k) {
+    const ResizeSpan r = resize_aa_span(int(src), int(resized), int(origin + k));
+    first[k] = r.first;
+    ntaps[k] = r.n;
+    sum[k] = r.sum;
+    if (weights)
+      for (int j = 0; j < ORE_AA_MAX_TAPS; ++j)
+        weights[k * ORE_AA_MAX_TAPS + j] = j < r.n ? resize_aa_weight(int(src), int(resized), int(origin + k), r.first + j) : 0;
+  }
+  return ORE_OK;
+}
+
 ore_status ore_preprocess_resize_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t hs, int64_t ws, int64_t c,
                                     const ore_resize* g, const float* scale, const float* shift, int32_t flags, ore_tensor* y) {
+  return ore_preprocess_resize_u8_ex(ctx, x, n, hs, ws, c, g, ORE_FILTER_BILINEAR, scale, shift, flags, y);
+}
+
+ore_status ore_preprocess_resize_u8_ex(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t hs, int64_t ws, int64_t c,
+                                       const ore_resize* g, int32_t filter, const float* scale, const float* shift,
+                                       int32_t flags, ore_tensor* y) {
   // the pointers, then the geometry, then the context: a host can exercise every check without a device
   if (!x || !g || !y || !y->data) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (n < 0) return set_error(ctx, ORE_ERR_INVALID, "negative batch %lld", (long long)n);
   if (y->ndim != 4 || y->dims[0] != n || y->dims[1] != c)
     return set_error(ctx, ORE_ERR_INVALID, "resize output must be [n,c,H,W] for the [n,hs,ws,c] input");
   ResizeParams p;
-  if (ore_status st = resize_params(ctx, hs, ws, c, y->dims[2], y->dims[3], g, scale, shift, flags, &p)) return st;
+  if (ore_status st = resize_params(ctx, hs, ws, c, y->dims[2], y->dims[3], g, scale, shift, flags, &p, filter)) return st;
   if (nstride_of(y) < c * y->dims[2] * y->dims[3])
     return set_error(ctx, ORE_ERR_INVALID, "resize output: image stride %lld below c*H*W", (long long)nstride_of(y));
   if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null context");
@@ -913,12 +970,22 @@ ore_status ore_preprocess_resize_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, i
   p.N = n;
   p.y_nstride = nstride_of(y);
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  launch_resize_u8(p, ctx->stream);
+  if (filter == ORE_FILTER_BILINEAR_AA)
+    launch_resize_aa_u8(p, ctx->stream);
+  else
+    launch_resize_u8(p, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }
 
 ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int64_t* bad_index) {
+  return ore_image_check_ex(imgs, n, c, h, w, ORE_FILTER_BILINEAR, bad_index);
+}
+
+ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int32_t filter,
+                              int64_t* bad_index) {
+  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+    return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
   PreprocParams q;  // c and the output size: the direct conversion's checks
   if (ore_status st = preproc_params(nullptr, h, w, c, nullptr, nullptr, 0, &q)) return st;
@@ -941,6 +1008,9 @@ ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: row stride %lld below ws*c = %lld", (long long)i, rs, ws * (long long)c);
     else if (hs > 1 && (!fits_i32(rs) || !fits_i32((hs - 1) * (rs ? rs : ws * c) + ws * c)))  // a one-row image never steps a row
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hs, rs);
+    else if (const char* axis = filter == ORE_FILTER_BILINEAR_AA ? aa_bad_axis(hs, ws, g) : nullptr)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
+                     (long long)i, ORE_AA_MAX_RATIO, axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
     if (st) {
       if (bad_index) *bad_index = i;
       return st;
@@ -950,7 +1020,16 @@ ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64
 }
 
 ore_status ore_image_list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, ore_image_list** out) {
+  return ore_image_list_create_ex(ctx, capacity, c, h, w, ORE_FILTER_BILINEAR, out);
+}
+
+int32_t ore_image_list_filter(ore_image_list* l) { return l ? l->filter : ORE_FILTER_BILINEAR; }
+
+ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter,
+                                    ore_image_list** out) {
   if (!ctx || !out) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+    return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   PreprocParams q;
   if (ore_status st = preproc_params(ctx, h, w, c, nullptr, nullptr, 0, &q)) return st;
   if (capacity < 1 || !fits_i32(capacity))
@@ -960,6 +1039,7 @@ ore_status ore_image_list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int6
   l->ctx = ctx;
   l->capacity = capacity;
   l->c = c; l->h = h; l->w = w;
+  l->filter = filter;
   const size_t bytes = size_t(capacity) * sizeof(ResizeImage);
   if (hipMalloc(reinterpret_cast<void**>(&l->table), bytes) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&l->mirror), bytes, hipHostMallocDefault) != hipSuccess ||
@@ -991,7 +1071,7 @@ ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
   int64_t bad = -1;
-  if (ore_image_check(imgs, n, l->c, l->h, l->w, &bad)) {
+  if (ore_image_check_ex(imgs, n, l->c, l->h, l->w, l->filter, &bad)) {
     ctx->err = ore_last_error(nullptr);
     return ORE_ERR_INVALID;
   }
@@ -1040,7 +1120,7 @@ ore_status ore_preprocess_list_u8(ore_ctx* ctx, ore_image_list* l, const float* 
   p.y = y->data;
   p.y_nstride = nstride_of(y);
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  launch_resize_u8_list(p, ctx->stream);
+  launch_list(ctx, l, p);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

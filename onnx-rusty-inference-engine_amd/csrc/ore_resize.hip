@@ -85,7 +85,205 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_list_kernel(const Resize
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// ORE_FILTER_BILINEAR_AA (include/ore.h has the arithmetic): an axis that shrinks sums every source sample of
+// the stretched triangle (resize_aa_span / resize_aa_weight), the other axis keeps resize_tap.  Per output
+// element: per tap row the column sum in integers (exact, one conversion) or the column lerp; then the row
+// taps in ascending order, fmul and fadd each rounded on its own, one division by the row weight sum (or the
+// row lerp); one division by the column weight sum; scale and shift.  The divisions are IEEE (hipcc's default
+// correctly rounded fdiv); they are the only place the ISA holds v_fma.  A run of column taps is read four
+// taps (4 C bytes) at a time as C dwords at the run's own alignment, the rest by bytes.
+//
+// One device body (aa_pixel), dense and list kernels over it, templated on the channel count so that the
+// per-channel sums live in registers: one thread per output pixel walks its taps_y x taps_x window in global
+// memory, any size, alignment, row stride and y stride, 64-bit image bases only.  A band kernel (a workgroup
+// computing the horizontal sums of a band's source rows once into LDS, then the vertical chains from LDS) gave
+// the same bits but was slower at both bench geometries and was removed (DESIGN.md 3.8d has the numbers).
+
+struct AaImage {
+  const unsigned char* x;
+  int Hs, Ws, row;  // row: bytes between rows
+  int Rh, Rw, top, left;
+};
+
+__device__ __forceinline__ float macc_rn(float acc, float v, float g) {
+#pragma clang fp contract(off)
+  const float p = v * g;
+  return acc + p;
+}
+
+// the taps of one axis for resized index o: a run (shrinking) or the two samples of resize_tap
+struct AaAxis {
+  int first, n, sum;  // shrinking: resize_aa_span
+  int i1;             // plain: samples first and i1, weight t
+  float t;
+};
+
+__device__ __forceinline__ AaAxis aa_axis(bool shrinks, int S, int D, int o) {
+  AaAxis a;
+  if (shrinks) {
+    const ResizeSpan sp = resize_aa_span(S, D, o);
+    a.first = sp.first; a.n = sp.n; a.sum = sp.sum;
+    a.i1 = sp.first; a.t = 0.f;
+  } else {
+    const ResizeTap tp = resize_tap(S, D, o);
+    a.first = tp.i0; a.n = 2; a.sum = 1;
+    a.i1 = tp.i1; a.t = tp.t;
+  }
+  return a;
+}
+
+// g of one source row (xr: its first byte) for resized column ox
+template <int C>
+__device__ __forceinline__ void aa_row(const unsigned char* __restrict__ xr, bool sx, const AaAxis& ax, int Ws, int Rw,
+                                       int ox, float (&g)[C]) {
+  if (sx) {
+    int acc[C];
+#pragma unroll
+    for (int s = 0; s < C; ++s) acc[s] = 0;
+    const unsigned char* pp = xr + ax.first * C;
+    int j = 0;
+    // four taps at a time: their 4 C bytes as C dword loads at the window's own (any) alignment, all inside it
+    for (; j + 4 <= ax.n; j += 4) {
+      unsigned d[C];
+#pragma unroll
+      for (int i = 0; i < C; ++i) __builtin_memcpy(&d[i], pp + j * C + 4 * i, 4);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int u = resize_aa_weight(Ws, Rw, ox, ax.first + j + t);
+#pragma unroll
+        for (int s = 0; s < C; ++s) {
+          const int k = t * C + s;
+          acc[s] += __mul24(u, int((d[k >> 2] >> (8 * (k & 3))) & 0xffu));
+        }
+      }
+    }
+    for (; j < ax.n; ++j) {
+      const int u = resize_aa_weight(Ws, Rw, ox, ax.first + j);
+#pragma unroll
+      for (int s = 0; s < C; ++s) acc[s] += __mul24(u, int(pp[j * C + s]));
+    }
+#pragma unroll
+    for (int s = 0; s < C; ++s) g[s] = float(acc[s]);
+  } else {
+#pragma unroll
+    for (int s = 0; s < C; ++s) g[s] = lerp_rn(float(xr[ax.first * C + s]), float(xr[ax.i1 * C + s]), ax.t);
+  }
+}
+
+// after the vertical step: the column division, scale and shift, and the C stores of pixel px
+template <int C, class P>
+__device__ __forceinline__ void aa_store(const P& p, float* __restrict__ yi, int HW, int px, bool sx, int U, float (&w)[C]) {
+  const float uf = float(U);
+#pragma unroll
+  for (int s = 0; s < C; ++s) {
+    const float v = sx ? w[s] / uf : w[s];
+    yi[size_t(p.plane[s]) * size_t(HW) + px] = norm_rn(v, p.scale[s], p.shift[s]);
+  }
+}
+
+// one output pixel (r, q) of image d from global memory
+template <int C, class P>
+__device__ __forceinline__ void aa_pixel(const AaImage& d, const P& p, float* __restrict__ yi, int HW, int W, int r, int q) {
+  const bool sx = d.Ws > d.Rw, sy = d.Hs > d.Rh;
+  const int oy = d.top + r, ox = d.left + q;
+  const AaAxis ax = aa_axis(sx, d.Ws, d.Rw, ox);
+  const AaAxis ay = aa_axis(sy, d.Hs, d.Rh, oy);
+  float w[C];
+  if (sy) {
+#pragma unroll
+    for (int s = 0; s < C; ++s) w[s] = 0.f;
+    for (int i = 0; i < ay.n; ++i) {
+      float g[C];
+      aa_row<C>(d.x + size_t(ay.first + i) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g);
+      const float v = float(resize_aa_weight(d.Hs, d.Rh, oy, ay.first + i));
+#pragma unroll
+      for (int s = 0; s < C; ++s) w[s] = macc_rn(w[s], v, g[s]);
+    }
+    const float vf = float(ay.sum);
+#pragma unroll
+    for (int s = 0; s < C; ++s) w[s] = w[s] / vf;
+  } else {
+    float g0[C], g1[C];
+    aa_row<C>(d.x + size_t(ay.first) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g0);
+    aa_row<C>(d.x + size_t(ay.i1) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g1);
+#pragma unroll
+    for (int s = 0; s < C; ++s) w[s] = lerp_rn(g0[s], g1[s], ay.t);
+  }
+  aa_store<C>(p, yi, HW, r * W + q, sx, ax.sum, w);
+}
+
+__device__ __forceinline__ AaImage aa_image(const ResizeParams& p, long long i) {
+  AaImage d;
+  d.row = p.Ws * p.C;
+  d.x = p.x + size_t(i) * size_t(p.Hs) * size_t(d.row);
+  d.Hs = p.Hs; d.Ws = p.Ws;
+  d.Rh = p.Rh; d.Rw = p.Rw; d.top = p.top; d.left = p.left;
+  return d;
+}
+
+__device__ __forceinline__ AaImage aa_image(const ResizeImage& t) {
+  AaImage d;
+  d.x = t.x;
+  d.Hs = t.Hs; d.Ws = t.Ws; d.row = t.row;
+  d.Rh = t.Rh; d.Rw = t.Rw; d.top = t.top; d.left = t.left;
+  return d;
+}
+
+template <int C>
+__global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_kernel(ResizeParams p) {
+  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
+    aa_pixel<C>(aa_image(p, i), p, p.y + size_t(i) * size_t(p.y_nstride), HW, p.W, r, q);
+}
+
+// the list descriptor is one scalar load per workgroup, as in resize_u8_list_kernel
+template <int C>
+__global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_list_kernel(const ResizeImage* __restrict__ table,
+                                                                          ResizeListParams p) {
+  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
+    aa_pixel<C>(aa_image(table[i]), p, p.y + size_t(i) * size_t(p.y_nstride), HW, p.W, r, q);
+}
+
+template <class K, class... A>
+void aa_launch(K k, const dim3& grid, hipStream_t s, A... a) {
+  hipLaunchKernelGGL(k, grid, dim3(RS_THREADS), 0, s, a...);
+}
+
 }  // namespace
+
+void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  if (p.Hs <= p.Rh && p.Ws <= p.Rw) return launch_resize_u8(p, s);  // nothing shrinks: the plain filter, bit for bit
+  const long long hw = (long long)p.H * p.W;
+  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  switch (p.C) {
+    case 1: return aa_launch(resize_aa_pixel_kernel<1>, grid, s, p);
+    case 2: return aa_launch(resize_aa_pixel_kernel<2>, grid, s, p);
+    case 3: return aa_launch(resize_aa_pixel_kernel<3>, grid, s, p);
+    default: return aa_launch(resize_aa_pixel_kernel<4>, grid, s, p);
+  }
+}
+
+void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  const ResizeImage* table = p.table + p.first;
+  const long long hw = (long long)p.H * p.W;
+  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  switch (p.C) {
+    case 1: return aa_launch(resize_aa_pixel_list_kernel<1>, grid, s, table, p);
+    case 2: return aa_launch(resize_aa_pixel_list_kernel<2>, grid, s, table, p);
+    case 3: return aa_launch(resize_aa_pixel_list_kernel<3>, grid, s, table, p);
+    default: return aa_launch(resize_aa_pixel_list_kernel<4>, grid, s, table, p);
+  }
+}
 
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;

@@ -28,6 +28,8 @@ LOAD_RETIRED_MASK = 10  # ABI 1's LOAD_X3 / LOAD_X3_ALL: rejected (ORE_ERR_UNSUP
 ABI_VERSION = 2  # ORE_ABI_VERSION this binding was written against
 CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD = 0, 1  # ore_ctx_set_conv_algo (per-op ore_conv2d_f32)
 PRE_REVERSE_CHANNELS = 1  # ore_preprocess_u8 / _resize_u8 / ore_model_set_input_norm flag: RGB <-> BGR
+FILTER_BILINEAR, FILTER_BILINEAR_AA = 0, 1  # ore_resize_filter (the _ex resize entries)
+AA_MAX_RATIO, AA_MAX_TAPS = 32, 64  # ORE_AA_MAX_RATIO / ORE_AA_MAX_TAPS: the antialiased filter's shrink limit and taps per axis
 PAD = {"NOTSET": 0, "NOT_SET": 0, "SAME_UPPER": 1, "SAME_LOWER": 2, "VALID": 3}
 
 # every symbol include/ore.h declares (checked by tests/test_abi.py on CPU)
@@ -39,6 +41,8 @@ EXPORTED = [
     "ore_reshape", "ore_preprocess_u8", "ore_model_set_input_norm", "ore_model_run_u8", "ore_model_graph_capture_u8",
     "ore_resize_taps", "ore_preprocess_resize_u8", "ore_model_set_input_resize",
     "ore_image_check", "ore_image_list_create", "ore_image_list_destroy", "ore_image_list_set", "ore_image_list_count",
+    "ore_resize_aa_taps", "ore_preprocess_resize_u8_ex", "ore_image_check_ex", "ore_image_list_create_ex", "ore_image_list_filter",
+    "ore_model_set_input_resize_ex", "ore_ctx_set_resize_variant",
     "ore_preprocess_list_u8", "ore_model_run_u8_list", "ore_model_classify_u8_list", "ore_model_graph_capture_u8_list",
     "ore_model_graph_capture_classify_u8_list",
     "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
@@ -140,6 +144,13 @@ def load():
         "ore_image_list_set": (i32, [vp, ctypes.POINTER(ImageU8), i64]),
         "ore_image_list_count": (i64, [vp]),
         "ore_preprocess_list_u8": (i32, [vp, vp, F32P, F32P, i32, T]),
+        "ore_resize_aa_taps": (i32, [i64, i64, i64, i64, vp, vp, vp, vp]),
+        "ore_preprocess_resize_u8_ex": (i32, [vp, vp, i64, i64, i64, i64, ctypes.POINTER(Resize), i32, F32P, F32P, i32, T]),
+        "ore_image_check_ex": (i32, [ctypes.POINTER(ImageU8), i64, i64, i64, i64, i32, I64P]),
+        "ore_image_list_create_ex": (i32, [vp, i64, i64, i64, i64, i32, ctypes.POINTER(vp)]),
+        "ore_image_list_filter": (i32, [vp]),
+        "ore_model_set_input_resize_ex": (i32, [vp, i64, i64, ctypes.POINTER(Resize), i32]),
+        "ore_ctx_set_resize_variant": (i32, [vp, i32]),
         "ore_model_run_u8_list": (i32, [vp, vp, vp]),
         "ore_model_classify_u8_list": (i32, [vp, vp, vp, vp]),
         "ore_model_graph_capture_u8_list": (i32, [vp, vp, vp]),

@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "preprocess_list_u8", "resize_taps", "center_crop_geometry", "topk", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "center_crop_geometry", "topk", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -60,6 +60,11 @@ class Context:
         """ore_ctx_set_pool_variant: force a MaxPool kernel (2 direct, 3 column strip, 4 plane-staged,
         5 chunk-staged; 0 = by layout)."""
         check(load().ore_ctx_set_pool_variant(self.h, int(variant)), self.h)
+
+    def set_resize_variant(self, variant: int = 0):
+        """ore_ctx_set_resize_variant: force a kernel of the antialiased resize (1 one thread per output
+        pixel; 0 = by geometry, which is that kernel today).  Results do not depend on it."""
+        check(load().ore_ctx_set_resize_variant(self.h, int(variant)), self.h)
 
     @property
     def stream(self) -> int:
@@ -300,18 +305,43 @@ def center_crop_geometry(src_hw, short: int, out_hw):
     return (rh, rw), ((rh - h) // 2, (rw - w) // 2)
 
 
-def _resize_arg(src_hw, out_hw, resized_hw, origin):
-    """The ore_resize of a [hs, ws] -> resized_hw (None: out_hw, a plain resize) -> out_hw window at origin."""
+def resize_aa_taps(src: int, resized: int, origin: int, count: int):
+    """ore_resize_aa_taps (host only): the antialiased filter's table of one shrinking axis (`src` > `resized`,
+    at most 32 times), for the `count` resized indices from `origin`: (first int32, ntaps int32, sum int32,
+    weights int32 [count, 64]): index k blends source samples first[k] .. first[k] + ntaps[k] - 1 with the
+    integer weights weights[k, :ntaps[k]] out of sum[k]."""
+    n = min(max(int(count), 0), 16384)  # the library rejects anything outside 1..16384
+    first, ntaps, total = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+    weights = np.empty((n, _lib.AA_MAX_TAPS), np.int32)
+    check(load().ore_resize_aa_taps(int(src), int(resized), int(origin), int(count), first.ctypes.data_as(ctypes.c_void_p),
+                                    ntaps.ctypes.data_as(ctypes.c_void_p), total.ctypes.data_as(ctypes.c_void_p),
+                                    weights.ctypes.data_as(ctypes.c_void_p)))
+    return first, ntaps, total, weights
+
+
+def _resize_arg(src_hw, out_hw, resized_hw, origin, antialias=False, name="resize"):
+    """The ore_resize of a [hs, ws] -> resized_hw (None: out_hw, a plain resize) -> out_hw window at origin.
+    Under antialias the ratio rule is checked here as the library checks it."""
     rh, rw = (int(v) for v in (out_hw if resized_hw is None else resized_hw))
     top, left = (int(v) for v in origin)
+    if antialias:
+        for axis, s, d in (("rows", int(src_hw[0]), rh), ("columns", int(src_hw[1]), rw)):
+            if d >= 1 and s > _lib.AA_MAX_RATIO * d:
+                raise OreError(1, f"{name}: the antialiasing filter shrinks an axis at most {_lib.AA_MAX_RATIO} times, "
+                                  f"the {axis} go {s} -> {d}")
     return Resize(rh, rw, top, left)
 
 
+def _filter(antialias) -> int:
+    return _lib.FILTER_BILINEAR_AA if antialias else _lib.FILTER_BILINEAR
+
+
 def preprocess_resize_u8(ctx: Context, x, out_hw, resized_hw=None, origin=(0, 0), scale=None, shift=None,
-                         reverse_channels: bool = False):
-    """ore_preprocess_resize_u8 (extension): uint8 [n, Hs, Ws, C] -> float32 [n, C, H, W] = out_hw: the images
+                         reverse_channels: bool = False, antialias: bool = False):
+    """ore_preprocess_resize_u8_ex (extension): uint8 [n, Hs, Ws, C] -> float32 [n, C, H, W] = out_hw: the images
     bilinearly resized to resized_hw (None: out_hw), of which the window at `origin` is kept, then normalised
-    as preprocess_u8 does, in one launch."""
+    as preprocess_u8 does, in one launch.  antialias=True: axes that shrink take the area-weighted filter of
+    F.interpolate(antialias=True) / PIL's BILINEAR (each by at most 32 times)."""
     torch = _torch()
     _check_u8(x, ctx.device)
     n, hs, ws, c = (int(d) for d in x.shape)
@@ -320,12 +350,12 @@ def preprocess_resize_u8(ctx: Context, x, out_hw, resized_hw=None, origin=(0, 0)
     h, w = (int(v) for v in out_hw)
     if h < 1 or w < 1:
         raise OreError(1, f"out_hw: {(h, w)}")
-    g = _resize_arg((hs, ws), (h, w), resized_hw, origin)
+    g = _resize_arg((hs, ws), (h, w), resized_hw, origin, antialias)
     y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
     flags = PRE_REVERSE_CHANNELS if reverse_channels else 0
-    check(load().ore_preprocess_resize_u8(ctx.h, ctypes.c_void_p(x.data_ptr()), n, hs, ws, c, ctypes.byref(g),
-                                          _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift"), flags,
-                                          ctypes.byref(_desc(y))), ctx.h)
+    check(load().ore_preprocess_resize_u8_ex(ctx.h, ctypes.c_void_p(x.data_ptr()), n, hs, ws, c, ctypes.byref(g),
+                                             _filter(antialias), _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift"),
+                                             flags, ctypes.byref(_desc(y))), ctx.h)
     return y
 
 
@@ -352,18 +382,21 @@ def _check_image_u8(x, device: int, c: int, name: str):
 class ImageList:
     """ore_image_list: up to `capacity` uint8 images of their own sizes and row strides, each resized and
     cropped to out_hw by its own geometry in ONE launch (preprocess_list_u8, Model.run_u8_list, ...).  The
-    device table and its pinned mirror are allocated here; set() only fills and uploads them."""
+    device table and its pinned mirror are allocated here; set() only fills and uploads them.  antialias=True
+    makes it a list of the antialiased filter (see preprocess_resize_u8): a property of the list."""
 
-    def __init__(self, ctx: Context, capacity: int, out_hw, channels: int = 3):
+    def __init__(self, ctx: Context, capacity: int, out_hw, channels: int = 3, antialias: bool = False):
         h, w = (int(v) for v in out_hw)
         self.ctx = ctx
         self.capacity = int(capacity)
         self.out_hw = (h, w)
         self.channels = int(channels)
+        self.antialias = bool(antialias)
         self._images = ()
         self.h = None
         hnd = ctypes.c_void_p()
-        check(load().ore_image_list_create(ctx.h, self.capacity, self.channels, h, w, ctypes.byref(hnd)), ctx.h)
+        check(load().ore_image_list_create_ex(ctx.h, self.capacity, self.channels, h, w, _filter(antialias),
+                                              ctypes.byref(hnd)), ctx.h)
         self.h = hnd
 
     def _descriptors(self, images, geometries, short):
@@ -388,7 +421,7 @@ class ImageList:
             arr[i].data = x.data_ptr()
             arr[i].hs, arr[i].ws = hs, ws
             arr[i].row_stride = int(x.stride(0))
-            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin)
+            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"images[{i}]")
         return images, arr
 
     def set(self, images, geometries=None, short=None):
@@ -531,18 +564,18 @@ class Model:
         sc, sh = _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift")
         check(load().ore_model_set_input_norm(self.h, sc, sh, c, flags), self.ctx.h)
 
-    def set_input_resize(self, src_hw, resized_hw=None, origin=(0, 0)):
-        """ore_model_set_input_resize: from now on run_u8 / classify_u8 / capture_u8 / capture_classify_u8 take
+    def set_input_resize(self, src_hw, resized_hw=None, origin=(0, 0), antialias: bool = False):
+        """ore_model_set_input_resize_ex: from now on run_u8 / classify_u8 / capture_u8 / capture_classify_u8 take
         uint8 [n, Hs, Ws, C] batches with (Hs, Ws) = src_hw, resized to resized_hw (None: the model's H x W) and
-        cropped to the model's H x W at `origin` on the device (see preprocess_resize_u8), with the
-        normalisation of set_input_norm.  src_hw None: back to [n, H, W, C]."""
+        cropped to the model's H x W at `origin` on the device (see preprocess_resize_u8, also for antialias),
+        with the normalisation of set_input_norm.  src_hw None: back to [n, H, W, C]."""
         if src_hw is None:
             check(load().ore_model_set_input_resize(self.h, 0, 0, None), self.ctx.h)
             self.input_src_hw = None
             return
         hs, ws = (int(v) for v in src_hw)
-        g = _resize_arg((hs, ws), self.input_dims[1:], resized_hw, origin)
-        check(load().ore_model_set_input_resize(self.h, hs, ws, ctypes.byref(g)), self.ctx.h)
+        g = _resize_arg((hs, ws), self.input_dims[1:], resized_hw, origin, antialias, "set_input_resize")
+        check(load().ore_model_set_input_resize_ex(self.h, hs, ws, ctypes.byref(g), _filter(antialias)), self.ctx.h)
         self.input_src_hw = (hs, ws)
 
     def _check_u8_dims(self, x):
