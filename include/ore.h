@@ -16,7 +16,12 @@
  *    same situations (unknown op / attribute / auto_pad string, missing input, shape mismatch).
  *  - Tensors are fp32, NCHW row-major, device memory.  `nstride` is the element distance
  *    between consecutive images (0 = contiguous); it lets an op write a channel slice of a
- *    wider tensor (Concat in place).
+ *    wider tensor (Concat in place).  A non-zero nstride is at least one image's elements (the
+ *    product of dims[1..]) with nstride * dims[0] + 256 below 2^31, or ore_conv2d_f32 and
+ *    ore_maxpool2d_f32 -- the ops that take slices, as x and as y -- return ORE_ERR_INVALID naming
+ *    the tensor before any device call.  (The other ops take contiguous tensors only.)  Any 4-byte
+ *    aligned base is accepted; no op writes outside y's elements, and no element outside x's
+ *    reaches a result (tests/test_slices_gpu.py).
  *  - Launches are asynchronous on the context's HIP stream; ore_sync() joins.  A context is
  *    bound to one device and is not thread-safe (one per host thread / device).
  *  - Padding is resolved exactly as the reference does (including its SAME split with the
@@ -63,7 +68,7 @@ typedef struct ore_tensor {
   float* data;      /* device pointer to element [0,0,0,0] */
   int32_t ndim;     /* 1..4 */
   int64_t dims[4];
-  int64_t nstride;  /* elements between images (dims[0] steps); 0 = contiguous */
+  int64_t nstride;  /* elements between images (dims[0] steps); 0 = contiguous, else >= one image */
 } ore_tensor;
 
 /* Conv attributes (convolution_op.rs:132-173).  pads use ONNX order

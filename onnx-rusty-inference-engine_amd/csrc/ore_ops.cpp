@@ -103,6 +103,21 @@ static bool contiguous(const ore_tensor* t) {
 
 static bool fits_i32(int64_t v) { return v >= 0 && v < (int64_t(1) << 31); }
 
+// The image stride of a 4-D activation that may be a slice (Conv's and MaxPool's x and y): 0 (contiguous) or at
+// least one image's elements -- below that the images overlap and one image's outputs overwrite another's --
+// and, for the kernels' 32-bit image offsets, nstride * N + 256 below 2^31.  Host only.
+static ore_status check_image_stride(ore_ctx* ctx, const char* op, const char* name, const ore_tensor* t) {
+  const int64_t img = t->dims[1] * t->dims[2] * t->dims[3], lim = int64_t(1) << 31;
+  if (t->nstride < 0 || (t->nstride && t->nstride < img))
+    return set_error(ctx, ORE_ERR_INVALID, "%s: %s->nstride %lld is below the image size %lld (images would overlap)", op,
+                     name, (long long)t->nstride, (long long)img);
+  const int64_t s = t->nstride ? t->nstride : img, n = std::max<int64_t>(t->dims[0], 1);
+  if (s >= lim || n >= lim || !fits_i32(s * n + 256))
+    return set_error(ctx, ORE_ERR_INVALID, "%s: %s spans %lld images of stride %lld, past 32-bit indexing", op, name,
+                     (long long)t->dims[0], (long long)s);
+  return ORE_OK;
+}
+
 // mapped bytes before x: the rest of x's 4 KiB page, or the walker's arena lead where x lies inside the
 // context's mapped range.  The streaming 3x3 conv, the row-walking pooled conv and the f32 fire kernels
 // read a few of them, masked, instead of issuing negative buffer offsets.
@@ -741,6 +756,8 @@ ore_status ore_conv2d_f32(ore_ctx* ctx, const ore_tensor* x, const ore_tensor* w
   if (y->dims[0] != x->dims[0] || y->dims[1] != w->dims[0] || y->dims[2] != win.Ho || y->dims[3] != win.Wo)
     return set_error(ctx, ORE_ERR_INVALID, "Conv output dims mismatch: expected [%lld,%lld,%lld,%lld]",
                      (long long)x->dims[0], (long long)w->dims[0], (long long)win.Ho, (long long)win.Wo);
+  if (ore_status sx = check_image_stride(ctx, "Conv", "x", x)) return sx;
+  if (ore_status sy = check_image_stride(ctx, "Conv", "y", y)) return sy;
   if (x->dims[0] == 0) return ORE_OK;
   const int2* kt = nullptr;
   const ConvGeom g{x->dims[1], x->dims[2], x->dims[3], w->dims[0], w->dims[2], w->dims[3], a->strides[0], a->strides[1],
@@ -761,6 +778,8 @@ ore_status ore_maxpool2d_f32(ore_ctx* ctx, const ore_tensor* x, const ore_pool_a
   if (st) return st;
   if (y->dims[0] != x->dims[0] || y->dims[1] != x->dims[1] || y->dims[2] != win.Ho || y->dims[3] != win.Wo)
     return set_error(ctx, ORE_ERR_INVALID, "MaxPool output dims mismatch");
+  if (ore_status sx = check_image_stride(ctx, "MaxPool", "x", x)) return sx;
+  if (ore_status sy = check_image_stride(ctx, "MaxPool", "y", y)) return sy;
   return run_maxpool(ctx, ref_of(x), ref_of(y), x->dims[0], x->dims[1], x->dims[2], x->dims[3],
                      {a->kernel[0], a->kernel[1], a->strides[0], a->strides[1], win});
 }
