@@ -303,6 +303,61 @@ ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, in
 ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter,
                                     ore_image_list** out);
 int32_t ore_image_list_filter(ore_image_list* l);
+/* NV12 image lists (extension, the *_nv12_list kernels in ore_resize.hip): frames as a video decoder leaves
+ * them -- a full-resolution Y plane and a half-resolution plane of interleaved (U, V) pairs, each with its own
+ * pitch -- straight into an image list, without a colour-conversion pass in between.  Chroma is taken nearest:
+ * source pixel (r, j) is Y at (r, j) and the UV pair at (r >> 1, j >> 1) (cv2.COLOR_YUV2RGB_NV12, libyuv).  The
+ * conversion is fixed in integers (csrc/ore_yuv.h): with U' = U - 128, V' = V - 128, a matrix {yoff, cy, cvr,
+ * cug, cvg, cub} and >> an arithmetic shift (floor),
+ *     y = max(Y - yoff, 0) * cy + 2^19
+ *     R = clamp((y + cvr V') >> 20, 0, 255)
+ *     G = clamp((y - cug U' - cvg V') >> 20, 0, 255)
+ *     B = clamp((y + cub U') >> 20, 0, 255)
+ * with each coefficient round(k * 2^20) of the usual three-decimal constants:
+ *     ORE_YUV_BT601      (limited range, OpenCV's)  {16, 1220542, 1673527, 409993, 852492, 2116026}
+ *     ORE_YUV_BT709      (limited range)            {16, 1220542, 1880097, 223347, 558891, 2214593}
+ *     ORE_YUV_BT601_FULL (JPEG / JFIF)              { 0, 1048576, 1470104, 360853, 748826, 1858077}
+ * Over all 2^24 triples every accumulator fits int32 and every channel is within 1 of the float64 formula
+ * rounded half up.  Image i of an NV12 list is, bit for bit, what an interleaved list (c = 3) of the same
+ * filter gives for the [hs,ws,3] R, G, B bytes of that frame converted by this formula, for the same geometry,
+ * scale / shift and ORE_PRE_REVERSE_CHANNELS (which then yields B, G, R planes).
+ *  ore_yuv_to_rgb: the conversion of n triples from three HOST arrays into rgb[3 n] (host only, it touches no
+ *    device, as ore_resize_taps); it is the map the kernels use.  An unknown matrix is ORE_ERR_INVALID.
+ *  ore_image_nv12: y and uv are DEVICE pointers of any alignment; the UV plane has ceil(hs/2) rows of ceil(ws/2)
+ *    pairs, so odd sizes are legal (the last row / column has a chroma pair of its own).  Strides are in bytes;
+ *    0 means dense: ws for Y, 2 * ceil(ws/2) for UV.  A region of interest of a larger frame is a descriptor
+ *    whose pointers are offset to an EVEN origin (y0, x0): y + y0 * y_pitch + x0 and uv + (y0/2) * uv_pitch + x0.
+ *    At an odd origin the pixels would pair up with the wrong chroma samples: rounding an odd origin to an even
+ *    one is the caller's to do, the library sees only the pointers.
+ *  ore_image_check_nv12: host only, the rules and messages of ore_image_check_ex with c = 3: both pointers
+ *    non-null; sizes, geometry and (under ORE_FILTER_BILINEAR_AA) the ratio rule as there; y_stride 0 or >= ws;
+ *    uv_stride 0 or >= 2 * ceil(ws/2); (hs-1) * y_stride + ws < 2^31 and (ceil(hs/2)-1) * uv_stride +
+ *    2 * ceil(ws/2) < 2^31.
+ *  ore_image_list_create_nv12: an ore_image_list with c = 3 whose format (ore_image_list_format: ORE_IMAGE_NV12)
+ *    and matrix (ore_image_list_matrix) are fixed at creation, as the filter is.  Every entry that takes a list
+ *    -- ore_preprocess_list_u8, the model's _u8_list runs, classifications and captures -- takes it as is.
+ *  ore_image_list_set_nv12: ore_image_list_set for an NV12 list, with the same semantics (check first, the old
+ *    content kept on failure, stream-ordered upload, ORE_ERR_INVALID inside a capture, n == 0 empties).
+ *    ore_image_list_set on an NV12 list and ore_image_list_set_nv12 on an interleaved one are ORE_ERR_INVALID
+ *    and leave the list unchanged. */
+typedef enum { ORE_YUV_BT601 = 0, ORE_YUV_BT709 = 1, ORE_YUV_BT601_FULL = 2 } ore_yuv_matrix;
+typedef enum { ORE_IMAGE_INTERLEAVED = 0, ORE_IMAGE_NV12 = 1 } ore_image_format;
+typedef struct ore_image_nv12 {
+  const uint8_t* y;          /* DEVICE pointer to row 0, column 0 of the Y plane; any alignment */
+  const uint8_t* uv;         /* DEVICE pointer to row 0, pair 0 of the UV plane; any alignment */
+  int64_t hs, ws;            /* frame size, each 1..16384; odd sizes are legal */
+  int64_t y_stride;          /* bytes from a Y row to the next, >= ws; 0 means dense */
+  int64_t uv_stride;         /* bytes from a UV row to the next, >= 2 * ceil(ws/2); 0 means dense */
+  ore_resize g;              /* this frame's own {rh, rw, top, left} */
+} ore_image_nv12;            /* 80 bytes */
+ore_status ore_yuv_to_rgb(int32_t matrix, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n, uint8_t* rgb);
+ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h, int64_t w, int32_t filter,
+                                int64_t* bad_index);
+ore_status ore_image_list_create_nv12(ore_ctx* ctx, int64_t capacity, int64_t h, int64_t w, int32_t filter,
+                                      int32_t matrix, ore_image_list** out);
+ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs, int64_t n);
+int32_t ore_image_list_format(ore_image_list* l);
+int32_t ore_image_list_matrix(ore_image_list* l);
 /* Row-wise top-k (extension; no reference counterpart -- the reference prints the full output tensor): the
  * k best elements of every row of x, in one launch (ore_topk.hip).  Rows are x->dims[0], the row length D
  * the product of the remaining dims (as for ore_softmax_f32); x->nstride >= D is honoured.  values and

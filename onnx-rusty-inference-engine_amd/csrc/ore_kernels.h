@@ -5,6 +5,8 @@
 
 #include <atomic>
 
+#include "ore_yuv.h"
+
 namespace ore {
 
 // XCD-aware bijective workgroup id: the hardware deals block ids round-robin over the 8 XCDs,
@@ -486,6 +488,30 @@ void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s);
 // shrinks goes to launch_resize_u8.
 void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s);
 void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s);
+// the list conversions over NV12 frames (ore_image_list_create_nv12): a full-resolution Y plane and a
+// half-resolution interleaved UV plane, each with its own pitch; source pixel (r, j) is Y at (r, j) and the UV
+// pair at (r >> 1, j >> 1), converted to R, G, B bytes by ore_yuv.h under the list's matrix.  The result is
+// what the interleaved kernels give for those bytes with C = 3.  Packed by ore_image_list_set_nv12:
+struct Nv12Image {
+  const unsigned char* y;   // row 0, column 0 of the Y plane; any alignment
+  const unsigned char* uv;  // row 0, pair 0 of the UV plane; any alignment
+  int Hs, Ws;               // <= RESIZE_MAX; the UV plane has ceil(Hs / 2) rows of ceil(Ws / 2) pairs
+  int yrow, uvrow;          // bytes between rows of each plane; offsets inside a plane stay below 2^31
+  int Rh, Rw, top, left;    // 48 bytes: an 8-byte multiple
+};
+struct Nv12ListParams {
+  const Nv12Image* table;  // image i of the launch is table[first + i]
+  long long first;
+  float* y;                // [N][3][H][W] at an image stride of y_nstride elements
+  long long N;
+  long long y_nstride;
+  int H, W;
+  YuvMatrix m;
+  int plane[3];            // indexed by R, G, B as ResizeListParams is by source channel
+  float scale[3], shift[3];
+};
+void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s);
+void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s);
 // row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,

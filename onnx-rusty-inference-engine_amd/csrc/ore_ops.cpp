@@ -205,6 +205,23 @@ ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale
 }
 
 void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& p) {
+  if (l->format == ORE_IMAGE_NV12) {
+    Nv12ListParams q{};
+    q.table = l->table_nv12;
+    q.first = p.first; q.y = p.y; q.N = p.N; q.y_nstride = p.y_nstride;
+    q.H = p.H; q.W = p.W;
+    yuv_matrix(l->matrix, &q.m);  // checked at creation
+    for (int s = 0; s < 3; ++s) {
+      q.plane[s] = p.plane[s];
+      q.scale[s] = p.scale[s];
+      q.shift[s] = p.shift[s];
+    }
+    if (l->filter == ORE_FILTER_BILINEAR_AA)
+      launch_resize_aa_nv12_list(q, ctx->stream);
+    else
+      launch_resize_nv12_list(q, ctx->stream);
+    return;
+  }
   if (l->filter == ORE_FILTER_BILINEAR_AA)
     launch_resize_aa_u8_list(p, ctx->stream);
   else
@@ -1038,17 +1055,76 @@ ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, in
   return ORE_OK;
 }
 
+ore_status ore_yuv_to_rgb(int32_t matrix, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n, uint8_t* rgb) {
+  YuvMatrix m;
+  if (!yuv_matrix(matrix, &m)) return set_error(nullptr, ORE_ERR_INVALID, "unknown YUV matrix %d", int(matrix));
+  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative count %lld", (long long)n);
+  if (n == 0) return ORE_OK;
+  if (!y || !u || !v || !rgb) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  for (int64_t i = 0; i < n; ++i) {
+    int c[3];
+    yuv_rgb(m, y[i], yuv_chroma(m, u[i], v[i]), c);
+    for (int s = 0; s < 3; ++s) rgb[3 * i + s] = uint8_t(c[s]);
+  }
+  return ORE_OK;
+}
+
+ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
+  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+    return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
+  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
+  PreprocParams q;  // the output size: the direct conversion's checks, with the three channels a frame converts to
+  if (ore_status st = preproc_params(nullptr, h, w, 3, nullptr, nullptr, 0, &q)) return st;
+  if (n == 0) return ORE_OK;
+  if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  for (int64_t i = 0; i < n; ++i) {
+    const ore_image_nv12& d = imgs[i];
+    const ore_resize& g = d.g;
+    const long long hs = d.hs, ws = d.ws, ys = d.y_stride, us = d.uv_stride;
+    const long long hc = (hs + 1) / 2, wc2 = 2 * ((ws + 1) / 2);  // UV rows, and the bytes of one
+    ore_status st = ORE_OK;
+    if (!d.y || !d.uv)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null %s pointer", (long long)i, d.y ? "uv" : "y");
+    else if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
+                     ws, (long long)g.rh, (long long)g.rw, RESIZE_MAX);
+    else if (!resize_axis_ok(hs, g.rh, g.top, h) || !resize_axis_ok(ws, g.rw, g.left, w))
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
+                     (long long)i, (long long)h, (long long)w, (long long)g.top, (long long)g.left, (long long)g.rh, (long long)g.rw);
+    else if (ys != 0 && ys < ws)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: y stride %lld below ws = %lld", (long long)i, ys, ws);
+    else if (us != 0 && us < wc2)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: uv stride %lld below 2*ceil(ws/2) = %lld", (long long)i, us, wc2);
+    else if (hs > 1 && (!fits_i32(ys) || !fits_i32((hs - 1) * (ys ? ys : ws) + ws)))  // a one-row plane never steps a row
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld y rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hs, ys);
+    else if (hc > 1 && (!fits_i32(us) || !fits_i32((hc - 1) * (us ? us : wc2) + wc2)))
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld uv rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hc, us);
+    else if (const char* axis = filter == ORE_FILTER_BILINEAR_AA ? aa_bad_axis(hs, ws, g) : nullptr)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
+                     (long long)i, ORE_AA_MAX_RATIO, axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
+    if (st) {
+      if (bad_index) *bad_index = i;
+      return st;
+    }
+  }
+  return ORE_OK;
+}
+
 ore_status ore_image_list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, ore_image_list** out) {
   return ore_image_list_create_ex(ctx, capacity, c, h, w, ORE_FILTER_BILINEAR, out);
 }
 
 int32_t ore_image_list_filter(ore_image_list* l) { return l ? l->filter : ORE_FILTER_BILINEAR; }
 
-ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter,
-                                    ore_image_list** out) {
+// ore_image_list_create_ex and ore_image_list_create_nv12: the list and the table and mirror of its format
+static ore_status list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter, int32_t format,
+                              int32_t matrix, ore_image_list** out) {
   if (!ctx || !out) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
     return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
+  YuvMatrix ym;
+  if (format == ORE_IMAGE_NV12 && !yuv_matrix(matrix, &ym))
+    return set_error(ctx, ORE_ERR_INVALID, "unknown YUV matrix %d", int(matrix));
   PreprocParams q;
   if (ore_status st = preproc_params(ctx, h, w, c, nullptr, nullptr, 0, &q)) return st;
   if (capacity < 1 || !fits_i32(capacity))
@@ -1059,9 +1135,13 @@ ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, i
   l->capacity = capacity;
   l->c = c; l->h = h; l->w = w;
   l->filter = filter;
-  const size_t bytes = size_t(capacity) * sizeof(ResizeImage);
-  if (hipMalloc(reinterpret_cast<void**>(&l->table), bytes) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&l->mirror), bytes, hipHostMallocDefault) != hipSuccess ||
+  l->format = format;
+  l->matrix = format == ORE_IMAGE_NV12 ? matrix : 0;
+  const bool nv12 = format == ORE_IMAGE_NV12;
+  const size_t bytes = size_t(capacity) * (nv12 ? sizeof(Nv12Image) : sizeof(ResizeImage));
+  void** table = nv12 ? reinterpret_cast<void**>(&l->table_nv12) : reinterpret_cast<void**>(&l->table);
+  void** mirror = nv12 ? reinterpret_cast<void**>(&l->mirror_nv12) : reinterpret_cast<void**>(&l->mirror);
+  if (hipMalloc(table, bytes) != hipSuccess || hipHostMalloc(mirror, bytes, hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&l->uploaded, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
     (void)ore_image_list_destroy(l);
@@ -1070,6 +1150,20 @@ ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, i
   *out = l;
   return ORE_OK;
 }
+
+ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter,
+                                    ore_image_list** out) {
+  return list_create(ctx, capacity, c, h, w, filter, ORE_IMAGE_INTERLEAVED, 0, out);
+}
+
+ore_status ore_image_list_create_nv12(ore_ctx* ctx, int64_t capacity, int64_t h, int64_t w, int32_t filter, int32_t matrix,
+                                      ore_image_list** out) {
+  return list_create(ctx, capacity, 3, h, w, filter, ORE_IMAGE_NV12, matrix, out);
+}
+
+int32_t ore_image_list_format(ore_image_list* l) { return l ? l->format : ORE_IMAGE_INTERLEAVED; }
+
+int32_t ore_image_list_matrix(ore_image_list* l) { return l ? l->matrix : ORE_YUV_BT601; }
 
 ore_status ore_image_list_destroy(ore_image_list* l) {
   if (!l) return ORE_OK;
@@ -1080,20 +1174,18 @@ ore_status ore_image_list_destroy(ore_image_list* l) {
   }
   if (l->mirror) (void)hipHostFree(l->mirror);
   if (l->table) (void)hipFree(l->table);
+  if (l->mirror_nv12) (void)hipHostFree(l->mirror_nv12);
+  if (l->table_nv12) (void)hipFree(l->table_nv12);
   delete l;
   return ORE_OK;
 }
 
 int64_t ore_image_list_count(ore_image_list* l) { return l ? l->count : 0; }
 
-ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n) {
-  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
+// The two sets between the descriptors' check and the mirror's rewrite: the capacity, the capture rule, and the
+// wait for the previous upload to have read the mirror.  n == 0 empties the list here.
+static ore_status list_set_begin(ore_image_list* l, int64_t n) {
   ore_ctx* ctx = l->ctx;
-  int64_t bad = -1;
-  if (ore_image_check_ex(imgs, n, l->c, l->h, l->w, l->filter, &bad)) {
-    ctx->err = ore_last_error(nullptr);
-    return ORE_ERR_INVALID;
-  }
   if (n > l->capacity)
     return set_error(ctx, ORE_ERR_INVALID, "%lld images exceed the list's capacity %lld", (long long)n, (long long)l->capacity);
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -1106,6 +1198,50 @@ ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64
     return ORE_OK;
   }
   ORE_HIP_CHECK(ctx, hipEventSynchronize(l->uploaded));  // the previous upload has read the mirror
+  return ORE_OK;
+}
+
+ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs, int64_t n) {
+  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
+  ore_ctx* ctx = l->ctx;
+  if (l->format != ORE_IMAGE_NV12)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_nv12 on a list of interleaved images: ore_image_list_set is its entry");
+  int64_t bad = -1;
+  if (ore_image_check_nv12(imgs, n, l->h, l->w, l->filter, &bad)) {
+    ctx->err = ore_last_error(nullptr);
+    return ORE_ERR_INVALID;
+  }
+  if (ore_status st = list_set_begin(l, n)) return st;
+  if (n == 0) return ORE_OK;
+  for (int64_t i = 0; i < n; ++i) {
+    const ore_image_nv12& d = imgs[i];
+    const int64_t hc = (d.hs + 1) / 2, wc = (d.ws + 1) / 2;
+    Nv12Image& r = l->mirror_nv12[i];
+    r = Nv12Image{};
+    r.y = d.y; r.uv = d.uv;
+    r.Hs = int(d.hs); r.Ws = int(d.ws);
+    r.yrow = int(d.hs > 1 && d.y_stride ? d.y_stride : d.ws);  // dense where 0, and where no row is ever stepped
+    r.uvrow = int(hc > 1 && d.uv_stride ? d.uv_stride : 2 * wc);
+    r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
+  }
+  ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_nv12, l->mirror_nv12, size_t(n) * sizeof(Nv12Image), hipMemcpyHostToDevice, ctx->stream));
+  ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
+  l->count = n;
+  return ORE_OK;
+}
+
+ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n) {
+  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
+  ore_ctx* ctx = l->ctx;
+  if (l->format != ORE_IMAGE_INTERLEAVED)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set on an NV12 list: ore_image_list_set_nv12 is its entry");
+  int64_t bad = -1;
+  if (ore_image_check_ex(imgs, n, l->c, l->h, l->w, l->filter, &bad)) {
+    ctx->err = ore_last_error(nullptr);
+    return ORE_ERR_INVALID;
+  }
+  if (ore_status st = list_set_begin(l, n)) return st;
+  if (n == 0) return ORE_OK;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_u8& d = imgs[i];
     ResizeImage& r = l->mirror[i];

@@ -12,6 +12,7 @@
 // where this kernel already moves its bytes at the device-to-device copy rate, and was removed
 // (DESIGN.md 3.8b has the numbers).
 // Image bases are 64-bit; offsets inside one image stay below 2^31 (sizes <= RESIZE_MAX, C <= 4).
+// The list kernels exist twice: over interleaved bytes, and over NV12 planes converted on the fly (further down).
 #include <hip/hip_runtime.h>
 
 #include "ore_kernels.h"
@@ -182,9 +183,104 @@ __device__ __forceinline__ void aa_store(const P& p, float* __restrict__ yi, int
   }
 }
 
-// one output pixel (r, q) of image d from global memory
-template <int C, class P>
-__device__ __forceinline__ void aa_pixel(const AaImage& d, const P& p, float* __restrict__ yi, int HW, int W, int r, int q) {
+// ---------------------------------------------------------------------------------------------------------
+// NV12 sources (ore_image_list_create_nv12): the pixel fetch of the kernels above replaced by fetch and convert.
+// Source pixel (r, j) is the Y byte at (r, j) and the UV pair at (r >> 1, j >> 1), converted by ore_yuv.h to the
+// R, G, B bytes the interleaved kernels would read with C = 3; everything after the fetch is their code.  The
+// six matrix integers are kernel arguments (SGPRs).  The clamp makes the conversion non-linear, so it is done
+// per tap and cannot leave the sums; what depends on the chroma pair alone (yuv_chroma) is computed once per pair.
+
+struct AaNv12 {
+  const unsigned char* y;
+  const unsigned char* uv;
+  int Hs, Ws, yrow, uvrow;
+  int Rh, Rw, top, left;
+  YuvMatrix m;
+};
+
+__device__ __forceinline__ AaNv12 aa_image(const Nv12Image& t, const YuvMatrix& m) {
+  AaNv12 d;
+  d.y = t.y; d.uv = t.uv;
+  d.Hs = t.Hs; d.Ws = t.Ws; d.yrow = t.yrow; d.uvrow = t.uvrow;
+  d.Rh = t.Rh; d.Rw = t.Rw; d.top = t.top; d.left = t.left;
+  d.m = m;
+  return d;
+}
+
+// the chroma terms of pair c of UV row ur: two bytes at any alignment
+__device__ __forceinline__ YuvChroma nv12_chroma(const YuvMatrix& m, const unsigned char* __restrict__ ur, int c) {
+  unsigned short uv;
+  __builtin_memcpy(&uv, ur + 2 * c, 2);
+  return yuv_chroma(m, int(uv & 0xffu), int(uv >> 8));
+}
+
+// R, G, B of source pixel j of a row (yr: its Y bytes, ur: its UV pairs)
+__device__ __forceinline__ void nv12_pixel(const YuvMatrix& m, const unsigned char* __restrict__ yr,
+                                           const unsigned char* __restrict__ ur, int j, int (&rgb)[3]) {
+  yuv_rgb(m, int(yr[j]), nv12_chroma(m, ur, j >> 1), rgb);
+}
+
+// g of source row r for resized column ox: aa_row over converted pixels.  A run of column taps reads its Y
+// bytes four taps at a time as one dword at the run's own alignment, and the two chroma pairs those four taps
+// share -- three where the run starts on an odd column, the first and the last then serving one tap each.
+__device__ __forceinline__ void aa_row_nv12(const AaNv12& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[3]) {
+  const unsigned char* yr = d.y + size_t(r) * size_t(d.yrow);
+  const unsigned char* ur = d.uv + size_t(r >> 1) * size_t(d.uvrow);
+  if (sx) {
+    int acc[3] = {0, 0, 0};
+    const unsigned char* pp = yr + ax.first;
+    const bool odd = (ax.first & 1) != 0;  // j steps by four: every group of the run starts on the same parity
+    int j = 0;
+    for (; j + 4 <= ax.n; j += 4) {
+      unsigned yy;
+      __builtin_memcpy(&yy, pp + j, 4);
+      const int c0 = (ax.first + j) >> 1;
+      const YuvChroma k0 = nv12_chroma(d.m, ur, c0), k1 = nv12_chroma(d.m, ur, c0 + 1);
+      // tap t takes pair (odd + t) >> 1; the third pair exists where it is needed: tap 3 of an odd start is inside the row
+      const YuvChroma k2 = odd ? nv12_chroma(d.m, ur, c0 + 2) : k1;
+      const YuvChroma kt[4] = {k0, odd ? k1 : k0, k1, k2};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j + t);
+        int rgb[3];
+        yuv_rgb(d.m, int((yy >> (8 * t)) & 0xffu), kt[t], rgb);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
+      }
+    }
+    for (; j < ax.n; ++j) {
+      const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j);
+      int rgb[3];
+      nv12_pixel(d.m, yr, ur, ax.first + j, rgb);
+#pragma unroll
+      for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) g[s] = float(acc[s]);
+  } else {
+    int a[3], b[3];
+    nv12_pixel(d.m, yr, ur, ax.first, a);
+    nv12_pixel(d.m, yr, ur, ax.i1, b);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) g[s] = lerp_rn(float(a[s]), float(b[s]), ax.t);
+  }
+}
+
+// g of source row r of an image, by the kind of its source
+template <int C>
+__device__ __forceinline__ void aa_src_row(const AaImage& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[C]) {
+  aa_row<C>(d.x + size_t(r) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g);
+}
+
+template <int C>
+__device__ __forceinline__ void aa_src_row(const AaNv12& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[C]) {
+  static_assert(C == 3, "an NV12 frame converts to three channels");
+  aa_row_nv12(d, r, sx, ax, ox, g);
+}
+
+// one output pixel (r, q) of image d (AaImage: interleaved bytes; AaNv12) from global memory
+template <int C, class D, class P>
+__device__ __forceinline__ void aa_pixel(const D& d, const P& p, float* __restrict__ yi, int HW, int W, int r, int q) {
   const bool sx = d.Ws > d.Rw, sy = d.Hs > d.Rh;
   const int oy = d.top + r, ox = d.left + q;
   const AaAxis ax = aa_axis(sx, d.Ws, d.Rw, ox);
@@ -195,7 +291,7 @@ __device__ __forceinline__ void aa_pixel(const AaImage& d, const P& p, float* __
     for (int s = 0; s < C; ++s) w[s] = 0.f;
     for (int i = 0; i < ay.n; ++i) {
       float g[C];
-      aa_row<C>(d.x + size_t(ay.first + i) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g);
+      aa_src_row<C>(d, ay.first + i, sx, ax, ox, g);
       const float v = float(resize_aa_weight(d.Hs, d.Rh, oy, ay.first + i));
 #pragma unroll
       for (int s = 0; s < C; ++s) w[s] = macc_rn(w[s], v, g[s]);
@@ -205,8 +301,8 @@ __device__ __forceinline__ void aa_pixel(const AaImage& d, const P& p, float* __
     for (int s = 0; s < C; ++s) w[s] = w[s] / vf;
   } else {
     float g0[C], g1[C];
-    aa_row<C>(d.x + size_t(ay.first) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g0);
-    aa_row<C>(d.x + size_t(ay.i1) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g1);
+    aa_src_row<C>(d, ay.first, sx, ax, ox, g0);
+    aa_src_row<C>(d, ay.i1, sx, ax, ox, g1);
 #pragma unroll
     for (int s = 0; s < C; ++s) w[s] = lerp_rn(g0[s], g1[s], ay.t);
   }
@@ -252,6 +348,45 @@ __global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_list_kernel(const 
     aa_pixel<C>(aa_image(table[i]), p, p.y + size_t(i) * size_t(p.y_nstride), HW, p.W, r, q);
 }
 
+// the NV12 list kernels: resize_u8_list_kernel and resize_aa_pixel_list_kernel<3> over converted pixels; the
+// descriptor is one scalar load per workgroup as there
+__global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
+  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const Nv12Image d = table[i];
+    const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
+    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
+    const unsigned char* y0 = d.y + size_t(ty.i0) * size_t(d.yrow);
+    const unsigned char* y1 = d.y + size_t(ty.i1) * size_t(d.yrow);
+    const unsigned char* u0 = d.uv + size_t(ty.i0 >> 1) * size_t(d.uvrow);
+    const unsigned char* u1 = d.uv + size_t(ty.i1 >> 1) * size_t(d.uvrow);
+    int a[3], b[3], c[3], e[3];
+    nv12_pixel(p.m, y0, u0, tx.i0, a);
+    nv12_pixel(p.m, y0, u0, tx.i1, b);
+    nv12_pixel(p.m, y1, u1, tx.i0, c);
+    nv12_pixel(p.m, y1, u1, tx.i1, e);
+    float* yi = p.y + size_t(i) * size_t(p.y_nstride) + px;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
+      const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
+      yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void resize_aa_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
+  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
+    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, p.W, r, q);
+}
+
 template <class K, class... A>
 void aa_launch(K k, const dim3& grid, hipStream_t s, A... a) {
   hipLaunchKernelGGL(k, grid, dim3(RS_THREADS), 0, s, a...);
@@ -283,6 +418,20 @@ void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s) {
     case 3: return aa_launch(resize_aa_pixel_list_kernel<3>, grid, s, table, p);
     default: return aa_launch(resize_aa_pixel_list_kernel<4>, grid, s, table, p);
   }
+}
+
+void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  const long long hw = (long long)p.H * p.W;
+  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  aa_launch(resize_nv12_list_kernel, grid, s, p.table + p.first, p);
+}
+
+void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  const long long hw = (long long)p.H * p.W;
+  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  aa_launch(resize_aa_nv12_list_kernel, grid, s, p.table + p.first, p);
 }
 
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s) {

@@ -30,6 +30,9 @@ CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD = 0, 1  # ore_ctx_set_conv_algo (per-op ore
 PRE_REVERSE_CHANNELS = 1  # ore_preprocess_u8 / _resize_u8 / ore_model_set_input_norm flag: RGB <-> BGR
 FILTER_BILINEAR, FILTER_BILINEAR_AA = 0, 1  # ore_resize_filter (the _ex resize entries)
 AA_MAX_RATIO, AA_MAX_TAPS = 32, 64  # ORE_AA_MAX_RATIO / ORE_AA_MAX_TAPS: the antialiased filter's shrink limit and taps per axis
+YUV_BT601, YUV_BT709, YUV_BT601_FULL = 0, 1, 2  # ore_yuv_matrix (ore_yuv_to_rgb, the NV12 image lists)
+YUV_MATRICES = {"bt601": YUV_BT601, "bt709": YUV_BT709, "bt601_full": YUV_BT601_FULL}
+IMAGE_INTERLEAVED, IMAGE_NV12 = 0, 1  # ore_image_format (ore_image_list_format)
 PAD = {"NOTSET": 0, "NOT_SET": 0, "SAME_UPPER": 1, "SAME_LOWER": 2, "VALID": 3}
 
 # every symbol include/ore.h declares (checked by tests/test_abi.py on CPU)
@@ -43,6 +46,8 @@ EXPORTED = [
     "ore_image_check", "ore_image_list_create", "ore_image_list_destroy", "ore_image_list_set", "ore_image_list_count",
     "ore_resize_aa_taps", "ore_preprocess_resize_u8_ex", "ore_image_check_ex", "ore_image_list_create_ex", "ore_image_list_filter",
     "ore_model_set_input_resize_ex", "ore_ctx_set_resize_variant",
+    "ore_yuv_to_rgb", "ore_image_check_nv12", "ore_image_list_create_nv12", "ore_image_list_set_nv12", "ore_image_list_format",
+    "ore_image_list_matrix",
     "ore_preprocess_list_u8", "ore_model_run_u8_list", "ore_model_classify_u8_list", "ore_model_graph_capture_u8_list",
     "ore_model_graph_capture_classify_u8_list",
     "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
@@ -76,6 +81,13 @@ class ImageU8(ctypes.Structure):
     (0: dense) and its own geometry."""
     _fields_ = [("data", ctypes.c_void_p), ("hs", ctypes.c_int64), ("ws", ctypes.c_int64), ("row_stride", ctypes.c_int64),
                 ("g", Resize)]
+
+
+class ImageNv12(ctypes.Structure):
+    """ore_image_nv12: one frame of an NV12 image list: DEVICE pointers to its Y and UV planes, its size, the bytes
+    from a row to the next of each plane (0: dense) and its own geometry."""
+    _fields_ = [("y", ctypes.c_void_p), ("uv", ctypes.c_void_p), ("hs", ctypes.c_int64), ("ws", ctypes.c_int64),
+                ("y_stride", ctypes.c_int64), ("uv_stride", ctypes.c_int64), ("g", Resize)]
 
 
 class ConvAttrs(ctypes.Structure):
@@ -149,6 +161,12 @@ def load():
         "ore_image_check_ex": (i32, [ctypes.POINTER(ImageU8), i64, i64, i64, i64, i32, I64P]),
         "ore_image_list_create_ex": (i32, [vp, i64, i64, i64, i64, i32, ctypes.POINTER(vp)]),
         "ore_image_list_filter": (i32, [vp]),
+        "ore_yuv_to_rgb": (i32, [i32, vp, vp, vp, i64, vp]),
+        "ore_image_check_nv12": (i32, [ctypes.POINTER(ImageNv12), i64, i64, i64, i32, I64P]),
+        "ore_image_list_create_nv12": (i32, [vp, i64, i64, i64, i32, i32, ctypes.POINTER(vp)]),
+        "ore_image_list_set_nv12": (i32, [vp, ctypes.POINTER(ImageNv12), i64]),
+        "ore_image_list_format": (i32, [vp]),
+        "ore_image_list_matrix": (i32, [vp]),
         "ore_model_set_input_resize_ex": (i32, [vp, i64, i64, ctypes.POINTER(Resize), i32]),
         "ore_ctx_set_resize_variant": (i32, [vp, i32]),
         "ore_model_run_u8_list": (i32, [vp, vp, vp]),

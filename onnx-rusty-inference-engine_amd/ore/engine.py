@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "center_crop_geometry", "topk", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "yuv_to_rgb", "nv12_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "center_crop_geometry", "topk", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -450,6 +450,135 @@ class ImageList:
             self.close()
         except Exception:
             pass
+
+
+def _yuv_matrix(matrix) -> int:
+    """An ore_yuv_matrix id from its name ("bt601", "bt709", "bt601_full") or the id itself."""
+    if isinstance(matrix, str):
+        if matrix.lower() not in _lib.YUV_MATRICES:
+            raise OreError(1, f"matrix: {matrix!r} is not one of {sorted(_lib.YUV_MATRICES)}")
+        return _lib.YUV_MATRICES[matrix.lower()]
+    return int(matrix)
+
+
+def yuv_to_rgb(y, u, v, matrix="bt601"):
+    """ore_yuv_to_rgb (host only): uint8 arrays y, u, v of one shape -> uint8 [..., 3] of R, G, B, by the integer
+    conversion the NV12 kernels use (include/ore.h has the formula and the three matrices)."""
+    y, u, v = (np.require(a, requirements="C") for a in (y, u, v))  # 0-d arrays stay 0-d
+    for name, a in (("y", y), ("u", u), ("v", v)):
+        if a.dtype != np.uint8:
+            raise OreError(1, f"{name}: expected uint8, got {a.dtype}")
+    if not y.shape == u.shape == v.shape:
+        raise OreError(1, f"y, u, v: shapes {y.shape}, {u.shape}, {v.shape} differ")
+    rgb = np.empty(y.shape + (3,), np.uint8)
+    vp = ctypes.c_void_p
+    check(load().ore_yuv_to_rgb(_yuv_matrix(matrix), y.ctypes.data_as(vp), u.ctypes.data_as(vp), v.ctypes.data_as(vp),
+                                y.size, rgb.ctypes.data_as(vp)))
+    return rgb
+
+
+def nv12_to_rgb(y_plane, uv_plane, matrix="bt601"):
+    """An NV12 frame on the host -- y_plane uint8 [Hs, Ws], uv_plane uint8 [ceil(Hs/2), ceil(Ws/2), 2] -> uint8
+    [Hs, Ws, 3]: pixel (r, j) takes the UV pair at (r >> 1, j >> 1) through yuv_to_rgb.  These are the bytes an
+    Nv12ImageList resizes: image i of one equals image i of an ImageList fed this array."""
+    y_plane, uv_plane = np.asarray(y_plane), np.asarray(uv_plane)
+    if y_plane.ndim != 2 or y_plane.size == 0:
+        raise OreError(1, f"y_plane: expected [Hs, Ws], got {y_plane.shape}")
+    hs, ws = y_plane.shape
+    if uv_plane.shape != ((hs + 1) // 2, (ws + 1) // 2, 2):
+        raise OreError(1, f"uv_plane: expected {((hs + 1) // 2, (ws + 1) // 2, 2)} for a {hs} x {ws} frame, got {uv_plane.shape}")
+    uv = uv_plane[np.arange(hs)[:, None] >> 1, np.arange(ws)[None, :] >> 1]
+    return yuv_to_rgb(y_plane, uv[..., 0], uv[..., 1], matrix)
+
+
+def _check_plane_u8(x, device: int, name: str):
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.uint8:
+        raise OreError(1, f"{name}: expected a uint8 CUDA tensor")
+    if x.device.index != device:
+        raise OreError(1, f"{name}: on cuda:{x.device.index}, the context is on cuda:{device}")
+
+
+def _check_frame_nv12(frame, device: int, name: str):
+    """One frame of an NV12 list, handed to the library as two raw device pointers with a pitch each (on the
+    pattern of _check_image_u8): y a torch.uint8 CUDA tensor [Hs, Ws] with unit column stride, uv one of
+    [ceil(Hs/2), ceil(Ws/2), 2] whose last two dims are dense; rows of neither overlap; views qualify."""
+    try:
+        y, uv = frame
+    except (TypeError, ValueError):
+        raise OreError(1, f"{name}: expected a (y, uv) pair of uint8 CUDA tensors") from None
+    _check_plane_u8(y, device, f"{name}.y")
+    _check_plane_u8(uv, device, f"{name}.uv")
+    if y.dim() != 2:
+        raise OreError(1, f"{name}.y: expected [Hs, Ws], got {tuple(y.shape)}")
+    hs, ws = (int(d) for d in y.shape)
+    if hs < 1 or ws < 1:
+        raise OreError(1, f"{name}.y: empty plane {tuple(y.shape)}")
+    hc, wc = (hs + 1) // 2, (ws + 1) // 2
+    if tuple(uv.shape) != (hc, wc, 2):
+        raise OreError(1, f"{name}.uv: expected {(hc, wc, 2)} for a {hs} x {ws} frame, got {tuple(uv.shape)}")
+    if y.stride(1) != 1 or y.stride(0) < ws:
+        raise OreError(1, f"{name}.y: strides {tuple(y.stride())}: expected a unit column stride and a row stride >= Ws")
+    if uv.stride(2) != 1 or uv.stride(1) != 2 or uv.stride(0) < 2 * wc:
+        raise OreError(1, f"{name}.uv: strides {tuple(uv.stride())}: expected dense pairs (2, 1) and a row stride >= 2 * ceil(Ws / 2)")
+    return y, uv, hs, ws
+
+
+class Nv12ImageList(ImageList):
+    """An ore_image_list of NV12 frames (ore_image_list_create_nv12): what a video decoder leaves -- a Y plane and a
+    half-resolution plane of (U, V) pairs, each with its own pitch -- resized, cropped and normalised in ONE launch
+    with the colour conversion inside it.  Image i is bit for bit image i of an ImageList fed nv12_to_rgb of the
+    frame.  Three channels (R, G, B); the matrix ("bt601", "bt709", "bt601_full") and the filter are properties of
+    the list.  Model.run_u8_list, classify_u8_list and the captures take it as they take an ImageList."""
+
+    def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601", antialias: bool = False):
+        h, w = (int(v) for v in out_hw)
+        self.ctx = ctx
+        self.capacity = int(capacity)
+        self.out_hw = (h, w)
+        self.channels = 3
+        self.antialias = bool(antialias)
+        self.matrix = _yuv_matrix(matrix)
+        self._images = ()
+        self.h = None
+        hnd = ctypes.c_void_p()
+        check(load().ore_image_list_create_nv12(ctx.h, self.capacity, h, w, _filter(antialias), self.matrix,
+                                                ctypes.byref(hnd)), ctx.h)
+        self.h = hnd
+
+    def _descriptors(self, frames, geometries, short):
+        """The host checks of set(): the ore_image_nv12 array of `frames`, before any library call."""
+        if geometries is not None and short is not None:
+            raise OreError(1, "set: pass geometries or short, not both")
+        frames = list(frames)
+        if len(frames) > self.capacity:
+            raise OreError(1, f"set: {len(frames)} frames exceed the list's capacity {self.capacity}")
+        if geometries is not None and len(geometries) != len(frames):
+            raise OreError(1, f"set: {len(geometries)} geometries for {len(frames)} frames")
+        arr = (_lib.ImageNv12 * max(len(frames), 1))()
+        for i, f in enumerate(frames):
+            y, uv, hs, ws = _check_frame_nv12(f, self.ctx.device, f"frames[{i}]")
+            if geometries is not None:
+                resized, origin = geometries[i]
+            elif short is not None:
+                resized, origin = center_crop_geometry((hs, ws), short, self.out_hw)
+            else:
+                resized, origin = None, (0, 0)
+            arr[i].y, arr[i].uv = y.data_ptr(), uv.data_ptr()
+            arr[i].hs, arr[i].ws = hs, ws
+            arr[i].y_stride, arr[i].uv_stride = int(y.stride(0)), int(uv.stride(0))
+            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]")
+        return frames, arr
+
+    def set(self, frames, geometries=None, short=None):
+        """ore_image_list_set_nv12: frames is a sequence of (y, uv) pairs of uint8 CUDA tensors, y [Hs, Ws] and uv
+        [ceil(Hs/2), ceil(Ws/2), 2], views included: the pitches are the tensors' row strides.  A window of a
+        larger frame must start at an even row and column (y[y0:, x0:] with uv[y0 // 2:, x0 // 2:]).  Geometry,
+        ordering and what a rejected set leaves behind are ImageList.set's."""
+        frames, arr = self._descriptors(frames, geometries, short)
+        check(load().ore_image_list_set_nv12(self.h, arr, len(frames)), self.ctx.h)
+        self._images = tuple(frames)
+        return self
 
 
 def preprocess_list_u8(ctx: Context, lst: ImageList, scale=None, shift=None, reverse_channels: bool = False):
