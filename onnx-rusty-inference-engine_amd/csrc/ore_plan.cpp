@@ -36,12 +36,13 @@ bool strided_writer(const Step& s) { return s.kind == S_CONV || s.kind == S_FIRE
 
 // step geometry, each spelled once; the passes add their own extras (Relu, precision, channel limits)
 bool same_plane(const Step& s) { return s.win.Ho == s.H && s.win.Wo == s.W; }
-// a 1x1 / stride-1 conv window with no top / left pad ...
-bool window_1x1_s1(const Step& s) {
-  return s.kind == S_CONV && s.kh == 1 && s.kw == 1 && s.sh == 1 && s.sw == 1 && s.win.pt == 0 && s.win.pl == 0;
+// a 1x1 / stride-1 conv without pads on any side: the output plane is the input plane.  Every pass that takes a
+// 1x1 conv into another kernel needs all of it: with bottom / right pads alone the output is a larger plane
+// whose pad rows and columns hold relu(bias), which none of the fused kernels writes
+bool conv_1x1_s1(const Step& s) {
+  return s.kind == S_CONV && s.kh == 1 && s.kw == 1 && s.sh == 1 && s.sw == 1 && s.win.pt == 0 && s.win.pl == 0 &&
+         same_plane(s);
 }
-// ... and none below / right either: the output plane is the input plane
-bool conv_1x1_s1(const Step& s) { return window_1x1_s1(s) && same_plane(s); }
 bool conv_3x3_same(const Step& s) {
   return s.kind == S_CONV && s.kh == 3 && s.kw == 3 && s.sh == 1 && s.sw == 1 && s.win.pt == 1 && s.win.pl == 1 &&
          same_plane(s);
@@ -221,7 +222,7 @@ struct Planner {
   // MaxPool step pl (3x3 / stride 2, f32 NCHW input) feeding 1x1 conv cv fits pool_conv1x1_f32_kernel
   bool pool_squeeze_fits(const Step& pl, const Step& cv) const {
     if (!pool_3x3_s2(pl) || m->values[pl.in0].es != 4 || m->values[pl.in0].nhwc) return false;
-    if (!window_1x1_s1(cv) || !unfused(cv) || cv.plan.f16 || cv.plan.wino || cv.M > 64 || cv.C % 32 ||
+    if (!conv_1x1_s1(cv) || !unfused(cv) || cv.plan.f16 || cv.plan.wino || cv.M > 64 || cv.C % 32 ||
         pl.win.pt > 2 || pl.win.pl > 2)
       return false;
     // pool_conv1x1_f32_kernel's own limits (run_conv_pool has no other kernel)
@@ -466,7 +467,7 @@ struct Planner {
       const int qi = reader(cv.out, i + 1);
       if (qi < 0) continue;
       Step& q = st(qi);
-      if (!window_1x1_s1(q) || !q.relu || !unfused(q) || q.in0 != cv.out || q.C != cv.M || q.in2 < 0 || q.in1 < 0 ||
+      if (!conv_1x1_s1(q) || !q.relu || !unfused(q) || q.in0 != cv.out || q.C != cv.M || q.in2 < 0 || q.in1 < 0 ||
           !val(q.in1).cptr)
         continue;
       if (f16 ? (!q.plan.f16 || q.plan.xmode != F16_X_NHWC_VEC || q.M > 32 || q.M % 8) : (q.plan.f16 || q.M > 16))

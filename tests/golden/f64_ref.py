@@ -41,8 +41,11 @@ def _windows(xp, kh, kw, sh, sw, Ho, Wo):
     return cols
 
 
-def run(model_bytes, x):
-    """Run graph.output[0] in float64 on x (numpy [N, ...]); returns float64."""
+def run(model_bytes, x, intermediates=False, gap=None):
+    """Run graph.output[0] in float64 on x (numpy [N, ...]); returns float64 [N, elems].  With
+    intermediates=True returns (output, {value name: float64 array}) over every value the graph
+    computes (initializers excluded).  gap: a function replacing GlobalAveragePool's float64 mean
+    ([N, C, H, W] -> [N, C]), for references that reduce as a kernel does."""
     g = onnx_wire.decode_model(model_bytes).graph
     env = {t.name: t.to_numpy().astype(np.float64) if t.to_numpy().dtype != np.int64 else t.to_numpy()
            for t in g.initializer}
@@ -88,7 +91,10 @@ def run(model_bytes, x):
         elif op == "Dropout":
             y = ins[0]
         elif op == "GlobalAveragePool":
-            y = ins[0].mean(axis=(2, 3), keepdims=True)
+            if gap is not None:
+                y = np.asarray(gap(ins[0]), dtype=np.float64).reshape(ins[0].shape[:2] + (1, 1))
+            else:
+                y = ins[0].mean(axis=(2, 3), keepdims=True)
         elif op == "Softmax":
             z = ins[0].reshape(ins[0].shape[0], -1)
             z = np.exp(z - z.max(axis=1, keepdims=True))
@@ -110,4 +116,7 @@ def run(model_bytes, x):
             consts.add(n.output[0])
         env[n.output[0]] = y
     out = env[g.output[0].name]
-    return out.reshape(out.shape[0], -1)
+    out = out.reshape(out.shape[0], -1)
+    if intermediates:
+        return out, {o: env[o] for n in g.node for o in n.output}
+    return out
