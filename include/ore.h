@@ -368,6 +368,39 @@ int32_t ore_image_list_matrix(ore_image_list* l);
  * (a zero keeps its sign, a NaN its payload).  rows == 0 is ORE_OK and launches nothing; a null argument
  * or a k out of range is ORE_ERR_INVALID, checked before any device call. */
 ore_status ore_topk_f32(ore_ctx* ctx, const ore_tensor* x, int32_t k, float* values, int32_t* indices);
+/* Several views of one subject (extension): mirrored images in image lists, and the top-k of
+ * the mean of every `views` consecutive rows -- the five / ten-crop evaluation protocol, or the frames of a clip.
+ *  ore_image_list_set_ex / _set_nv12_ex: ore_image_list_set / _set_nv12 with one flag word per descriptor.
+ *    flags is a HOST array of n words, read before the call returns; NULL means all zero, and the call is then
+ *    ore_image_list_set / _set_nv12 exactly.  A bit other than ORE_IMAGE_FLIP_H is ORE_ERR_INVALID with the
+ *    descriptor's index in the message, and the list keeps its previous content, as for every rejected set.
+ *    Everything else is ore_image_list_set's: the descriptors are checked first, the upload is stream-ordered
+ *    from the pinned mirror, a set inside a capture or on a list of the other format is ORE_ERR_INVALID, and
+ *    n == 0 empties the list.  ore_image_u8 and ore_image_nv12 are unchanged.
+ *  ORE_IMAGE_FLIP_H: a horizontal mirror, defined by the unflipped result: output element (ch, r, q) of a
+ *    flipped descriptor is, bit for bit, output element (ch, r, W-1-q) of the same descriptor without the flag.
+ *    It is the mirror of the window at (top, left) of the resized image, NOT a resize of the mirrored source: the
+ *    two differ in the last bits, because a tap weight t and its mirror image 1 - t do not round alike.  (The
+ *    window of the mirrored image at column `left` is this flag with left' = rw - W - left.)  It holds for both
+ *    filters, interleaved c = 1..4 and NV12 under every matrix, ORE_PRE_REVERSE_CHANNELS and y given as a
+ *    slice; flipped image i of an NV12 list equals what a flipped interleaved list gives for the converted bytes.
+ *    The dense entries (ore_preprocess_resize_u8*, ore_model_set_input_resize*) have no flip.
+ *  ore_topk_mean_f32: ore_topk_f32 over the mean rows of groups of `views` consecutive rows.  x is [rows, D] as
+ *    there (nstride >= D honoured), 1 <= views <= ORE_MAX_VIEWS, rows % views == 0; values and indices are
+ *    contiguous DEVICE arrays [rows / views, k], 1 <= k <= min(D, 64).  All of this is checked from the arguments
+ *    alone, before the context and any device call (ORE_ERR_INVALID, the message names views or k); rows == 0 is
+ *    ORE_OK and launches nothing.  Element i of group g's mean:
+ *        acc = x[gV, i];  for v = 1 .. V-1: acc = fadd_rn(acc, x[gV+v, i]);  m_i = fdiv_rn(acc, (float)V)
+ *    in ascending view order, every operation rounded on its own, IEEE division, subnormals kept: numpy float32
+ *    arrays reproduce m bit for bit.  The selection is ore_topk_f32's order applied to m; values[g,j] is a bit
+ *    copy of m at indices[g,j] (a zero keeps its sign).  A NaN mean ranks as a NaN, after every number, by
+ *    index; its payload is unspecified.  views == 1 is ore_topk_f32 itself (NaN payloads kept).  One launch, one
+ *    wavefront per group. */
+#define ORE_IMAGE_FLIP_H 1u
+#define ORE_MAX_VIEWS 64
+ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, int64_t n);
+ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, int64_t n);
+ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, int32_t k, float* values, int32_t* indices);
 
 /* ------------------------------------------------------------------ graph walker (inference()) */
 /* Parse an ONNX ModelProto (bytes), upload every initializer to HBM once, plan the value
@@ -594,6 +627,15 @@ ore_status ore_model_run_u8_list(ore_model* m, ore_image_list* l, float* d_outpu
 ore_status ore_model_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes);
 ore_status ore_model_graph_capture_u8_list(ore_model* m, ore_image_list* l, float* d_output);
 ore_status ore_model_graph_capture_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes);
+/* Views (extension, see ore_topk_mean_f32): after ore_model_set_views(m, V) every classify entry --
+ * ore_model_classify, _classify_u8, _classify_u8_list and the three _graph_capture_classify* -- treats
+ * consecutive runs of V images as one subject: the selection is ore_topk_mean_f32 over the rows, and d_scores /
+ * d_classes are [n / V, k].  1 <= V <= min(ORE_MAX_VIEWS, run_batch), default 1; n (or the list's count) must be
+ * a multiple of V (ORE_ERR_INVALID otherwise).  ore_model_run* and the full-row outputs ignore the setting; a
+ * captured graph keeps the V it was captured with.  Chunks hold whole groups: with G = n / V and gb = run_batch
+ * / V there are ceil(G / gb) chunks of ceil(G / nchunks) groups each, chunk c writing rows [g0, g0 + gc) -- at
+ * V == 1 the arithmetic of ore_model_run.  Buffers, timing events and the step list are unchanged. */
+ore_status ore_model_set_views(ore_model* m, int32_t views);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);
 int32_t ore_model_step_count(ore_model* m);
 ore_status ore_model_step_info(ore_model* m, int32_t i, const char** op, const char** name, double* flops,

@@ -34,4 +34,17 @@ struct Chunk {
 };
 inline Chunk chunk_at(int64_t i0, int64_t N, int64_t nb) { return {i0, std::max<int64_t>(0, std::min(nb, N - i0))}; }
 
+// The model's passes over n images, run_batch at the most in each, in whole groups of `views` consecutive images
+// (ore_model_set_views; n a multiple of views, 1 <= views <= run_batch): with G = n / views groups and gb =
+// run_batch / views groups per pass, ceil(G / gb) equal chunks of ceil(G / nchunks) groups.  chunk is in images;
+// walk it with chunk_at(i0, n, chunk).  At views == 1: equal chunks of consecutive images, at most run_batch each.
+struct GroupChunks {
+  int64_t nchunks, chunk;
+};
+inline GroupChunks group_chunks(int64_t n, int64_t run_batch, int64_t views) {
+  const int64_t G = n / views, gb = run_batch / views;
+  const int64_t nchunks = G > gb ? (G + gb - 1) / gb : 1;
+  return {nchunks, (G + nchunks - 1) / nchunks * views};
+}
+
 }  // namespace ore

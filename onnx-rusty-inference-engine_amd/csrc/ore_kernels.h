@@ -469,8 +469,8 @@ struct ResizeImage {
   int Hs, Ws;              // <= RESIZE_MAX
   int row;                 // bytes between rows, >= Ws * C; (Hs - 1) * row + Ws * C < 2^31
   int Rh, Rw, top, left;
-  int pad_;                // 40 bytes: an 8-byte multiple, so the pointers of a table stay aligned
-};
+  int flip;                // ORE_IMAGE_FLIP_H or 0: output column q shows resized column left + W - 1 - q
+};                         // 40 bytes: an 8-byte multiple, so the pointers of a table stay aligned
 struct ResizeListParams {
   const ResizeImage* table;  // image i of the launch is table[first + i]
   long long first;
@@ -480,6 +480,7 @@ struct ResizeListParams {
   int C, H, W;
   int plane[4];
   float scale[4], shift[4];
+  int flips;                 // 0: no descriptor of the launch is flipped, the flag-free instance of the kernel runs
 };
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s);
 // the same two conversions under ORE_FILTER_BILINEAR_AA: axes that shrink take the area-weighted filter of
@@ -497,7 +498,8 @@ struct Nv12Image {
   const unsigned char* uv;  // row 0, pair 0 of the UV plane; any alignment
   int Hs, Ws;               // <= RESIZE_MAX; the UV plane has ceil(Hs / 2) rows of ceil(Ws / 2) pairs
   int yrow, uvrow;          // bytes between rows of each plane; offsets inside a plane stay below 2^31
-  int Rh, Rw, top, left;    // 48 bytes: an 8-byte multiple
+  int Rh, Rw, top, left;
+  int flip, pad_;           // flip as in ResizeImage; 56 bytes: an 8-byte multiple
 };
 struct Nv12ListParams {
   const Nv12Image* table;  // image i of the launch is table[first + i]
@@ -509,6 +511,7 @@ struct Nv12ListParams {
   YuvMatrix m;
   int plane[3];            // indexed by R, G, B as ResizeListParams is by source channel
   float scale[3], shift[3];
+  int flips;               // as ResizeListParams::flips
 };
 void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s);
 void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s);
@@ -516,5 +519,9 @@ void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s);
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,
                  hipStream_t s);
+// view-mean top-k: group g is rows [g V, (g + 1) V) of x; the selection runs over their mean row (summed in
+// ascending row order, one IEEE division by V); values / indices are contiguous [groups][k].  V == 1 is launch_topk.
+void launch_topk_mean(const float* x, long long stride, long long groups, int V, int D, int k, float* values,
+                      int* indices, hipStream_t s);
 
 }  // namespace ore

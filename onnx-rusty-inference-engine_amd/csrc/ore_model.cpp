@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "ore_chunk.h"
 #include "ore_model_types.h"
 
 using namespace ore;
@@ -898,17 +899,31 @@ static ore_status check_run_args(ore_model* m, const void* d_input, int64_t n, f
   return ORE_OK;
 }
 
-// the classify entries' checks: check_run_args with two outputs
+// the classify entries' rule for n images under ore_model_set_views: whole groups (plan() may have lowered
+// run_batch since the views were set)
+static ore_status check_views(ore_model* m, int64_t n) {
+  if (m->views > m->run_batch)
+    return set_error(m->ctx, ORE_ERR_INVALID, "views = %d exceed the run batch %lld: call ore_model_set_views again", int(m->views),
+                     (long long)m->run_batch);
+  if (n % m->views != 0)
+    return set_error(m->ctx, ORE_ERR_INVALID, "%lld images are not a multiple of views = %d", (long long)n, int(m->views));
+  return ORE_OK;
+}
+
+// the classify entries' checks: check_run_args with two outputs, and whole groups of views
 static ore_status check_classify_args(ore_model* m, const void* d_input, int64_t n, float* d_scores, int32_t* d_classes) {
   if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
-  return check_run_args(m, d_input, n, d_scores);
+  if (ore_status st = check_run_args(m, d_input, n, d_scores)) return st;
+  return check_views(m, n);
 }
 
 // ore_model_run, ore_model_run_u8 and the classify entries: the graph over n images, in chunks of at most
 // run_batch.  With d_u8 the input is the uint8 NHWC batch: each chunk is converted into the staging buffer
 // (ensure_stage), then run.  With d_classes each chunk's output stays on the model's side (the rows buffer of
 // ensure_rows, or the arena where the output value lives there) and its m->topk best per image go to rows
-// [i0, i0 + nc) of d_output (the scores) and d_classes, both [n, topk].  With lst the input is an image list
+// [i0, i0 + nc) of d_output (the scores) and d_classes, both [n, topk] -- under ore_model_set_views the best of
+// the mean of every `views` consecutive rows, to rows [i0 / views, (i0 + nc) / views) of [n / views, topk], the
+// chunks holding whole groups.  With lst the input is an image list
 // of n descriptors (check_list_args): chunk i0 converts descriptors [i0, i0 + nc) into the staging buffer.
 static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* d_u8, int64_t n, float* d_output,
                              int32_t* d_classes = nullptr, ore_image_list* lst = nullptr) {
@@ -940,8 +955,10 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
   m->out_bound = ov.alias_of < 0 && !ov.elided;
   // n > run_batch: equal chunks of consecutive images, at most run_batch each (every image's
   // arithmetic is independent of the batch it runs in)
-  const int64_t nchunks = n > m->run_batch ? (n + m->run_batch - 1) / m->run_batch : 1;
-  const int64_t chunk = (n + nchunks - 1) / nchunks;
+  // the classify entries keep the groups of ore_model_set_views whole (group_chunks; the same arithmetic at 1)
+  const int64_t views = d_classes ? m->views : 1;
+  const GroupChunks gc = group_chunks(n, m->run_batch, views);
+  const int64_t nchunks = gc.nchunks, chunk = gc.chunk;
   m->last_chunked = nchunks > 1;
   const size_t nev = m->exec_steps.size() + 1;
   if (m->timing && m->events.size() < nev * size_t(nchunks)) {
@@ -984,7 +1001,9 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
       return st;
     if (d_classes) {  // after the pass's last timing event: not an exec step
       const Ref r = ref_of(m, m->output_value);
-      launch_topk(r.p, r.nstride, nc, int(out_img), m->topk, d_output + i0 * m->topk, d_classes + i0 * m->topk, ctx->stream);
+      const int64_t g0 = i0 / views;  // the chunk's nc / views groups go to rows [g0, g0 + nc / views)
+      launch_topk_mean(r.p, r.nstride, nc / views, int(views), int(out_img), m->topk, d_output + g0 * m->topk,
+                       d_classes + g0 * m->topk, ctx->stream);
       ORE_HIP_CHECK(ctx, hipGetLastError());
     }
   }
@@ -1053,6 +1072,15 @@ ore_status ore_model_set_topk(ore_model* m, int32_t k) {
   return ORE_OK;
 }
 
+ore_status ore_model_set_views(ore_model* m, int32_t views) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  const int64_t vmax = std::min<int64_t>(ORE_MAX_VIEWS, m->run_batch);
+  if (views < 1 || views > vmax)
+    return set_error(m->ctx, ORE_ERR_INVALID, "views = %d outside 1..%lld (min(ORE_MAX_VIEWS, run batch))", int(views), (long long)vmax);
+  m->views = views;
+  return ORE_OK;
+}
+
 ore_status ore_model_classify(ore_model* m, const float* d_input, int64_t n, float* d_scores, int32_t* d_classes) {
   if (ore_status st = check_classify_args(m, d_input, n, d_scores, d_classes)) return st;
   if (n == 0) return ORE_OK;
@@ -1089,6 +1117,7 @@ ore_status ore_model_run_u8_list(ore_model* m, ore_image_list* l, float* d_outpu
 ore_status ore_model_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes) {
   if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
   if (ore_status st = check_list_args(m, l, d_scores)) return st;
+  if (ore_status st = check_views(m, l->count)) return st;
   if (l->count == 0) return ORE_OK;
   if (ore_status st = ensure_stage(m)) return st;
   if (ore_status st = ensure_rows(m)) return st;
@@ -1331,6 +1360,7 @@ ore_status ore_model_graph_capture_u8_list(ore_model* m, ore_image_list* l, floa
 ore_status ore_model_graph_capture_classify_u8_list(ore_model* m, ore_image_list* l, float* d_scores, int32_t* d_classes) {
   if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
   if (ore_status st = check_list_args(m, l, d_scores)) return st;
+  if (ore_status st = check_views(m, l->count)) return st;
   return capture_run(m, nullptr, nullptr, l->count, d_scores, d_classes, l);
 }
 

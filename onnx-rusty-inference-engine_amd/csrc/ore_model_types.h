@@ -195,6 +195,7 @@ struct ore_model {
   float* rows = nullptr;
   size_t rows_bytes = 0;
   int32_t topk = 1;
+  int32_t views = 1;  // ore_model_set_views: the classify entries select over the mean of this many consecutive rows
 };
 
 namespace ore {

@@ -204,12 +204,19 @@ ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale
   return ORE_OK;
 }
 
-void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& p) {
+void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& p0) {
+  // The flag-free instance of the kernel when no descriptor of the list is flipped.  Not inside a stream capture:
+  // a captured graph reads at replay whatever table a later set uploaded, flags included.
+  ResizeListParams p = p0;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool capturing = ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  p.flips = l->any_flip || capturing;
   if (l->format == ORE_IMAGE_NV12) {
     Nv12ListParams q{};
     q.table = l->table_nv12;
     q.first = p.first; q.y = p.y; q.N = p.N; q.y_nstride = p.y_nstride;
     q.H = p.H; q.W = p.W;
+    q.flips = p.flips;
     yuv_matrix(l->matrix, &q.m);  // checked at creation
     for (int s = 0; s < 3; ++s) {
       q.plane[s] = p.plane[s];
@@ -847,6 +854,10 @@ ore_status ore_softmax_f32(ore_ctx* ctx, const ore_tensor* x, ore_tensor* y) {
 }
 
 ore_status ore_topk_f32(ore_ctx* ctx, const ore_tensor* x, int32_t k, float* values, int32_t* indices) {
+  return ore_topk_mean_f32(ctx, x, 1, k, values, indices);  // one view: launch_topk_mean hands it to launch_topk
+}
+
+ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, int32_t k, float* values, int32_t* indices) {
   // the context last: what can be judged without one is (a null context still gets the message)
   if (!x || !x->data || !values || !indices) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (x->ndim < 1 || x->ndim > 4) return set_error(ctx, ORE_ERR_INVALID, "top-k input of %d dims", int(x->ndim));
@@ -854,13 +865,17 @@ ore_status ore_topk_f32(ore_ctx* ctx, const ore_tensor* x, int32_t k, float* val
   int64_t D = 1;
   for (int i = 1; i < x->ndim; ++i) D *= x->dims[i];
   if (rows < 0 || D <= 0 || !fits_i32(D) || nstride_of(x) < D) return set_error(ctx, ORE_ERR_INVALID, "top-k row length");
+  if (views < 1 || views > ORE_MAX_VIEWS)
+    return set_error(ctx, ORE_ERR_INVALID, "top-k views = %d outside 1..%d (ORE_MAX_VIEWS)", int(views), ORE_MAX_VIEWS);
+  if (rows % views != 0)
+    return set_error(ctx, ORE_ERR_INVALID, "top-k of %lld rows: not a multiple of views = %d", (long long)rows, int(views));
   if (k < 1 || k > std::min<int64_t>(D, 64))
     return set_error(ctx, ORE_ERR_INVALID, "top-k k = %d outside 1..%lld (min(row length, 64))", int(k),
                      (long long)std::min<int64_t>(D, 64));
   if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (rows == 0) return ORE_OK;
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  launch_topk(x->data, nstride_of(x), rows, int(D), int(k), values, indices, ctx->stream);
+  launch_topk_mean(x->data, nstride_of(x), rows / views, int(views), int(D), int(k), values, indices, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }
@@ -1201,7 +1216,20 @@ static ore_status list_set_begin(ore_image_list* l, int64_t n) {
   return ORE_OK;
 }
 
+// the per-descriptor flag words of the _ex sets (null: all zero): ORE_IMAGE_FLIP_H is the only bit
+static ore_status list_check_flags(ore_ctx* ctx, const uint32_t* flags, int64_t n) {
+  for (int64_t i = 0; flags && i < n; ++i)
+    if (flags[i] & ~uint32_t(ORE_IMAGE_FLIP_H))
+      return set_error(ctx, ORE_ERR_INVALID, "image %lld: unknown flag bits 0x%x (ORE_IMAGE_FLIP_H is the only one)", (long long)i,
+                       unsigned(flags[i] & ~uint32_t(ORE_IMAGE_FLIP_H)));
+  return ORE_OK;
+}
+
 ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs, int64_t n) {
+  return ore_image_list_set_nv12_ex(l, imgs, nullptr, n);
+}
+
+ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, int64_t n) {
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
   if (l->format != ORE_IMAGE_NV12)
@@ -1211,8 +1239,10 @@ ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs
     ctx->err = ore_last_error(nullptr);
     return ORE_ERR_INVALID;
   }
+  if (ore_status st = list_check_flags(ctx, flags, n)) return st;
   if (ore_status st = list_set_begin(l, n)) return st;
   if (n == 0) return ORE_OK;
+  bool any_flip = false;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_nv12& d = imgs[i];
     const int64_t hc = (d.hs + 1) / 2, wc = (d.ws + 1) / 2;
@@ -1223,14 +1253,21 @@ ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs
     r.yrow = int(d.hs > 1 && d.y_stride ? d.y_stride : d.ws);  // dense where 0, and where no row is ever stepped
     r.uvrow = int(hc > 1 && d.uv_stride ? d.uv_stride : 2 * wc);
     r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
+    r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
+    any_flip |= r.flip != 0;
   }
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_nv12, l->mirror_nv12, size_t(n) * sizeof(Nv12Image), hipMemcpyHostToDevice, ctx->stream));
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
+  l->any_flip = any_flip;
   return ORE_OK;
 }
 
 ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n) {
+  return ore_image_list_set_ex(l, imgs, nullptr, n);
+}
+
+ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, int64_t n) {
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
   if (l->format != ORE_IMAGE_INTERLEAVED)
@@ -1240,8 +1277,10 @@ ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64
     ctx->err = ore_last_error(nullptr);
     return ORE_ERR_INVALID;
   }
+  if (ore_status st = list_check_flags(ctx, flags, n)) return st;
   if (ore_status st = list_set_begin(l, n)) return st;
   if (n == 0) return ORE_OK;
+  bool any_flip = false;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_u8& d = imgs[i];
     ResizeImage& r = l->mirror[i];
@@ -1250,11 +1289,14 @@ ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64
     r.Hs = int(d.hs); r.Ws = int(d.ws);
     r.row = int(d.hs > 1 && d.row_stride ? d.row_stride : d.ws * l->c);  // dense where 0, and where no row is ever stepped
     r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
+    r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
+    any_flip |= r.flip != 0;
   }
   // stream-ordered: launches submitted earlier read the old table, later ones the new
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table, l->mirror, size_t(n) * sizeof(ResizeImage), hipMemcpyHostToDevice, ctx->stream));
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
+  l->any_flip = any_flip;
   return ORE_OK;
 }
 

@@ -64,6 +64,18 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_generic_kernel(ResizePar
 // lives in SGPRs; the taps, which the dense kernel computes once per thread, are computed per image (one
 // image per thread unless the list passes the grid's 65,535).  Every output pixel costs the same work
 // whatever its source size, so mixed sizes bring no load imbalance.
+//
+// A descriptor's flip (ORE_IMAGE_FLIP_H, ore_image_list_set_ex) mirrors its window: output column q takes resized
+// column left + W - 1 - q, the store position stays q, so the image is the unflipped one with its columns
+// reversed, bit for bit.  The flag comes with the descriptor: wave-uniform, one scalar select per image.  Each
+// list kernel exists twice: FLIP reads the flag; the other instance does not, and is the one launched when no
+// descriptor of the list is flipped (ResizeListParams::flips), so that such a launch pays nothing for the feature.
+template <bool FLIP>
+__device__ __forceinline__ int list_column(int flip, int W, int q) {
+  return FLIP && flip ? W - 1 - q : q;
+}
+
+template <bool FLIP>
 __global__ __launch_bounds__(RS_THREADS) void resize_u8_list_kernel(const ResizeImage* __restrict__ table,
                                                                     ResizeListParams p) {
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
@@ -73,7 +85,7 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_list_kernel(const Resize
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
     const ResizeImage d = table[i];
     const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
+    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_column<FLIP>(d.flip, p.W, q));
     const size_t r0 = size_t(ty.i0) * size_t(d.row), r1 = size_t(ty.i1) * size_t(d.row);
     const size_t c0 = size_t(tx.i0) * p.C, c1 = size_t(tx.i1) * p.C;
     const unsigned char* xi = d.x;
@@ -278,9 +290,10 @@ __device__ __forceinline__ void aa_src_row(const AaNv12& d, int r, bool sx, cons
   aa_row_nv12(d, r, sx, ax, ox, g);
 }
 
-// one output pixel (r, q) of image d (AaImage: interleaved bytes; AaNv12) from global memory
+// output pixel px of image d (AaImage: interleaved bytes; AaNv12) from global memory: row r and column q of the
+// window (q is not px's column where a list descriptor is flipped)
 template <int C, class D, class P>
-__device__ __forceinline__ void aa_pixel(const D& d, const P& p, float* __restrict__ yi, int HW, int W, int r, int q) {
+__device__ __forceinline__ void aa_pixel(const D& d, const P& p, float* __restrict__ yi, int HW, int px, int r, int q) {
   const bool sx = d.Ws > d.Rw, sy = d.Hs > d.Rh;
   const int oy = d.top + r, ox = d.left + q;
   const AaAxis ax = aa_axis(sx, d.Ws, d.Rw, ox);
@@ -306,7 +319,7 @@ __device__ __forceinline__ void aa_pixel(const D& d, const P& p, float* __restri
 #pragma unroll
     for (int s = 0; s < C; ++s) w[s] = lerp_rn(g0[s], g1[s], ay.t);
   }
-  aa_store<C>(p, yi, HW, r * W + q, sx, ax.sum, w);
+  aa_store<C>(p, yi, HW, px, sx, ax.sum, w);
 }
 
 __device__ __forceinline__ AaImage aa_image(const ResizeParams& p, long long i) {
@@ -333,11 +346,11 @@ __global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_kernel(ResizeParam
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
-    aa_pixel<C>(aa_image(p, i), p, p.y + size_t(i) * size_t(p.y_nstride), HW, p.W, r, q);
+    aa_pixel<C>(aa_image(p, i), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, q);
 }
 
 // the list descriptor is one scalar load per workgroup, as in resize_u8_list_kernel
-template <int C>
+template <int C, bool FLIP>
 __global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_list_kernel(const ResizeImage* __restrict__ table,
                                                                           ResizeListParams p) {
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
@@ -345,11 +358,12 @@ __global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_list_kernel(const 
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
-    aa_pixel<C>(aa_image(table[i]), p, p.y + size_t(i) * size_t(p.y_nstride), HW, p.W, r, q);
+    aa_pixel<C>(aa_image(table[i]), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, list_column<FLIP>(table[i].flip, p.W, q));
 }
 
 // the NV12 list kernels: resize_u8_list_kernel and resize_aa_pixel_list_kernel<3> over converted pixels; the
 // descriptor is one scalar load per workgroup as there
+template <bool FLIP>
 __global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
   const int HW = p.H * p.W;
@@ -358,7 +372,7 @@ __global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
     const Nv12Image d = table[i];
     const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
+    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_column<FLIP>(d.flip, p.W, q));
     const unsigned char* y0 = d.y + size_t(ty.i0) * size_t(d.yrow);
     const unsigned char* y1 = d.y + size_t(ty.i1) * size_t(d.yrow);
     const unsigned char* u0 = d.uv + size_t(ty.i0 >> 1) * size_t(d.uvrow);
@@ -378,13 +392,14 @@ __global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12
   }
 }
 
+template <bool FLIP>
 __global__ __launch_bounds__(RS_THREADS) void resize_aa_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
-    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, p.W, r, q);
+    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, list_column<FLIP>(table[i].flip, p.W, q));
 }
 
 template <class K, class... A>
@@ -412,11 +427,19 @@ void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s) {
   const ResizeImage* table = p.table + p.first;
   const long long hw = (long long)p.H * p.W;
   const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  if (p.flips) {
+    switch (p.C) {
+      case 1: return aa_launch(resize_aa_pixel_list_kernel<1, true>, grid, s, table, p);
+      case 2: return aa_launch(resize_aa_pixel_list_kernel<2, true>, grid, s, table, p);
+      case 3: return aa_launch(resize_aa_pixel_list_kernel<3, true>, grid, s, table, p);
+      default: return aa_launch(resize_aa_pixel_list_kernel<4, true>, grid, s, table, p);
+    }
+  }
   switch (p.C) {
-    case 1: return aa_launch(resize_aa_pixel_list_kernel<1>, grid, s, table, p);
-    case 2: return aa_launch(resize_aa_pixel_list_kernel<2>, grid, s, table, p);
-    case 3: return aa_launch(resize_aa_pixel_list_kernel<3>, grid, s, table, p);
-    default: return aa_launch(resize_aa_pixel_list_kernel<4>, grid, s, table, p);
+    case 1: return aa_launch(resize_aa_pixel_list_kernel<1, false>, grid, s, table, p);
+    case 2: return aa_launch(resize_aa_pixel_list_kernel<2, false>, grid, s, table, p);
+    case 3: return aa_launch(resize_aa_pixel_list_kernel<3, false>, grid, s, table, p);
+    default: return aa_launch(resize_aa_pixel_list_kernel<4, false>, grid, s, table, p);
   }
 }
 
@@ -424,22 +447,22 @@ void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
   const long long hw = (long long)p.H * p.W;
   const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
-  aa_launch(resize_nv12_list_kernel, grid, s, p.table + p.first, p);
+  aa_launch(p.flips ? resize_nv12_list_kernel<true> : resize_nv12_list_kernel<false>, grid, s, p.table + p.first, p);
 }
 
 void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
   const long long hw = (long long)p.H * p.W;
   const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
-  aa_launch(resize_aa_nv12_list_kernel, grid, s, p.table + p.first, p);
+  aa_launch(p.flips ? resize_aa_nv12_list_kernel<true> : resize_aa_nv12_list_kernel<false>, grid, s, p.table + p.first, p);
 }
 
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
   const unsigned gy = unsigned(p.N < 65535 ? p.N : 65535);
   const long long hw = (long long)p.H * p.W;
-  hipLaunchKernelGGL(resize_u8_list_kernel, dim3(unsigned((hw + RS_THREADS - 1) / RS_THREADS), gy), dim3(RS_THREADS), 0, s,
-                     p.table + p.first, p);
+  aa_launch(p.flips ? resize_u8_list_kernel<true> : resize_u8_list_kernel<false>,
+            dim3(unsigned((hw + RS_THREADS - 1) / RS_THREADS), gy), s, p.table + p.first, p);
 }
 
 void launch_resize_u8(const ResizeParams& p, hipStream_t s) {

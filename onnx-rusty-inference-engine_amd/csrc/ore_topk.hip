@@ -17,6 +17,18 @@
 // x[index]: the sign of a zero and a NaN's payload survive.
 //  * topk_kernel<NE>: D <= 64 NE, the keys stay in registers (one read of the row); NE = 4 and 16.
 //  * topk_long_kernel: any D; every round re-reads the row (it stays in cache) and rebuilds the keys.
+//
+// View-mean top-k (extension, ore_topk_mean_f32 / ore_model_set_views): rows come in groups of V consecutive
+// rows (the views of one subject); the selection runs over the mean row of each group, one wavefront per group.
+// Element i of group g is
+//     acc = x[gV, i];  for v = 1 .. V-1: acc = fadd_rn(acc, x[gV+v, i]);  m_i = fdiv_rn(acc, (float)V)
+// in ascending view order, every operation rounded on its own, division IEEE, subnormals kept: numpy float32
+// reproduces m bit for bit.  The keys are those of m; the stored value is m recomputed at the winning index by
+// the same chain (the same bits: the sign of a zero survives, a NaN mean ranks as a NaN).  V == 1 is launch_topk.
+//  * topk_mean_kernel<NE>: D <= 64 NE; V reads of the group's rows build the means, their keys stay in registers.
+//  * topk_mean_long_kernel: any D; every round recomputes the means, so it reads k V D elements per group where
+//    the register kernel reads V D (the rows stay in cache; at D = 4100, V = 10, k = 5 that is 50 reads and 45
+//    adds per element against 10 and 9).  Correctness over speed past D = 1024.
 #include <hip/hip_runtime.h>
 
 #include "ore_kernels.h"
@@ -78,6 +90,23 @@ __device__ __forceinline__ void topk_store(const unsigned* xr, u64 mine, int lan
   }
 }
 
+// the k rounds over keys held in registers; returns lane j's key of round j
+template <int NE>
+__device__ __forceinline__ u64 topk_rounds(const u64 (&key)[NE], int k, int lane) {
+  u64 prev = ~0ull, mine = 0ull;
+  for (int j = 0; j < k; ++j) {  // wave-uniform trip count
+    u64 best = 0ull;
+#pragma unroll
+    for (int t = 0; t < NE; ++t) {
+      const u64 c = key[t] < prev ? key[t] : 0ull;
+      best = c > best ? c : best;
+    }
+    prev = wave_max(best);
+    mine = lane == j ? prev : mine;
+  }
+  return mine;
+}
+
 template <int NE>  // elements per lane held in registers: D <= 64 NE
 __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ x, long long stride, long long rows,
                                                    int D, int k, float* __restrict__ values,
@@ -92,18 +121,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ x, 
     const int i = 64 * t + lane;
     key[t] = i < D ? topk_key(xr[i], i) : 0ull;
   }
-  u64 prev = ~0ull, mine = 0ull;
-  for (int j = 0; j < k; ++j) {  // wave-uniform trip count
-    u64 best = 0ull;
-#pragma unroll
-    for (int t = 0; t < NE; ++t) {
-      const u64 c = key[t] < prev ? key[t] : 0ull;
-      best = c > best ? c : best;
-    }
-    prev = wave_max(best);
-    mine = lane == j ? prev : mine;
-  }
-  topk_store(xr, mine, lane, k, row, values, indices);
+  topk_store(xr, topk_rounds<NE>(key, k, lane), lane, k, row, values, indices);
 }
 
 __global__ __launch_bounds__(256) void topk_long_kernel(const float* __restrict__ x, long long stride,
@@ -127,7 +145,98 @@ __global__ __launch_bounds__(256) void topk_long_kernel(const float* __restrict_
   topk_store(xr, mine, lane, k, row, values, indices);
 }
 
+// element i of the mean row of a group (xg: its first row)
+__device__ __forceinline__ float view_mean(const float* __restrict__ xg, long long stride, int V, float fv, int i) {
+#pragma clang fp contract(off)
+  float acc = xg[i];
+#pragma unroll 4  // the loads of four views in flight; the additions stay in view order
+  for (int v = 1; v < V; ++v) acc = acc + xg[v * stride + i];
+  return acc / fv;
+}
+
+// lane j < k holds output j's key: the value is the mean at its index, recomputed
+__device__ __forceinline__ void topk_mean_store(const float* xg, long long stride, int V, float fv, u64 mine, int lane,
+                                                int k, long long g, float* values, int* indices) {
+  if (lane < k && mine != 0ull) {
+    const int idx = int(~unsigned(mine));
+    values[g * k + lane] = view_mean(xg, stride, V, fv, idx);
+    indices[g * k + lane] = idx;
+  }
+}
+
+template <int NE>  // topk_kernel<NE> whose key build reads V rows
+__global__ __launch_bounds__(256) void topk_mean_kernel(const float* __restrict__ x, long long stride, long long groups,
+                                                        int V, int D, int k, float* __restrict__ values,
+                                                        int* __restrict__ indices) {
+  const int lane = threadIdx.x & 63;
+  const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= groups) return;  // wave-uniform; no barrier in this kernel
+  const float* xg = x + g * V * stride;
+  const float fv = float(V);
+  u64 key[NE];
+  {
+#pragma clang fp contract(off)
+    // the slots past D read element 0 (D >= 1) and are never used: every load is unconditional, no divergence
+    float acc[NE];
+#pragma unroll
+    for (int t = 0; t < NE; ++t) {
+      const int i = 64 * t + lane;
+      acc[t] = xg[i < D ? i : 0];
+    }
+#pragma unroll 2  // two views' loads in flight
+    for (int v = 1; v < V; ++v) {  // ascending view order; the NE chains of a lane are independent
+      const float* xv = xg + v * stride;
+#pragma unroll
+      for (int t = 0; t < NE; ++t) {
+        const int i = 64 * t + lane;
+        acc[t] = acc[t] + xv[i < D ? i : 0];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NE; ++t) {
+      const int i = 64 * t + lane;
+      key[t] = i < D ? topk_key(__float_as_uint(acc[t] / fv), i) : 0ull;
+    }
+  }
+  topk_mean_store(xg, stride, V, fv, topk_rounds<NE>(key, k, lane), lane, k, g, values, indices);
+}
+
+__global__ __launch_bounds__(256) void topk_mean_long_kernel(const float* __restrict__ x, long long stride,
+                                                             long long groups, int V, int D, int k,
+                                                             float* __restrict__ values, int* __restrict__ indices) {
+  const int lane = threadIdx.x & 63;
+  const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= groups) return;
+  const float* xg = x + g * V * stride;
+  const float fv = float(V);
+  u64 prev = ~0ull, mine = 0ull;
+  for (int j = 0; j < k; ++j) {
+    u64 best = 0ull;
+    for (int i = lane; i < D; i += 64) {
+      const u64 key = topk_key(__float_as_uint(view_mean(xg, stride, V, fv, i)), i);
+      const u64 c = key < prev ? key : 0ull;
+      best = c > best ? c : best;
+    }
+    prev = wave_max(best);
+    mine = lane == j ? prev : mine;
+  }
+  topk_mean_store(xg, stride, V, fv, mine, lane, k, g, values, indices);
+}
+
 }  // namespace
+
+void launch_topk_mean(const float* x, long long stride, long long groups, int V, int D, int k, float* values,
+                      int* indices, hipStream_t s) {
+  if (groups <= 0) return;
+  if (V == 1) return launch_topk(x, stride, groups, D, k, values, indices, s);
+  const dim3 grid((unsigned)((groups + 3) / 4));
+  if (D <= 256)
+    hipLaunchKernelGGL(topk_mean_kernel<4>, grid, dim3(256), 0, s, x, stride, groups, V, D, k, values, indices);
+  else if (D <= 1024)
+    hipLaunchKernelGGL(topk_mean_kernel<16>, grid, dim3(256), 0, s, x, stride, groups, V, D, k, values, indices);
+  else
+    hipLaunchKernelGGL(topk_mean_long_kernel, grid, dim3(256), 0, s, x, stride, groups, V, D, k, values, indices);
+}
 
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,
                  hipStream_t s) {

@@ -33,6 +33,8 @@ AA_MAX_RATIO, AA_MAX_TAPS = 32, 64  # ORE_AA_MAX_RATIO / ORE_AA_MAX_TAPS: the an
 YUV_BT601, YUV_BT709, YUV_BT601_FULL = 0, 1, 2  # ore_yuv_matrix (ore_yuv_to_rgb, the NV12 image lists)
 YUV_MATRICES = {"bt601": YUV_BT601, "bt709": YUV_BT709, "bt601_full": YUV_BT601_FULL}
 IMAGE_INTERLEAVED, IMAGE_NV12 = 0, 1  # ore_image_format (ore_image_list_format)
+IMAGE_FLIP_H = 1  # ORE_IMAGE_FLIP_H: the per-descriptor flag of ore_image_list_set_ex / _set_nv12_ex
+MAX_VIEWS = 64  # ORE_MAX_VIEWS (ore_topk_mean_f32, ore_model_set_views)
 PAD = {"NOTSET": 0, "NOT_SET": 0, "SAME_UPPER": 1, "SAME_LOWER": 2, "VALID": 3}
 
 # every symbol include/ore.h declares (checked by tests/test_abi.py on CPU)
@@ -52,6 +54,7 @@ EXPORTED = [
     "ore_model_graph_capture_classify_u8_list",
     "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
     "ore_model_graph_capture_classify", "ore_model_graph_capture_classify_u8",
+    "ore_image_list_set_ex", "ore_image_list_set_nv12_ex", "ore_topk_mean_f32", "ore_model_set_views",
     "ore_model_parse", "ore_model_load", "ore_model_load_ex", "ore_model_destroy", "ore_model_set_fusion", "ore_model_input_dims",
     "ore_model_output_elems", "ore_model_run", "ore_model_read_value", "ore_model_autotune",
     "ore_model_step_tile", "ore_model_set_step_tile", "ore_model_step_mfma_flops", "ore_model_set_streams",
@@ -179,6 +182,10 @@ def load():
         "ore_model_classify_u8": (i32, [vp, vp, i64, vp, vp]),
         "ore_model_graph_capture_classify": (i32, [vp, vp, i64, vp, vp]),
         "ore_model_graph_capture_classify_u8": (i32, [vp, vp, i64, vp, vp]),
+        "ore_image_list_set_ex": (i32, [vp, ctypes.POINTER(ImageU8), ctypes.POINTER(ctypes.c_uint32), i64]),
+        "ore_image_list_set_nv12_ex": (i32, [vp, ctypes.POINTER(ImageNv12), ctypes.POINTER(ctypes.c_uint32), i64]),
+        "ore_topk_mean_f32": (i32, [vp, T, i32, i32, vp, vp]),
+        "ore_model_set_views": (i32, [vp, i32]),
         "ore_model_parse": (i32, [ctypes.c_char_p, ctypes.c_size_t]),
         "ore_model_load": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, ctypes.POINTER(vp)]),
         "ore_model_load_ex": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, i32, ctypes.POINTER(vp)]),

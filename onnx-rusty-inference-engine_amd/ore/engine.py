@@ -305,6 +305,24 @@ def center_crop_geometry(src_hw, short: int, out_hw):
     return (rh, rw), ((rh - h) // 2, (rw - w) // 2)
 
 
+def multi_crop_geometries(src_hw, short: int, out_hw, crops: int = 5):
+    """[(resized_hw, origin, flip), ...] of the five- or ten-crop protocol for a source of `src_hw`: the short
+    side resized to `short` by center_crop_geometry's rule, then, in torchvision's FiveCrop / TenCrop order, the
+    `out_hw` windows at the top left, top right, bottom left and bottom right corners and the centre one
+    (center_crop_geometry's).  crops=10 adds the five crops of the mirrored image: a flipped list image is the
+    mirror of its window, so these are the top right, top left, bottom right, bottom left and centre windows
+    with flip=True.  Feed ImageList.set with geometries=[(r, o) ...] and flips=[f ...] of the entries."""
+    if crops not in (5, 10):
+        raise OreError(1, f"multi_crop_geometries: crops = {crops} (5 or 10)")
+    resized, centre = center_crop_geometry(src_hw, short, out_hw)
+    bottom, right = resized[0] - int(out_hw[0]), resized[1] - int(out_hw[1])
+    five = [(0, 0), (0, right), (bottom, 0), (bottom, right), centre]
+    out = [(resized, o, False) for o in five]
+    if crops == 10:
+        out += [(resized, five[i], True) for i in (1, 0, 3, 2, 4)]
+    return out
+
+
 def resize_aa_taps(src: int, resized: int, origin: int, count: int):
     """ore_resize_aa_taps (host only): the antialiased filter's table of one shrinking axis (`src` > `resized`,
     at most 32 times), for the `count` resized indices from `origin`: (first int32, ntaps int32, sum int32,
@@ -379,6 +397,17 @@ def _check_image_u8(x, device: int, c: int, name: str):
         raise OreError(1, f"{name}: strides {tuple(x.stride())}: expected dense pixels (C, 1) and a row stride >= Ws * C")
 
 
+def _flip_words(flips, n: int):
+    """The HOST flag array of ore_image_list_set_ex / _set_nv12_ex from `flips`, one bool per image."""
+    flips = list(flips)
+    if len(flips) != n:
+        raise OreError(1, f"set: {len(flips)} flips for {n} images")
+    words = (ctypes.c_uint32 * max(n, 1))()
+    for i, f in enumerate(flips):
+        words[i] = _lib.IMAGE_FLIP_H if f else 0
+    return words
+
+
 class ImageList:
     """ore_image_list: up to `capacity` uint8 images of their own sizes and row strides, each resized and
     cropped to out_hw by its own geometry in ONE launch (preprocess_list_u8, Model.run_u8_list, ...).  The
@@ -424,14 +453,20 @@ class ImageList:
             arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"images[{i}]")
         return images, arr
 
-    def set(self, images, geometries=None, short=None):
+    def set(self, images, geometries=None, short=None, flips=None):
         """ore_image_list_set: images is a sequence of uint8 CUDA tensors [Hs, Ws, C] (sliced views included:
         that is where row strides come from).  Geometry per image: geometries[i] = (resized_hw, origin); or
         short=S for center_crop_geometry(src_hw, S, out_hw); or neither, a plain resize to out_hw.  The upload
         is ordered on the context's stream; a rejected set leaves the list as it was.  The list keeps
-        references to the tensors."""
+        references to the tensors.  flips (ore_image_list_set_ex): one bool per image; a flipped image is its
+        unflipped output with the columns reversed, bit for bit -- the mirror of the window, not a resize of
+        the mirrored source."""
         images, arr = self._descriptors(images, geometries, short)
-        check(load().ore_image_list_set(self.h, arr, len(images)), self.ctx.h)
+        if flips is None:
+            check(load().ore_image_list_set(self.h, arr, len(images)), self.ctx.h)
+        else:
+            words = _flip_words(flips, len(images))
+            check(load().ore_image_list_set_ex(self.h, arr, words, len(images)), self.ctx.h)
         self._images = tuple(images)
         return self
 
@@ -570,13 +605,17 @@ class Nv12ImageList(ImageList):
             arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]")
         return frames, arr
 
-    def set(self, frames, geometries=None, short=None):
+    def set(self, frames, geometries=None, short=None, flips=None):
         """ore_image_list_set_nv12: frames is a sequence of (y, uv) pairs of uint8 CUDA tensors, y [Hs, Ws] and uv
         [ceil(Hs/2), ceil(Ws/2), 2], views included: the pitches are the tensors' row strides.  A window of a
         larger frame must start at an even row and column (y[y0:, x0:] with uv[y0 // 2:, x0 // 2:]).  Geometry,
-        ordering and what a rejected set leaves behind are ImageList.set's."""
+        flips (ore_image_list_set_nv12_ex), ordering and what a rejected set leaves behind are ImageList.set's."""
         frames, arr = self._descriptors(frames, geometries, short)
-        check(load().ore_image_list_set_nv12(self.h, arr, len(frames)), self.ctx.h)
+        if flips is None:
+            check(load().ore_image_list_set_nv12(self.h, arr, len(frames)), self.ctx.h)
+        else:
+            words = _flip_words(flips, len(frames))
+            check(load().ore_image_list_set_nv12_ex(self.h, arr, words, len(frames)), self.ctx.h)
         self._images = tuple(frames)
         return self
 
@@ -618,9 +657,35 @@ def topk(ctx: Context, x, k: int):
     return values, indices
 
 
+def topk_mean(ctx: Context, x, views: int, k: int):
+    """ore_topk_mean_f32 (extension): topk over the mean rows of groups of `views` consecutive rows of x, as
+    (values float32 [rows // views, k], indices int32 [rows // views, k]).  The mean is the float32 sum in
+    ascending row order divided by float32(views), every operation rounded on its own; views=1 is topk."""
+    torch = _torch()
+    d = _desc(x)
+    rows = int(x.shape[0])
+    D = 1
+    for s in x.shape[1:]:
+        D *= int(s)
+    views = int(views)
+    if not 1 <= views <= _lib.MAX_VIEWS:
+        raise OreError(1, f"views = {views} outside 1..{_lib.MAX_VIEWS}")
+    if rows % views:
+        raise OreError(1, f"{rows} rows are not a multiple of views = {views}")
+    if not 1 <= int(k) <= min(D, 64):
+        raise OreError(1, f"k = {k} outside 1..{min(D, 64)} (min(row length, 64))")
+    values = torch.empty((rows // views, int(k)), dtype=torch.float32, device=x.device)
+    indices = torch.empty((rows // views, int(k)), dtype=torch.int32, device=x.device)
+    check(load().ore_topk_mean_f32(ctx.h, ctypes.byref(d), views, int(k), ctypes.c_void_p(values.data_ptr()),
+                                   ctypes.c_void_p(indices.data_ptr())), ctx.h)
+    return values, indices
+
+
 # ------------------------------------------------------------------------------ graph walker
 class Model:
     """ore_model: the device-resident walker over one ONNX graph."""
+
+    views = 1  # set_views: the classify entries' images per subject
 
     def __init__(self, ctx: Context, onnx_bytes: bytes, max_batch: int, precision: str = "f32",
                  winograd: bool = True):
@@ -772,6 +837,19 @@ class Model:
         check(load().ore_model_set_topk(self.h, int(k)), self.ctx.h)
         self.topk = int(k)
 
+    def set_views(self, views: int):
+        """ore_model_set_views: classify* / capture_classify* treat every `views` consecutive images as the views
+        of one subject and select over the mean of their rows (topk_mean): scores and classes are
+        [n // views, topk], n a multiple of views.  1 <= views <= min(64, run_batch); default 1.  run* ignore it."""
+        check(load().ore_model_set_views(self.h, int(views)), self.ctx.h)
+        self.views = int(views)
+
+    def _subjects(self, n: int) -> int:
+        """The output rows of a classification of n images: n // views, n a multiple of views."""
+        if n % self.views:
+            raise OreError(1, f"{n} images are not a multiple of views = {self.views}")
+        return n // self.views
+
     def _check_classify_in(self, x, u8: bool):
         """The input checks of run_into (float32 [n, C, H, W]) or run_u8_into (uint8 [n, H, W, C]); returns n."""
         torch = _torch()
@@ -794,7 +872,7 @@ class Model:
 
     def _check_classify_out(self, n: int, scores, classes):
         """The walker writes scores and classes through raw device pointers: contiguous CUDA tensors on this
-        context's device, float32 and int32, both [n, topk]."""
+        context's device, float32 and int32, both [n, topk]; n is the number of output rows (images // views)."""
         torch = _torch()
         for name, t, dt, dn in (("scores", scores, torch.float32, "float32"), ("classes", classes, torch.int32, "int32")):
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
@@ -808,16 +886,16 @@ class Model:
 
     def _classify(self, entry, x, scores, classes, u8: bool):
         n = self._check_classify_in(x, u8)
-        self._check_classify_out(n, scores, classes)
+        self._check_classify_out(self._subjects(n), scores, classes)
         check(entry(self.h, ctypes.c_void_p(x.data_ptr()), int(n), ctypes.c_void_p(scores.data_ptr()),
                     ctypes.c_void_p(classes.data_ptr())), self.ctx.h)
         return scores, classes
 
     def _classify_bufs(self, x, u8: bool):
         torch = _torch()
-        n = self._check_classify_in(x, u8)
-        return (torch.empty((n, self.topk), dtype=torch.float32, device=x.device),
-                torch.empty((n, self.topk), dtype=torch.int32, device=x.device))
+        g = self._subjects(self._check_classify_in(x, u8))
+        return (torch.empty((g, self.topk), dtype=torch.float32, device=x.device),
+                torch.empty((g, self.topk), dtype=torch.int32, device=x.device))
 
     def classify_into(self, x, scores, classes):
         """ore_model_classify: run_into that keeps the rows on the device and writes only the topk best
@@ -886,7 +964,7 @@ class Model:
 
     def _classify_list(self, entry, lst, scores, classes):
         n = self._check_list(lst)
-        self._check_classify_out(n, scores, classes)
+        self._check_classify_out(self._subjects(n), scores, classes)
         check(entry(self.h, lst.h, ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(classes.data_ptr())), self.ctx.h)
         return scores, classes
 
@@ -898,8 +976,9 @@ class Model:
         torch = _torch()
         n = self._check_list(lst)
         dev = f"cuda:{self.ctx.device}"
-        scores = torch.empty((n, self.topk), dtype=torch.float32, device=dev)
-        classes = torch.empty((n, self.topk), dtype=torch.int32, device=dev)
+        g = self._subjects(n)
+        scores = torch.empty((g, self.topk), dtype=torch.float32, device=dev)
+        classes = torch.empty((g, self.topk), dtype=torch.int32, device=dev)
         if n == 0:
             return scores, classes
         return self.classify_u8_list_into(lst, scores, classes)

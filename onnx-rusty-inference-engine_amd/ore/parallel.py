@@ -63,14 +63,21 @@ def run_sharded(run_fn: Callable, x_global, group=None):
     return gather_rows(local, x_global.shape[0], group)
 
 
-def classify_sharded(classify_fn: Callable, x_global, group=None):
+def classify_sharded(classify_fn: Callable, x_global, group=None, views: int = 1):
     """Run `classify_fn(x_slice) -> (scores [n_slice, k] float32, classes [n_slice, k] int32)` on this
     rank's slice of x_global and return the gathered ([n_total, k], [n_total, k]) on every rank: n * k * 8
-    bytes per rank and step instead of run_sharded's n * D * 4.  Classes stay per-image class ids."""
+    bytes per rank and step instead of run_sharded's n * D * 4.  Classes stay per-image class ids.
+    With views > 1 (Model.set_views) every `views` consecutive images are one subject: the slices hold whole
+    subjects (shard_bounds over n_total // views, scaled), classify_fn returns one row per subject and the
+    gathered arrays are [n_total // views, k]."""
     import torch.distributed as dist
+    n_total = x_global.shape[0]
+    views = int(views)
+    if views < 1 or n_total % views:
+        raise ValueError(f"{n_total} images are not a multiple of views = {views}")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
-    n_total = x_global.shape[0]
-    s, e = shard_bounds(n_total, world, rank)
-    scores, classes = classify_fn(x_global[s:e])
-    return gather_rows(scores, n_total, group), gather_rows(classes, n_total, group)
+    g_total = n_total // views
+    s, e = shard_bounds(g_total, world, rank)
+    scores, classes = classify_fn(x_global[s * views: e * views])
+    return gather_rows(scores, g_total, group), gather_rows(classes, g_total, group)
