@@ -447,7 +447,16 @@ ore_status ore_model_destroy(ore_model* m);
  * arithmetic as the separate ones, so results do not depend on the flags (tested bit for bit).
  * bit 0 = fuse Conv->Relu, bit 1 = Concat in place (and padded channel planes), bit 2 = alias
  * Dropout / Reshape; bits 5-10 and 12 below.  Bit 4 (ABI 1's ORE_FUSE_POOL_CONV, a MaxPool inside a
- * 1x1 conv's operand gather, measured slower) is retired: ORE_ERR_UNSUPPORTED. */
+ * 1x1 conv's operand gather, measured slower) is retired: ORE_ERR_UNSUPPORTED.
+ * Non-finite activations (an f16 model makes them itself: outputs past 65504 are +-inf, and the next layer
+ * sees inf x 0 or inf - inf): every plan of a model still returns the same result, and it is the
+ * reference's.  Relu(NaN) = +0 (Relu is f32::max, relu_op.rs); MaxPool ignores NaN and pads with zero (it
+ * folds f32::max from f32::MIN over the zero-padded window, so a window of NaN alone gives f32::MIN, which an
+ * f16 model stores as -inf); Conv, GlobalAveragePool and Softmax propagate NaN, and inf x 0 is NaN under a
+ * zero weight as under any other -- but only under a weight of the graph: the zero weights and zero operands
+ * the kernels pad their tiles with never meet an activation's inf or NaN (tests/test_nonfinite_gpu.py).
+ * Winograd is exempt: its input transform adds and subtracts neighbouring pixels before the multiply, so inf -
+ * inf and the footprint of a NaN differ from the direct sum; load with ORE_LOAD_NO_WINOGRAD where that matters. */
 #define ORE_FUSE_CONV_RELU 1
 #define ORE_FUSE_CONCAT 2
 #define ORE_FUSE_ALIAS 4
@@ -507,6 +516,26 @@ ore_status ore_model_destroy(ore_model* m);
 /* debug: give every value its own storage (no liveness reuse) so any value can be read back */
 #define ORE_KEEP_VALUES 8
 ore_status ore_model_set_fusion(ore_model* m, int32_t flags);
+/* Scratch poisoning (debug extension, off by default; nothing on a run's path reads these settings).  The
+ * library never initialises the device memory it allocates for itself, and kernels read parts of it by
+ * design: padded channel planes, the slots' 256-B rounding tails, the 4 KiB lead in front of the arena, the
+ * slots of images n .. run_batch-1 of a smaller run, what an earlier value left in a reused slot.  None of
+ * that may reach a result, whatever bits it holds (tests/test_scratch_poison_gpu.py, with NaN and +inf).
+ *  ore_ctx_set_alloc_fill: while on, every device allocation the library makes for itself on this context
+ *    -- a model's arena block with its lead, its f16 input conversion buffer (xcvt), uint8 staging buffer
+ *    (stage) and top-k rows buffer (rows), its initializer block, its packed weights and the fused kernels'
+ *    weight packs, and the context's per-op weight scratch -- is filled with the 32-bit pattern on the
+ *    context's stream before anything else touches it.  ore_malloc is the caller's memory and is not filled;
+ *    the image lists' descriptor tables hold device addresses and are not filled either.
+ *  ore_model_fill_scratch: the same fill, now, of the model's activation memory (arena block with lead, xcvt,
+ *    stage, rows; never weights), stream-ordered: between ore_model_set_fusion (which plans into the arena
+ *    it has) and a run, or between two runs.  ORE_ERR_INVALID while the context's stream is capturing.
+ *  ore_model_scratch_info: buffer i of that activation memory (those that exist, in the order above): its
+ *    name, device pointer and size, for ore_download; ORE_ERR_INVALID past the last one.  Host only.
+ * A null context / model is ORE_ERR_INVALID before any device call. */
+ore_status ore_ctx_set_alloc_fill(ore_ctx* ctx, int32_t on, uint32_t pattern);
+ore_status ore_model_fill_scratch(ore_model* m, uint32_t pattern);
+ore_status ore_model_scratch_info(ore_model* m, int32_t i, const char** name, void** dptr, size_t* bytes);
 /* The seeded model input (graph.input entries that are not initializers, utils.rs:29-45):
  * per-image dims; dims[0] is the batch. */
 ore_status ore_model_input_dims(ore_model* m, int64_t dims[4]);

@@ -18,8 +18,8 @@
 //   * per channel fragment the conv values (bias, Relu, f16; 0 outside the conv plane) go to an LDS
 //     tile [pixel][32 channels] and each (pooled output, 8 channels) takes its 3x3 max from -FLT_MAX
 //     in f32 (the EP kernel's arithmetic) and leaves by one 16-B NHWC store.
-// Same operands (the PAIR padding tap meets a zero weight; the gather path zeroes the operand too:
-// zero products either way), same k order, same MFMA chain and epilogue as the two-launch path:
+// Same operands (the PAIR padding tap is zeroed, as the gather path zeroes it, and meets a zero
+// weight: zero products either way, whatever the pixel beside the window holds), same k order, same MFMA chain and epilogue as the two-launch path:
 // bit-identical output (tests/test_f16_gpu.py).
 #include <float.h>
 #include <hip/hip_runtime.h>
@@ -42,6 +42,7 @@ constexpr int C1_TS = 40;                                                  // co
 static_assert(C1_NPX <= 256, "one 256-pixel patch per tile (8 fragments)");
 
 typedef unsigned short c1u8 __attribute__((ext_vector_type(8)));
+typedef unsigned c1u4 __attribute__((ext_vector_type(4)));
 
 // 3x3 max of 8 channels of conv-tile pixels (row stride C1_CC pixels of C1_TS halves) from -FLT_MAX in
 // f32 (the separate pool's arithmetic).  After the Relu every value is +0 or positive, so its f16 bits
@@ -247,13 +248,22 @@ __global__ __launch_bounds__(256, 2) void conv_pair_pool_f16_kernel(ConvParams p
           for (int i = 0; i < MF; ++i) ag[(ks + 1) & 1][i] = *reinterpret_cast<const c1h8*>(arow_g[i] + 16 * (ks + 1));
         }
       }
-      // the padding tap s + 1 = KW (odd KW) is read as it lies in the window (a finite value: image
-      // data or an outside-the-image zero) and meets a zero weight (pack_weights_f16_kernel): its
-      // products are zeros, as the gather path's zeroed operand gives
+      // the padding tap s + 1 = KW (odd KW) is read as it lies in the window (image data or an
+      // outside-the-image zero) and zeroed here, as the gather path zeroes its operand: its zero weight
+      // (pack_weights_f16_kernel) alone would turn an inf or a NaN there into a NaN of every output whose
+      // window ends beside it (tests/test_nonfinite_gpu.py)
       const int pair = 2 * ks + h, tap = 2 * pair, r = tap / KWP, s = tap - r * KWP;
+      const unsigned keep = (KW & 1) && s + 1 == KW ? 0u : ~0u;  // two v_and_b32 on the tap's four halves
       c1h8 b[2];
 #pragma unroll
-      for (int f = 0; f < 2; ++f) b[f] = *reinterpret_cast<const c1h8*>(halo + bofs[f] + (r * HC + s) * 4);
+      for (int f = 0; f < 2; ++f) {
+        c1u4 w = *reinterpret_cast<const c1u4*>(halo + bofs[f] + (r * HC + s) * 4);
+        if constexpr (KW & 1) {
+          w[2] &= keep;
+          w[3] &= keep;
+        }
+        b[f] = __builtin_bit_cast(c1h8, w);
+      }
 #pragma unroll
       for (int i = 0; i < MF; ++i) {
         const c1h8 a = C1_WLDS ? *reinterpret_cast<const c1h8*>(Ws + ((ks * MF + i) * 32 + lr) * 16 + 8 * h) : ag[ks & 1][i];
@@ -403,6 +413,7 @@ __global__ __launch_bounds__(512, 1) void conv_band_pool_f16_kernel(ConvParams p
   const int tid = threadIdx.x, lane = tid & 63, lr = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int Kp = (p.K + 31) & ~31;
+  const unsigned padkeep = h ? 0u : ~0u;  // lane half 1 holds the padding tap on the odd k-steps
   const _Float16* __restrict__ wh = reinterpret_cast<const _Float16*>(p.wp);  // [Mp][Kp]
   // weights once, as the patch kernel stages them: LDS row R of each 32-row block <- packed row (R & ~31) +
   // 16 (i >> 1) + 8 hh + 4 (i & 1) + j for R % 32 = 8 i + 4 hh + j (rows past M zero)
@@ -506,7 +517,16 @@ __global__ __launch_bounds__(512, 1) void conv_band_pool_f16_kernel(ConvParams p
           const int ko = ((4 * ks) / 8 * FB_RW + (4 * ks) % 8) * 4;
           c1h8 b[2];
 #pragma unroll
-          for (int f = 0; f < 2; ++f) b[f] = *reinterpret_cast<const c1h8*>(win + bo[f] + ko);
+          for (int f = 0; f < 2; ++f) {
+            c1u4 w = *reinterpret_cast<const c1u4*>(win + bo[f] + ko);
+            // columns 6 and 7 of the 8-tap row: 7 is the padding tap, zeroed as in the patch kernel (an inf or
+            // NaN pixel there must not meet its zero weight): two v_and_b32 on the odd k-steps
+            if (ks & 1) {
+              w[2] &= padkeep;
+              w[3] &= padkeep;
+            }
+            b[f] = __builtin_bit_cast(c1h8, w);
+          }
 #pragma unroll
           for (int i = 0; i < MF; ++i) {
             const c1h8 a = *reinterpret_cast<const c1h8*>(Ws + (ks * MF + i) * 512 + aofs);
@@ -538,8 +558,10 @@ __global__ __launch_bounds__(512, 1) void conv_band_pool_f16_kernel(ConvParams p
               const fbf2 v0 = fbf2{acc[i][0][8 * g + e], acc[i][0][8 * g + e + 1]} + b2;
               const fbf2 v1 = fbf2{acc[i][1][8 * g + e], acc[i][1][8 * g + e + 1]} + b2;
               const fbf2 m01 = {fmaxf(v0[0], v1[0]), fmaxf(v0[1], v1[1])};
-              const fbs2 r0 = __builtin_elementwise_max(__builtin_bit_cast(fbs2, __builtin_convertvector(v0, fbh2)), fbs2{0, 0});
-              const fbs2 rm = __builtin_elementwise_max(__builtin_bit_cast(fbs2, __builtin_convertvector(m01, fbh2)), fbs2{0, 0});
+              // Relu as the f16 maximum with +0 (maxNum: a NaN becomes +0, as under fmaxf; ore_f16_epilogue8)
+              const fbh2 z2 = {(_Float16)0.0f, (_Float16)0.0f};
+              const fbs2 r0 = __builtin_bit_cast(fbs2, __builtin_elementwise_max(__builtin_convertvector(v0, fbh2), z2));
+              const fbs2 rm = __builtin_bit_cast(fbs2, __builtin_elementwise_max(__builtin_convertvector(m01, fbh2), z2));
               const int nb = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r0), 0x130, 0xf, 0xf, true);
               // Relu outputs are >= +0: their f16 bits order like the values (unsigned max)
               o[e >> 1] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(fbus2, rm),

@@ -25,6 +25,8 @@ struct ore_ctx {
   int conv_tile = -1;    // ore_ctx_set_conv_tile: a forced tile id (-1: per-layer heuristic / autotune)
   int pool_variant = 0;  // ore_ctx_set_pool_variant: a forced MaxPool kernel (0: by layout)
   int resize_variant = 0;  // ore_ctx_set_resize_variant: 0 by geometry, 1 thread per pixel -- one kernel today, so nothing reads it
+  bool alloc_fill = false;         // ore_ctx_set_alloc_fill (debug): device_alloc fills what the library allocates for itself
+  uint32_t alloc_pattern = 0;
 };
 
 // ore_image_list: a device table of `capacity` packed descriptors for one output shape and its pinned host
@@ -55,6 +57,16 @@ ore_status set_error(ore_ctx* ctx, ore_status st, const char* fmt, ...);
     if (e_ != hipSuccess)                                                                 \
       return ::ore::set_error((ctx), ORE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+// ---------------------------------------------------------------- device memory
+// Every device allocation of the library goes through here.  own: memory the library keeps for itself (arena,
+// conversion / staging / rows buffers, weight packs, the weight scratch) -- under ore_ctx_set_alloc_fill it is
+// filled with the context's pattern on the context's stream before the caller gets the pointer, so whatever
+// the caller launches on that stream afterwards is ordered behind the fill.  Not own: the caller's memory
+// (ore_malloc) and the image-list tables, which hold addresses and geometry and are never filled.
+hipError_t device_alloc(ore_ctx* ctx, void** dptr, size_t bytes, bool own);
+// `bytes` of device memory set to the 32-bit pattern, stream-ordered (a tail of bytes % 4 takes its low bytes)
+hipError_t device_fill(ore_ctx* ctx, void* dptr, size_t bytes, uint32_t pattern);
 
 // ---------------------------------------------------------------- ONNX subset (onnx.proto)
 struct Attr {

@@ -22,9 +22,11 @@ __device__ __forceinline__ int xcd_block_id() {
 }
 
 // f16 epilogue of 8 f32 accumulators: + bias, one rounding to f16, Relu -- as packed pairs
-// (v_pk_add_f32, v_cvt_pk_f16_f32, v_pk_max_i16: 1.5 VALU per value against 3 for add / max / cvt).
-// Relu after the rounding on the f16 bits as int16 (max with 0) equals Relu before it for every
-// finite value: round-to-nearest keeps the sign, a negative or -0 result becomes +0 either way.
+// (v_pk_add_f32, v_cvt_pk_f16_f32, v_pk_max_f16: 1.5 VALU per value against 3 for add / max / cvt).
+// Relu after the rounding, as the f16 maximum with +0, equals Relu before it for every value: round-to-nearest
+// keeps the sign, so a negative or -0 result becomes +0 either way, and the maximum is maxNum, so a NaN of
+// either sign becomes +0 as under the separate kernels' fmaxf(v, 0.0f) (the reference's f32::max; an int16
+// max on the bits, which this was, keeps a NaN whose sign bit is clear: tests/test_nonfinite_gpu.py).
 // PK_ADD = false keeps the bias adds scalar (v_add_f32): inside kernels whose epilogue runs beside
 // MFMAs, where packed f32 VALU costs more than scalar pairs (MI355X_MICROARCH.md 'price of one filler
 // beside MFMAs'; measured: the fire f16 kernels 10-20 % slower with v_pk_add_f32)
@@ -45,8 +47,9 @@ __device__ __forceinline__ ore_h8 ore_f16_epilogue8(const float* a, const float*
       v[0] = a[e] + b[e];
       v[1] = a[e + 1] + b[e + 1];
     }
-    s2 q = __builtin_bit_cast(s2, __builtin_convertvector(v, h2));
-    if (relu) q = __builtin_elementwise_max(q, s2{0, 0});
+    h2 r = __builtin_convertvector(v, h2);
+    if (relu) r = __builtin_elementwise_max(r, h2{(_Float16)0.0f, (_Float16)0.0f});
+    const s2 q = __builtin_bit_cast(s2, r);
     o[e] = q[0];
     o[e + 1] = q[1];
   }

@@ -649,8 +649,11 @@ ore_status ore_model_load_ex(ore_ctx* ctx, const void* bytes, size_t len, int64_
   size_t total = 0;
   for (auto& t : g.inits) total += (t.f32.size() * 4 + 255) / 256 * 256;
   std::vector<char> host(total ? total : 1, 0);
-  if (total && hipMalloc(reinterpret_cast<void**>(&m->consts), total) != hipSuccess)
+  if (total && device_alloc(ctx, reinterpret_cast<void**>(&m->consts), total, true) != hipSuccess)
     return fail(set_error(ctx, ORE_ERR_OOM, "initializer upload allocation failed"));
+  // the upload below is not on the context's stream: a fill (ore_ctx_set_alloc_fill) has to land first
+  if (total && ctx->alloc_fill && hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return fail(set_error(ctx, ORE_ERR_HIP, "initializer buffer fill failed"));
   size_t off = 0;
   for (auto& t : g.inits) {
     int id = new_value(m, t.name);
@@ -724,7 +727,7 @@ ore_status ore_model_load_ex(ore_ctx* ctx, const void* bytes, size_t len, int64_
       }
     }
     if (total_packed) {
-      if (hipMalloc(reinterpret_cast<void**>(&m->packed), total_packed) != hipSuccess)
+      if (device_alloc(ctx, reinterpret_cast<void**>(&m->packed), total_packed, true) != hipSuccess)
         return fail(set_error(ctx, ORE_ERR_OOM, "packed weight allocation failed"));
       size_t poff = 0;
       for (auto& s : m->base_steps) {
@@ -787,6 +790,43 @@ ore_status ore_model_set_fusion(ore_model* m, int32_t flags) {
   if (flags & ~known) return set_error(m->ctx, ORE_ERR_INVALID, "unknown fusion flags 0x%x", unsigned(flags & ~known));
   m->fusion = flags;
   return plan(m);
+}
+
+// the model's activation memory, in the order ore_model_scratch_info enumerates it
+namespace {
+struct ScratchBuf { const char* name; void* p; size_t bytes; };
+int scratch_bufs(ore_model* m, ScratchBuf out[4]) {
+  int n = 0;
+  if (m->arena_alloc) out[n++] = {"arena", m->arena_alloc, m->arena_bytes + ARENA_LEAD};
+  if (m->xcvt) out[n++] = {"xcvt", m->xcvt, m->xcvt_bytes};
+  if (m->stage) out[n++] = {"stage", m->stage, m->stage_bytes};
+  if (m->rows) out[n++] = {"rows", m->rows, m->rows_bytes};
+  return n;
+}
+}  // namespace
+
+ore_status ore_model_fill_scratch(ore_model* m, uint32_t pattern) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  ore_ctx* ctx = m->ctx;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_model_fill_scratch inside a stream capture");
+  ScratchBuf b[4];
+  const int n = scratch_bufs(m, b);
+  for (int i = 0; i < n; ++i) ORE_HIP_CHECK(ctx, device_fill(ctx, b[i].p, b[i].bytes, pattern));
+  return ORE_OK;
+}
+
+ore_status ore_model_scratch_info(ore_model* m, int32_t i, const char** name, void** dptr, size_t* bytes) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  ScratchBuf b[4];
+  const int n = scratch_bufs(m, b);
+  if (i < 0 || i >= n) return set_error(m->ctx, ORE_ERR_INVALID, "scratch buffer %d of %d", int(i), n);
+  if (name) *name = b[i].name;
+  if (dptr) *dptr = b[i].p;
+  if (bytes) *bytes = b[i].bytes;
+  return ORE_OK;
 }
 
 ore_status ore_model_input_dims(ore_model* m, int64_t dims[4]) {
@@ -860,7 +900,7 @@ static ore_status ensure_stage(ore_model* m) {
   if (m->stage) (void)hipFree(m->stage);
   m->stage = nullptr;
   m->stage_bytes = 0;
-  if (hipMalloc(&m->stage, need) != hipSuccess) {
+  if (device_alloc(ctx, reinterpret_cast<void**>(&m->stage), need, true) != hipSuccess) {
     (void)hipGetLastError();
     return set_error(ctx, ORE_ERR_OOM, "uint8 input staging buffer (%zu bytes) allocation failed", need);
   }
@@ -883,7 +923,7 @@ static ore_status ensure_rows(ore_model* m) {
   if (m->rows) (void)hipFree(m->rows);
   m->rows = nullptr;
   m->rows_bytes = 0;
-  if (hipMalloc(&m->rows, need) != hipSuccess) {
+  if (device_alloc(ctx, reinterpret_cast<void**>(&m->rows), need, true) != hipSuccess) {
     (void)hipGetLastError();
     return set_error(ctx, ORE_ERR_OOM, "top-k rows buffer (%zu bytes) allocation failed", need);
   }

@@ -241,6 +241,28 @@ ConvPlan conv_plan(int64_t M, int64_t C, int64_t H, int64_t W, int64_t kh, int64
                    int(win.Ho), int(win.Wo), kh == 1 && kw == 1, f16, xmode, wino, forced);
 }
 
+hipError_t device_fill(ore_ctx* ctx, void* dptr, size_t bytes, uint32_t pattern) {
+  char* p = static_cast<char*>(dptr);
+  const size_t words = bytes / 4;
+  if (words)
+    if (hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), int(pattern), words, ctx->stream)) return e;
+  for (size_t i = words * 4; i < bytes; ++i)
+    if (hipError_t e = hipMemsetAsync(p + i, int((pattern >> (8 * (i & 3))) & 0xff), 1, ctx->stream)) return e;
+  return hipSuccess;
+}
+
+hipError_t device_alloc(ore_ctx* ctx, void** dptr, size_t bytes, bool own) {
+  *dptr = nullptr;
+  if (hipError_t e = hipMalloc(dptr, bytes)) return e;
+  if (!own || !ctx->alloc_fill) return hipSuccess;
+  const hipError_t e = device_fill(ctx, *dptr, bytes, ctx->alloc_pattern);
+  if (e != hipSuccess) {
+    (void)hipFree(*dptr);
+    *dptr = nullptr;
+  }
+  return e;
+}
+
 size_t packed_bytes(const ConvPlan& pln) { return conv_packed_bytes(pln) + size_t(pln.krows) * sizeof(int2); }
 
 float* pack_to_scratch(ore_ctx* ctx, const ConvPlan& pln, const float* w, bool kmajor_src, int64_t M, int64_t C,
@@ -253,7 +275,7 @@ float* pack_to_scratch(ore_ctx* ctx, const ConvPlan& pln, const float* w, bool k
     }
     ctx->scratch = nullptr;
     ctx->scratch_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->scratch), need) != hipSuccess) {
+    if (device_alloc(ctx, reinterpret_cast<void**>(&ctx->scratch), need, true) != hipSuccess) {
       set_error(ctx, ORE_ERR_OOM, "weight scratch allocation (%zu bytes) failed", need);
       return nullptr;
     }
@@ -687,6 +709,13 @@ ore_status ore_ctx_set_resize_variant(ore_ctx* ctx, int32_t variant) {
   return ORE_OK;
 }
 
+ore_status ore_ctx_set_alloc_fill(ore_ctx* ctx, int32_t on, uint32_t pattern) {
+  if (!ctx) return set_error(nullptr, ORE_ERR_INVALID, "null context");
+  ctx->alloc_fill = on != 0;
+  ctx->alloc_pattern = pattern;
+  return ORE_OK;
+}
+
 ore_status ore_ctx_set_stream(ore_ctx* ctx, void* s) {
   if (!ctx) return set_error(nullptr, ORE_ERR_INVALID, "null ctx");
   ctx->stream = reinterpret_cast<hipStream_t>(s);
@@ -705,7 +734,7 @@ ore_status ore_sync(ore_ctx* ctx) {
 ore_status ore_malloc(ore_ctx* ctx, size_t bytes, void** dptr) {
   if (!ctx || !dptr) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (hipMalloc(dptr, bytes ? bytes : 1) != hipSuccess) return set_error(ctx, ORE_ERR_OOM, "hipMalloc(%zu) failed", bytes);
+  if (device_alloc(ctx, dptr, bytes ? bytes : 1, false) != hipSuccess) return set_error(ctx, ORE_ERR_OOM, "hipMalloc(%zu) failed", bytes);
   return ORE_OK;
 }
 
@@ -1156,7 +1185,8 @@ static ore_status list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t
   const size_t bytes = size_t(capacity) * (nv12 ? sizeof(Nv12Image) : sizeof(ResizeImage));
   void** table = nv12 ? reinterpret_cast<void**>(&l->table_nv12) : reinterpret_cast<void**>(&l->table);
   void** mirror = nv12 ? reinterpret_cast<void**>(&l->mirror_nv12) : reinterpret_cast<void**>(&l->mirror);
-  if (hipMalloc(table, bytes) != hipSuccess || hipHostMalloc(mirror, bytes, hipHostMallocDefault) != hipSuccess ||
+  // the table holds device addresses and geometry: never filled (device_alloc, own = false)
+  if (device_alloc(ctx, table, bytes, false) != hipSuccess || hipHostMalloc(mirror, bytes, hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&l->uploaded, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
     (void)ore_image_list_destroy(l);

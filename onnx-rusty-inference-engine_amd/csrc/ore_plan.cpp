@@ -116,7 +116,7 @@ struct Planner {
     const auto it = m->packs.find(key);
     if (it != m->packs.end()) return it->second;
     float* buf = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&buf), bytes) != hipSuccess) return nullptr;
+    if (device_alloc(m->ctx, reinterpret_cast<void**>(&buf), bytes, true) != hipSuccess) return nullptr;
     launch(buf);
     m->packs[key] = buf;
     return hipGetLastError() == hipSuccess && hipStreamSynchronize(m->ctx->stream) == hipSuccess ? buf : nullptr;
@@ -740,7 +740,7 @@ struct Planner {
       if (m->xcvt) (void)hipFree(m->xcvt);
       m->xcvt = nullptr;
       m->xcvt_bytes = 0;
-      if (hipMalloc(&m->xcvt, size_t(xcvt_img * m->run_batch)) != hipSuccess)
+      if (device_alloc(m->ctx, &m->xcvt, size_t(xcvt_img * m->run_batch), true) != hipSuccess)
         return err(m, ORE_ERR_OOM, "input conversion buffer allocation failed");
       m->xcvt_bytes = size_t(xcvt_img * m->run_batch);
     }
@@ -767,7 +767,8 @@ struct Planner {
       if (m->arena_alloc) (void)hipFree(m->arena_alloc);
       m->arena = m->arena_alloc = nullptr;
       m->arena_bytes = 0;
-      if (arena > 0 && hipMalloc(reinterpret_cast<void**>(&m->arena_alloc), size_t(arena) + ARENA_LEAD) != hipSuccess)
+      if (arena > 0 &&
+          device_alloc(m->ctx, reinterpret_cast<void**>(&m->arena_alloc), size_t(arena) + ARENA_LEAD, true) != hipSuccess)
         return err(m, ORE_ERR_OOM, "arena allocation of " + std::to_string(arena) + " bytes failed");
       if (m->arena_alloc) m->arena = m->arena_alloc + ARENA_LEAD;
       m->arena_bytes = size_t(arena);

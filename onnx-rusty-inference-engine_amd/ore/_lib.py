@@ -60,6 +60,7 @@ EXPORTED = [
     "ore_model_step_tile", "ore_model_set_step_tile", "ore_model_step_mfma_flops", "ore_model_set_streams",
     "ore_model_graph_capture", "ore_model_graph_launch", "ore_model_enable_timing",
     "ore_model_step_count", "ore_model_step_info", "ore_model_step_times", "ore_model_run_batch",
+    "ore_ctx_set_alloc_fill", "ore_model_fill_scratch", "ore_model_scratch_info",
 ]
 
 
@@ -208,6 +209,9 @@ def load():
         "ore_model_step_info": (i32, [vp, i32, ctypes.POINTER(cs), ctypes.POINTER(cs),
                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
         "ore_model_step_times": (i32, [vp, ctypes.POINTER(ctypes.c_float), i32]),
+        "ore_ctx_set_alloc_fill": (i32, [vp, i32, ctypes.c_uint32]),
+        "ore_model_fill_scratch": (i32, [vp, ctypes.c_uint32]),
+        "ore_model_scratch_info": (i32, [vp, i32, ctypes.POINTER(cs), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -66,6 +66,11 @@ class Context:
         pixel; 0 = by geometry, which is that kernel today).  Results do not depend on it."""
         check(load().ore_ctx_set_resize_variant(self.h, int(variant)), self.h)
 
+    def set_alloc_fill(self, on: bool, pattern: int = 0):
+        """ore_ctx_set_alloc_fill (debug): while on, every device allocation the library makes for itself on
+        this context is filled with the 32-bit pattern before anything else touches it."""
+        check(load().ore_ctx_set_alloc_fill(self.h, 1 if on else 0, int(pattern) & 0xFFFFFFFF), self.h)
+
     @property
     def stream(self) -> int:
         return load().ore_ctx_get_stream(self.h) or 0
@@ -718,6 +723,20 @@ class Model:
 
     def set_fusion(self, flags: int):
         check(load().ore_model_set_fusion(self.h, int(flags)), self.ctx.h)
+
+    def fill_scratch(self, pattern: int):
+        """ore_model_fill_scratch (debug): fill the model's activation memory (arena with its lead, xcvt, stage,
+        rows) with the 32-bit pattern, stream-ordered; refused inside a capture."""
+        check(load().ore_model_fill_scratch(self.h, int(pattern) & 0xFFFFFFFF), self.ctx.h)
+
+    def scratch_buffers(self):
+        """ore_model_scratch_info: [(name, device pointer, bytes)] of the model's activation buffers."""
+        out = []
+        name, ptr, size = ctypes.c_char_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        while load().ore_model_scratch_info(self.h, len(out), ctypes.byref(name), ctypes.byref(ptr),
+                                            ctypes.byref(size)) == _lib.ORE_OK:
+            out.append((name.value.decode(), ptr.value, size.value))
+        return out
 
     def _check_io(self, x, out):
         """The walker reads x and writes out through raw device pointers: both must be contiguous

@@ -106,6 +106,19 @@ def test_errors_without_gpu():
     assert L.ore_sync(None) == 1 and b"null" in L.ore_last_error(None)
 
 
+def test_scratch_poison_argument_errors():
+    """The debug entries check their arguments before the context and any device call: a null context or model is
+    ORE_ERR_INVALID, whatever the index, and nothing is written through the out pointers."""
+    L = ore.load()
+    assert L.ore_ctx_set_alloc_fill(None, 1, 0x7FC07FC0) == 1 and b"null context" in L.ore_last_error(None)
+    assert L.ore_model_fill_scratch(None, 0x7FC07FC0) == 1 and b"null model" in L.ore_last_error(None)
+    name, ptr, size = ctypes.c_char_p(b"kept"), ctypes.c_void_p(5), ctypes.c_size_t(7)
+    for i in (0, 4, -1, 2 ** 31 - 1):  # the first, one past the most a model can have, and nonsense
+        assert L.ore_model_scratch_info(None, i, ctypes.byref(name), ctypes.byref(ptr), ctypes.byref(size)) == 1
+        assert b"null model" in L.ore_last_error(None)
+    assert (name.value, ptr.value, size.value) == (b"kept", 5, 7)
+
+
 def test_reshape_host_only():
     t = _lib.Tensor()
     t.data = 0x1000
