@@ -341,7 +341,7 @@ int32_t ore_image_list_filter(ore_image_list* l);
  *    ore_image_list_set on an NV12 list and ore_image_list_set_nv12 on an interleaved one are ORE_ERR_INVALID
  *    and leave the list unchanged. */
 typedef enum { ORE_YUV_BT601 = 0, ORE_YUV_BT709 = 1, ORE_YUV_BT601_FULL = 2 } ore_yuv_matrix;
-typedef enum { ORE_IMAGE_INTERLEAVED = 0, ORE_IMAGE_NV12 = 1 } ore_image_format;
+typedef enum { ORE_IMAGE_INTERLEAVED = 0, ORE_IMAGE_NV12 = 1, ORE_IMAGE_YUV = 2 } ore_image_format;
 typedef struct ore_image_nv12 {
   const uint8_t* y;          /* DEVICE pointer to row 0, column 0 of the Y plane; any alignment */
   const uint8_t* uv;         /* DEVICE pointer to row 0, pair 0 of the UV plane; any alignment */
@@ -358,6 +358,66 @@ ore_status ore_image_list_create_nv12(ore_ctx* ctx, int64_t capacity, int64_t h,
 ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs, int64_t n);
 int32_t ore_image_list_format(ore_image_list* l);
 int32_t ore_image_list_matrix(ore_image_list* l);
+/* YUV image lists (extension, the *_yuv_list kernels in ore_resize.hip): frames as a JPEG decoder leaves them.  A
+ * hardware JPEG decoder writes what the file's chroma subsampling dictates -- three planes for 4:4:4 and 4:4:0,
+ * one packed YUYV plane for 4:2:2, NV12 for 4:2:0, a single Y plane for 4:0:0, or three planes for every
+ * subsampling (4:1:1 included) in its planar mode -- and one batch of files mixes them.  So every descriptor of
+ * such a list carries its own plane layout (ore_yuv_format), and one launch takes the batch as it was decoded.
+ * With (sx, sy) the format's chroma shifts, source pixel (r, j) is Y at (r, j) and the chroma sample at
+ * (r >> sy, j >> sx): chroma is taken nearest, as for NV12 lists.  A chroma plane has ceil(hs / 2^sy) rows of
+ * ceil(ws / 2^sx) samples, so the last row / column of an odd-sized frame has a sample of its own.  The conversion
+ * is the one above under the list's matrix (a property of the list, as for NV12 lists; a JPEG caller passes
+ * ORE_YUV_BT601_FULL); a grey frame has U = V = 128, hence R = G = B.
+ * Image i of a YUV list is, bit for bit, what an interleaved list (c = 3) of the same filter gives for the
+ * [hs,ws,3] R, G, B bytes of that frame converted by this rule, for the same geometry, scale / shift,
+ * ORE_PRE_REVERSE_CHANNELS and ORE_IMAGE_FLIP_H.  Hence an ORE_YUV_FMT_NV12 descriptor gives what the same frame
+ * gives in an NV12 list.
+ *  ore_image_yuv: plane[] are DEVICE pointers of any alignment; a plane the format does not use must be NULL.
+ *    stride[] are bytes between rows, 0 meaning dense; the bytes of a row ("row bytes") are, with wc = ceil(ws/2^sx):
+ *        plane[0]: ws (4 * ceil(ws/2) for YUYV);  plane[1]: wc (2 * ceil(ws/2) for NV12's UV);  plane[2]: wc.
+ *    plane[0] has hs rows, the others ceil(hs / 2^sy).  reserved must be 0.  A region of interest of a larger frame
+ *    is a descriptor whose pointers are offset to an origin (y0, x0) that is a multiple of (2^sy, 2^sx) -- for YUYV
+ *    an even column: plane[0] + y0 * stride[0] + x0 (2 * x0 for YUYV) and plane[k] + (y0 >> sy) * stride[k] +
+ *    (x0 >> sx) (times 2 for NV12's UV).  At any other origin the pixels would pair up with the wrong chroma
+ *    samples: rounding the origin is the caller's to do, the library sees only the pointers.
+ *  ore_image_check_yuv: host only.  Per descriptor, in this order: the format is one of ore_yuv_format; reserved
+ *    is 0; every plane the format uses is non-null and every other is NULL; sizes, geometry as in
+ *    ore_image_check_ex with c = 3; each used plane's stride is 0 or >= its row bytes; (rows - 1) * stride + row
+ *    bytes < 2^31 for each used plane (a plane of one row never steps a row); under ORE_FILTER_BILINEAR_AA the
+ *    ratio rule.  The first failing descriptor gives ORE_ERR_INVALID, a message with its index, the plane where
+ *    one is at fault and the reason, and *bad_index (when non-null).  n == 0 is ORE_OK.
+ *  ore_image_list_create_yuv: an ore_image_list with c = 3 whose format (ore_image_list_format: ORE_IMAGE_YUV) and
+ *    matrix are fixed at creation.  Every entry that takes a list -- ore_preprocess_list_u8, the model's _u8_list
+ *    runs, classifications and captures, chunked runs and views -- takes it as is.
+ *  ore_image_list_set_yuv / _set_yuv_ex: ore_image_list_set / _set_ex for a YUV list, with the same semantics
+ *    (check first, the old content kept on failure, stream-ordered upload from the pinned mirror,
+ *    ORE_ERR_INVALID inside a capture, n == 0 empties, flags as for ore_image_list_set_ex).  A set of another kind
+ *    on a YUV list, and these on a list of another kind (an NV12 list included), are ORE_ERR_INVALID and leave
+ *    the list unchanged. */
+typedef enum {
+  ORE_YUV_FMT_NV12 = 0,  /* plane[0] Y, plane[1] interleaved (U,V) pairs; chroma halved both ways */
+  ORE_YUV_FMT_YUYV = 1,  /* plane[0] packed Y0 U Y1 V groups of 4 bytes, ceil(ws/2) per row; chroma halved horizontally */
+  ORE_YUV_FMT_I444 = 2,  /* plane[0] Y, plane[1] U, plane[2] V; chroma (sx, sy) = (0, 0) */
+  ORE_YUV_FMT_I440 = 3,  /* (0, 1) */
+  ORE_YUV_FMT_I422 = 4,  /* (1, 0) */
+  ORE_YUV_FMT_I420 = 5,  /* (1, 1) */
+  ORE_YUV_FMT_I411 = 6,  /* (2, 0) */
+  ORE_YUV_FMT_GRAY = 7   /* plane[0] Y only; U = V = 128, so R = G = B */
+} ore_yuv_format;
+typedef struct ore_image_yuv {
+  const uint8_t* plane[3];  /* DEVICE pointers, any alignment; planes the format does not use must be NULL */
+  int64_t stride[3];        /* bytes between rows of each plane; 0 = dense */
+  int64_t hs, ws;           /* 1..16384, any parity */
+  int32_t format;           /* ore_yuv_format */
+  int32_t reserved;         /* must be 0 */
+  ore_resize g;             /* this frame's own {rh, rw, top, left} */
+} ore_image_yuv;            /* 104 bytes */
+ore_status ore_image_check_yuv(const ore_image_yuv* imgs, int64_t n, int64_t h, int64_t w, int32_t filter,
+                               int64_t* bad_index);
+ore_status ore_image_list_create_yuv(ore_ctx* ctx, int64_t capacity, int64_t h, int64_t w, int32_t filter,
+                                     int32_t matrix, ore_image_list** out);
+ore_status ore_image_list_set_yuv(ore_image_list* l, const ore_image_yuv* imgs, int64_t n);
+ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags, int64_t n);
 /* Row-wise top-k (extension; no reference counterpart -- the reference prints the full output tensor): the
  * k best elements of every row of x, in one launch (ore_topk.hip).  Rows are x->dims[0], the row length D
  * the product of the remaining dims (as for ore_softmax_f32); x->nstride >= D is honoured.  values and

@@ -38,12 +38,14 @@ struct ore_image_list {
   int64_t c = 0, h = 0, w = 0;
   int32_t filter = 0;                  // ore_resize_filter, fixed at creation
   int32_t format = 0;                  // ore_image_format, fixed at creation
-  int32_t matrix = 0;                  // ore_yuv_matrix of an NV12 list, fixed at creation
+  int32_t matrix = 0;                  // ore_yuv_matrix of an NV12 or YUV list, fixed at creation
   bool any_flip = false;               // the last set flipped a descriptor: launches take the kernels' flag-reading instance
   ore::ResizeImage* table = nullptr;   // device
   ore::ResizeImage* mirror = nullptr;  // pinned host: the source of the stream-ordered upload
   ore::Nv12Image* table_nv12 = nullptr;   // the same two of an NV12 list (table and mirror are then null)
   ore::Nv12Image* mirror_nv12 = nullptr;
+  ore::YuvImage* table_yuv = nullptr;     // and of a YUV list (ORE_IMAGE_YUV, ore_image_list_set_yuv)
+  ore::YuvImage* mirror_yuv = nullptr;
   hipEvent_t uploaded = nullptr;       // recorded after each upload; the next set waits on it before it rewrites the mirror
 };
 
@@ -240,7 +242,7 @@ ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_
 ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale, const float* shift, int32_t flags,
                        ResizeListParams* p);
 // the list conversion's launch under the list's format and filter (ore_preprocess_list_u8 and the model's
-// _u8_list entries); of an NV12 list p carries everything but the table and the matrix, which are the list's
+// _u8_list entries); of an NV12 or YUV list p carries everything but the table and the matrix, which are the list's
 void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& p);
 
 }  // namespace ore

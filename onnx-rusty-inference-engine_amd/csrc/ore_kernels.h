@@ -518,6 +518,39 @@ struct Nv12ListParams {
 };
 void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s);
 void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s);
+// the list conversions over YUV frames of any ore_yuv_format (ore_image_list_create_yuv): every format reduced by
+// ore_image_list_set_yuv to strided planes, so that the kernels never see the format.  Source pixel (r, j) is
+//     Y = y[r * yrow + j * ystep],  U = u[(r >> sy) * urow + (j >> sx) * cstep],  V = v[(r >> sy) * vrow + (j >> sx) * cstep]
+// converted as for an NV12 list.  Planar formats: ystep = cstep = 1 and three planes; NV12: u = uv, v = uv + 1,
+// cstep = 2; YUYV: ystep = 2, u = y + 1, v = y + 3, cstep = 4, one pitch, sx = 1; grey: u = v = null, every chroma
+// term zero.  The kernels rely on two of these being what they say: cstep == 2 IS the pair layout (v == u + 1,
+// sx = 1; a pair is one two-byte load) and ystep == 2 IS the packed one (luma and chroma of a pixel, or of a run
+// of taps, come out of the same dwords).
+struct YuvImage {
+  const unsigned char* y;   // row 0, column 0 of the luma samples; any alignment
+  const unsigned char* u;   // row 0, sample 0 of U; null: a grey frame (U = V = 128)
+  const unsigned char* v;   // the same of V
+  int Hs, Ws;               // <= RESIZE_MAX; chroma has ceil(Hs / 2^sy) rows of ceil(Ws / 2^sx) samples
+  int yrow, urow, vrow;     // bytes between rows; offsets inside a plane stay below 2^31
+  int ystep, cstep;         // bytes between luma samples (1, 2) and between chroma samples (1, 2, 4) of a row
+  int sx, sy;               // chroma subsampling shifts: 0..2 and 0..1
+  int Rh, Rw, top, left;
+  int flip;                 // as in ResizeImage; 80 bytes: an 8-byte multiple
+};
+struct YuvListParams {
+  const YuvImage* table;   // image i of the launch is table[first + i]
+  long long first;
+  float* y;                // [N][3][H][W] at an image stride of y_nstride elements
+  long long N;
+  long long y_nstride;
+  int H, W;
+  YuvMatrix m;
+  int plane[3];            // indexed by R, G, B
+  float scale[3], shift[3];
+  int flips;               // as ResizeListParams::flips
+};
+void launch_resize_yuv_list(const YuvListParams& p, hipStream_t s);
+void launch_resize_aa_yuv_list(const YuvListParams& p, hipStream_t s);
 // row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,

@@ -211,6 +211,24 @@ void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& 
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   const bool capturing = ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
   p.flips = l->any_flip || capturing;
+  if (l->format == ORE_IMAGE_YUV) {
+    YuvListParams q{};
+    q.table = l->table_yuv;
+    q.first = p.first; q.y = p.y; q.N = p.N; q.y_nstride = p.y_nstride;
+    q.H = p.H; q.W = p.W;
+    q.flips = p.flips;
+    yuv_matrix(l->matrix, &q.m);  // checked at creation
+    for (int s = 0; s < 3; ++s) {
+      q.plane[s] = p.plane[s];
+      q.scale[s] = p.scale[s];
+      q.shift[s] = p.shift[s];
+    }
+    if (l->filter == ORE_FILTER_BILINEAR_AA)
+      launch_resize_aa_yuv_list(q, ctx->stream);
+    else
+      launch_resize_yuv_list(q, ctx->stream);
+    return;
+  }
   if (l->format == ORE_IMAGE_NV12) {
     Nv12ListParams q{};
     q.table = l->table_nv12;
@@ -1154,20 +1172,98 @@ ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h
   return ORE_OK;
 }
 
+// What an ore_yuv_format is, for ore_image_check_yuv and for ore_image_list_set_yuv's reduction to strided planes
+// (YuvImage): the planes in use, the chroma shifts, and the bytes between the luma and the chroma samples of a row.
+struct YuvLayout {
+  const char* name;
+  int planes;  // plane[0 .. planes) are in use
+  int sx, sy;
+  int ystep, cstep;
+};
+
+static const YuvLayout* yuv_layout(int32_t format) {
+  static const YuvLayout table[] = {
+      {"NV12", 2, 1, 1, 1, 2}, {"YUYV", 1, 1, 0, 2, 4}, {"I444", 3, 0, 0, 1, 1}, {"I440", 3, 0, 1, 1, 1},
+      {"I422", 3, 1, 0, 1, 1}, {"I420", 3, 1, 1, 1, 1}, {"I411", 3, 2, 0, 1, 1}, {"GRAY", 1, 0, 0, 1, 0},
+  };
+  return format >= 0 && format < int32_t(sizeof(table) / sizeof(table[0])) ? &table[format] : nullptr;
+}
+
+// rows of plane k of an hs x ws frame, and the bytes of one
+static long long yuv_plane_rows(const YuvLayout& f, int k, long long hs) { return k == 0 ? hs : (hs + (1 << f.sy) - 1) >> f.sy; }
+static long long yuv_plane_row_bytes(const YuvLayout& f, int k, long long ws) {
+  if (k == 0) return f.ystep == 2 ? 4 * ((ws + 1) / 2) : ws;
+  return ((ws + (1 << f.sx) - 1) >> f.sx) * f.cstep;
+}
+
+ore_status ore_image_check_yuv(const ore_image_yuv* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
+  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+    return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
+  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
+  PreprocParams q;  // the output size: the direct conversion's checks, with the three channels a frame converts to
+  if (ore_status st = preproc_params(nullptr, h, w, 3, nullptr, nullptr, 0, &q)) return st;
+  if (n == 0) return ORE_OK;
+  if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  for (int64_t i = 0; i < n; ++i) {
+    const ore_image_yuv& d = imgs[i];
+    const ore_resize& g = d.g;
+    const long long hs = d.hs, ws = d.ws;
+    const YuvLayout* f = yuv_layout(d.format);
+    ore_status st = ORE_OK;
+    if (!f)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: unknown YUV format %d", (long long)i, int(d.format));
+    else if (d.reserved != 0)
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: reserved is %d, it must be 0", (long long)i, int(d.reserved));
+    // from here on a rule is tried while none has failed, and f is then non-null
+    for (int k = 0; !st && k < 3; ++k) {
+      if (k < f->planes && !d.plane[k])
+        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null plane %d pointer (%s has %d)", (long long)i, k, f->name, f->planes);
+      else if (k >= f->planes && d.plane[k])
+        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: plane %d must be null (%s has %d)", (long long)i, k, f->name, f->planes);
+    }
+    if (!st && (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX))
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
+                     ws, (long long)g.rh, (long long)g.rw, RESIZE_MAX);
+    if (!st && (!resize_axis_ok(hs, g.rh, g.top, h) || !resize_axis_ok(ws, g.rw, g.left, w)))
+      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
+                     (long long)i, (long long)h, (long long)w, (long long)g.top, (long long)g.left, (long long)g.rh, (long long)g.rw);
+    for (int k = 0; !st && k < f->planes; ++k) {
+      const long long rb = yuv_plane_row_bytes(*f, k, ws), ps = d.stride[k];
+      if (ps != 0 && ps < rb)
+        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: plane %d stride %lld below its %lld row bytes", (long long)i, k, ps, rb);
+    }
+    for (int k = 0; !st && k < f->planes; ++k) {
+      const long long rows = yuv_plane_rows(*f, k, hs), rb = yuv_plane_row_bytes(*f, k, ws), ps = d.stride[k];
+      if (rows > 1 && (!fits_i32(ps) || !fits_i32((rows - 1) * (ps ? ps : rb) + rb)))  // a one-row plane never steps a row
+        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: plane %d: %lld rows at a stride of %lld bytes reach past 2^31 bytes",
+                       (long long)i, k, rows, ps);
+    }
+    if (!st)
+      if (const char* axis = filter == ORE_FILTER_BILINEAR_AA ? aa_bad_axis(hs, ws, g) : nullptr)
+        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
+                       (long long)i, ORE_AA_MAX_RATIO, axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
+    if (st) {
+      if (bad_index) *bad_index = i;
+      return st;
+    }
+  }
+  return ORE_OK;
+}
+
 ore_status ore_image_list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, ore_image_list** out) {
   return ore_image_list_create_ex(ctx, capacity, c, h, w, ORE_FILTER_BILINEAR, out);
 }
 
 int32_t ore_image_list_filter(ore_image_list* l) { return l ? l->filter : ORE_FILTER_BILINEAR; }
 
-// ore_image_list_create_ex and ore_image_list_create_nv12: the list and the table and mirror of its format
+// ore_image_list_create_ex, _create_nv12 and _create_yuv: the list and the table and mirror of its format
 static ore_status list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter, int32_t format,
                               int32_t matrix, ore_image_list** out) {
   if (!ctx || !out) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
     return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   YuvMatrix ym;
-  if (format == ORE_IMAGE_NV12 && !yuv_matrix(matrix, &ym))
+  if (format != ORE_IMAGE_INTERLEAVED && !yuv_matrix(matrix, &ym))
     return set_error(ctx, ORE_ERR_INVALID, "unknown YUV matrix %d", int(matrix));
   PreprocParams q;
   if (ore_status st = preproc_params(ctx, h, w, c, nullptr, nullptr, 0, &q)) return st;
@@ -1180,11 +1276,11 @@ static ore_status list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t
   l->c = c; l->h = h; l->w = w;
   l->filter = filter;
   l->format = format;
-  l->matrix = format == ORE_IMAGE_NV12 ? matrix : 0;
-  const bool nv12 = format == ORE_IMAGE_NV12;
-  const size_t bytes = size_t(capacity) * (nv12 ? sizeof(Nv12Image) : sizeof(ResizeImage));
-  void** table = nv12 ? reinterpret_cast<void**>(&l->table_nv12) : reinterpret_cast<void**>(&l->table);
-  void** mirror = nv12 ? reinterpret_cast<void**>(&l->mirror_nv12) : reinterpret_cast<void**>(&l->mirror);
+  l->matrix = format != ORE_IMAGE_INTERLEAVED ? matrix : 0;
+  const bool nv12 = format == ORE_IMAGE_NV12, yuv = format == ORE_IMAGE_YUV;
+  const size_t bytes = size_t(capacity) * (yuv ? sizeof(YuvImage) : nv12 ? sizeof(Nv12Image) : sizeof(ResizeImage));
+  void** table = yuv ? reinterpret_cast<void**>(&l->table_yuv) : nv12 ? reinterpret_cast<void**>(&l->table_nv12) : reinterpret_cast<void**>(&l->table);
+  void** mirror = yuv ? reinterpret_cast<void**>(&l->mirror_yuv) : nv12 ? reinterpret_cast<void**>(&l->mirror_nv12) : reinterpret_cast<void**>(&l->mirror);
   // the table holds device addresses and geometry: never filled (device_alloc, own = false)
   if (device_alloc(ctx, table, bytes, false) != hipSuccess || hipHostMalloc(mirror, bytes, hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&l->uploaded, hipEventDisableTiming) != hipSuccess) {
@@ -1206,6 +1302,11 @@ ore_status ore_image_list_create_nv12(ore_ctx* ctx, int64_t capacity, int64_t h,
   return list_create(ctx, capacity, 3, h, w, filter, ORE_IMAGE_NV12, matrix, out);
 }
 
+ore_status ore_image_list_create_yuv(ore_ctx* ctx, int64_t capacity, int64_t h, int64_t w, int32_t filter, int32_t matrix,
+                                     ore_image_list** out) {
+  return list_create(ctx, capacity, 3, h, w, filter, ORE_IMAGE_YUV, matrix, out);
+}
+
 int32_t ore_image_list_format(ore_image_list* l) { return l ? l->format : ORE_IMAGE_INTERLEAVED; }
 
 int32_t ore_image_list_matrix(ore_image_list* l) { return l ? l->matrix : ORE_YUV_BT601; }
@@ -1221,6 +1322,8 @@ ore_status ore_image_list_destroy(ore_image_list* l) {
   if (l->table) (void)hipFree(l->table);
   if (l->mirror_nv12) (void)hipHostFree(l->mirror_nv12);
   if (l->table_nv12) (void)hipFree(l->table_nv12);
+  if (l->mirror_yuv) (void)hipHostFree(l->mirror_yuv);
+  if (l->table_yuv) (void)hipFree(l->table_yuv);
   delete l;
   return ORE_OK;
 }
@@ -1262,6 +1365,8 @@ ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs
 ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, int64_t n) {
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
+  if (l->format == ORE_IMAGE_YUV)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_nv12 on a YUV list: ore_image_list_set_yuv is its entry");
   if (l->format != ORE_IMAGE_NV12)
     return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_nv12 on a list of interleaved images: ore_image_list_set is its entry");
   int64_t bad = -1;
@@ -1293,6 +1398,64 @@ ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* i
   return ORE_OK;
 }
 
+static_assert(sizeof(ore_image_yuv) == 104, "ore_image_yuv is part of the ABI");
+static_assert(sizeof(YuvImage) == 80 && sizeof(YuvImage) % 8 == 0, "the pointers of a YuvImage table stay aligned");
+
+ore_status ore_image_list_set_yuv(ore_image_list* l, const ore_image_yuv* imgs, int64_t n) {
+  return ore_image_list_set_yuv_ex(l, imgs, nullptr, n);
+}
+
+ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags, int64_t n) {
+  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
+  ore_ctx* ctx = l->ctx;
+  if (l->format == ORE_IMAGE_NV12)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_yuv on an NV12 list: ore_image_list_set_nv12 is its entry");
+  if (l->format != ORE_IMAGE_YUV)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_yuv on a list of interleaved images: ore_image_list_set is its entry");
+  int64_t bad = -1;
+  if (ore_image_check_yuv(imgs, n, l->h, l->w, l->filter, &bad)) {
+    ctx->err = ore_last_error(nullptr);
+    return ORE_ERR_INVALID;
+  }
+  if (ore_status st = list_check_flags(ctx, flags, n)) return st;
+  if (ore_status st = list_set_begin(l, n)) return st;
+  if (n == 0) return ORE_OK;
+  bool any_flip = false;
+  for (int64_t i = 0; i < n; ++i) {
+    const ore_image_yuv& d = imgs[i];
+    const YuvLayout& f = *yuv_layout(d.format);  // checked
+    int pitch[3] = {0, 0, 0};  // dense where 0, and where no row is ever stepped
+    for (int k = 0; k < f.planes; ++k)
+      pitch[k] = int(yuv_plane_rows(f, k, d.hs) > 1 && d.stride[k] ? d.stride[k] : yuv_plane_row_bytes(f, k, d.ws));
+    // the format ends here: the kernels see three strided planes
+    YuvImage& r = l->mirror_yuv[i];
+    r = YuvImage{};
+    r.y = d.plane[0];
+    r.yrow = pitch[0];
+    if (f.ystep == 2) {  // YUYV: U and V inside the luma plane's groups
+      r.u = d.plane[0] + 1; r.v = d.plane[0] + 3;
+      r.urow = r.vrow = pitch[0];
+    } else if (f.planes == 2) {  // NV12: V one byte after U
+      r.u = d.plane[1]; r.v = d.plane[1] + 1;
+      r.urow = r.vrow = pitch[1];
+    } else if (f.planes == 3) {
+      r.u = d.plane[1]; r.v = d.plane[2];
+      r.urow = pitch[1]; r.vrow = pitch[2];
+    }  // grey: no chroma, u and v stay null
+    r.Hs = int(d.hs); r.Ws = int(d.ws);
+    r.ystep = f.ystep; r.cstep = f.cstep;
+    r.sx = f.sx; r.sy = f.sy;
+    r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
+    r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
+    any_flip |= r.flip != 0;
+  }
+  ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_yuv, l->mirror_yuv, size_t(n) * sizeof(YuvImage), hipMemcpyHostToDevice, ctx->stream));
+  ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
+  l->count = n;
+  l->any_flip = any_flip;
+  return ORE_OK;
+}
+
 ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n) {
   return ore_image_list_set_ex(l, imgs, nullptr, n);
 }
@@ -1300,6 +1463,8 @@ ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64
 ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, int64_t n) {
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
+  if (l->format == ORE_IMAGE_YUV)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set on a YUV list: ore_image_list_set_yuv is its entry");
   if (l->format != ORE_IMAGE_INTERLEAVED)
     return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set on an NV12 list: ore_image_list_set_nv12 is its entry");
   int64_t bad = -1;

@@ -12,7 +12,8 @@
 // where this kernel already moves its bytes at the device-to-device copy rate, and was removed
 // (DESIGN.md 3.8b has the numbers).
 // Image bases are 64-bit; offsets inside one image stay below 2^31 (sizes <= RESIZE_MAX, C <= 4).
-// The list kernels exist twice: over interleaved bytes, and over NV12 planes converted on the fly (further down).
+// The list kernels exist three times: over interleaved bytes, over NV12 planes converted on the fly, and over the
+// strided planes every YUV format reduces to (both further down).
 #include <hip/hip_runtime.h>
 
 #include "ore_kernels.h"
@@ -278,10 +279,215 @@ __device__ __forceinline__ void aa_row_nv12(const AaNv12& d, int r, bool sx, con
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// YUV sources of any ore_yuv_format (ore_image_list_create_yuv): the NV12 fetch above generalised to strided planes
+// (YuvImage, ore_kernels.h).  ore_image_list_set_yuv reduced the format to three bases, three pitches, a luma and
+// a chroma byte step and the two subsampling shifts, so nothing here reads the format.  Those fields leave four ways
+// to fetch a pixel (YuvFetch), and the code is templated on them: the way is chosen ONCE per image (bilinear) or per
+// tap row (antialiased) from the descriptor -- one scalar load per workgroup, so the branch is wave-uniform -- and
+// the body it selects is branch-free, so that its loads issue together.  (Choosing per pixel instead, inside the
+// fetch, put each of the four taps' loads behind a wait of its own: 162 us against 109 us for 256 NV12 frames of
+// 1080 x 1920 under the plain filter)
+enum YuvFetch {
+  YUV_GREY = 0,    // u == null: Y alone, every chroma term zero
+  YUV_PLANES = 1,  // cstep == 1: Y, U and V by a byte load each
+  YUV_PAIRS = 2,   // cstep == 2: NV12's interleaved pairs, v == u + 1: Y by a byte, (U, V) by one two-byte load
+  YUV_PACKED = 3,  // ystep == 2: YUYV, a pixel's group Y0 U Y1 V is one dword
+};
+
+template <class D>
+__device__ __forceinline__ int yuv_fetch(const D& d) {
+  return d.ystep != 1 ? YUV_PACKED : !d.u ? YUV_GREY : d.cstep == 2 ? YUV_PAIRS : YUV_PLANES;
+}
+
+struct AaYuv {
+  const unsigned char* y;
+  const unsigned char* u;
+  const unsigned char* v;
+  int Hs, Ws, yrow, urow, vrow;
+  int ystep, cstep, sx, sy;
+  int Rh, Rw, top, left;
+  YuvMatrix m;
+};
+
+__device__ __forceinline__ AaYuv aa_image(const YuvImage& t, const YuvMatrix& m) {
+  AaYuv d;
+  d.y = t.y; d.u = t.u; d.v = t.v;
+  d.Hs = t.Hs; d.Ws = t.Ws; d.yrow = t.yrow; d.urow = t.urow; d.vrow = t.vrow;
+  d.ystep = t.ystep; d.cstep = t.cstep; d.sx = t.sx; d.sy = t.sy;
+  d.Rh = t.Rh; d.Rw = t.Rw; d.top = t.top; d.left = t.left;
+  d.m = m;
+  return d;
+}
+
+// the three rows source row r reads; u and v are null in a grey frame
+struct YuvRow {
+  const unsigned char* y;
+  const unsigned char* u;
+  const unsigned char* v;
+};
+
+template <class D>
+__device__ __forceinline__ YuvRow yuv_row(const D& d, int r) {
+  YuvRow w;
+  w.y = d.y + size_t(r) * size_t(d.yrow);
+  w.u = nullptr; w.v = nullptr;
+  if (d.u) {
+    const size_t cr = size_t(r >> d.sy);
+    w.u = d.u + cr * size_t(d.urow);
+    w.v = d.v + cr * size_t(d.vrow);
+  }
+  return w;
+}
+
+// the chroma terms of sample c of a row of planes or pairs; the pair is two bytes at any alignment, as nv12_chroma
+template <int F>
+__device__ __forceinline__ YuvChroma yuv_sample(const YuvMatrix& m, const YuvRow& w, int c) {
+  static_assert(F == YUV_PLANES || F == YUV_PAIRS, "grey rows have no chroma, packed rows carry it beside the luma");
+  if (F == YUV_PAIRS) {
+    unsigned short uv;
+    __builtin_memcpy(&uv, w.u + 2 * c, 2);
+    return yuv_chroma(m, int(uv & 0xffu), int(uv >> 8));
+  }
+  return yuv_chroma(m, int(w.u[c]), int(w.v[c]));
+}
+
+// R, G, B of source pixel j of a row
+template <int F, class D>
+__device__ __forceinline__ void yuv_pixel(const D& d, const YuvMatrix& m, const YuvRow& w, int j, int (&rgb)[3]) {
+  if constexpr (F == YUV_PACKED) {
+    unsigned g;
+    __builtin_memcpy(&g, w.y + 4 * (j >> 1), 4);
+    yuv_rgb(m, int((g >> (16 * (j & 1))) & 0xffu), yuv_chroma(m, int((g >> 8) & 0xffu), int(g >> 24)), rgb);
+  } else if constexpr (F == YUV_GREY) {
+    yuv_rgb(m, int(w.y[j]), YuvChroma{0, 0, 0}, rgb);  // U = V = 128
+  } else {
+    yuv_rgb(m, int(w.y[j]), yuv_sample<F>(m, w, j >> d.sx), rgb);
+  }
+}
+
+__device__ __forceinline__ void yuv_tap(const AaYuv& d, int ox, int col, int Y, const YuvChroma& k, int (&acc)[3]) {
+  const int u = resize_aa_weight(d.Ws, d.Rw, ox, col);
+  int rgb[3];
+  yuv_rgb(d.m, Y, k, rgb);
+#pragma unroll
+  for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
+}
+
+// The groups of four taps of a run over planes whose luma step is 1 (every format but YUYV), as aa_row_nv12 does
+// them: the four Y bytes as one dword at the run's own alignment, and each chroma sample those taps touch fetched
+// and multiplied out once -- four samples under SX = 0; two under SX = 1, three where the run starts on an odd
+// column; one under SX = 2, two where it does not start on a multiple of four; none for grey (SX = -1).  j steps
+// by four, so every group of the run starts on the same phase.  Returns the taps done; the rest go one by one.
+template <int F, int SX>
+__device__ __forceinline__ int aa_run_planar(const AaYuv& d, const YuvRow& w, const AaAxis& ax, int ox, int (&acc)[3]) {
+  static_assert((F == YUV_GREY) == (SX < 0), "SX = -1 stands for no chroma");
+  constexpr int S = SX < 0 ? 0 : SX;
+  constexpr int NK = SX < 0 ? 1 : ((2 + (1 << S)) >> S) + 1;
+  const int ph = ax.first & ((1 << S) - 1);
+  int j = 0;
+  for (; j + 4 <= ax.n; j += 4) {
+    const int col = ax.first + j;
+    unsigned yy;
+    __builtin_memcpy(&yy, w.y + col, 4);
+    YuvChroma k[NK];
+    if constexpr (SX < 0) {
+      k[0] = YuvChroma{0, 0, 0};
+    } else {
+      const int c0 = col >> S;
+      k[0] = yuv_sample<F>(d.m, w, c0);
+      // sample c0 + s exists where a tap of the group needs it: the last tap takes sample c0 + ((ph + 3) >> S)
+#pragma unroll
+      for (int s = 1; s < NK; ++s) k[s] = ((ph + 3) >> S) >= s ? yuv_sample<F>(d.m, w, c0 + s) : k[s - 1];
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      constexpr int last = NK - 1;
+      const int lo = t >> S, hi = lo + 1 < last ? lo + 1 : last;  // tap t takes sample (ph + t) >> S: lo or the next
+      const YuvChroma kt = ((ph + t) >> S) != lo ? k[hi] : k[lo < last ? lo : last];
+      yuv_tap(d, ox, col + t, int((yy >> (8 * t)) & 0xffu), kt, acc);
+    }
+  }
+  return j;
+}
+
+// The same groups of a YUYV row (luma step 2): row bytes are groups Y0 U Y1 V of two columns.  The two groups of
+// four taps from an even column carry their four lumas and both chroma pairs: two dword loads and nothing else; from
+// an odd column the taps reach into a third group, which is inside the row because its first column is a tap.
+__device__ __forceinline__ int aa_run_yuyv(const AaYuv& d, const YuvRow& w, const AaAxis& ax, int ox, int (&acc)[3]) {
+  const bool odd = (ax.first & 1) != 0;
+  int j = 0;
+  for (; j + 4 <= ax.n; j += 4) {
+    const int col = ax.first + j;
+    const unsigned char* gp = w.y + 4 * (col >> 1);
+    unsigned g0, g1, g2;
+    __builtin_memcpy(&g0, gp, 4);
+    __builtin_memcpy(&g1, gp + 4, 4);
+    g2 = g1;
+    if (odd) __builtin_memcpy(&g2, gp + 8, 4);
+    const YuvChroma k0 = yuv_chroma(d.m, int((g0 >> 8) & 0xffu), int(g0 >> 24));
+    const YuvChroma k1 = yuv_chroma(d.m, int((g1 >> 8) & 0xffu), int(g1 >> 24));
+    const YuvChroma k2 = odd ? yuv_chroma(d.m, int((g2 >> 8) & 0xffu), int(g2 >> 24)) : k1;
+    const YuvChroma kt[4] = {k0, odd ? k1 : k0, k1, k2};
+    const unsigned yt[4] = {odd ? g0 >> 16 : g0, odd ? g1 : g0 >> 16, odd ? g1 >> 16 : g1, odd ? g2 : g1 >> 16};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) yuv_tap(d, ox, col + t, int(yt[t] & 0xffu), kt[t], acc);
+  }
+  return j;
+}
+
+// g of source row r for resized column ox under one way to fetch and, for planes, one horizontal chroma shift
+template <int F, int SX>
+__device__ __forceinline__ void aa_row_yuv_as(const AaYuv& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[3]) {
+  const YuvRow w = yuv_row(d, r);
+  if (sx) {
+    int acc[3] = {0, 0, 0};
+    int j;
+    if constexpr (F == YUV_PACKED)
+      j = aa_run_yuyv(d, w, ax, ox, acc);
+    else
+      j = aa_run_planar<F, SX>(d, w, ax, ox, acc);
+    for (; j < ax.n; ++j) {
+      const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j);
+      int rgb[3];
+      yuv_pixel<F>(d, d.m, w, ax.first + j, rgb);
+#pragma unroll
+      for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) g[s] = float(acc[s]);
+  } else {
+    int a[3], b[3];
+    yuv_pixel<F>(d, d.m, w, ax.first, a);
+    yuv_pixel<F>(d, d.m, w, ax.i1, b);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) g[s] = lerp_rn(float(a[s]), float(b[s]), ax.t);
+  }
+}
+
+// g of source row r for resized column ox: aa_row over converted pixels, by the descriptor's way to fetch
+__device__ __forceinline__ void aa_row_yuv(const AaYuv& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[3]) {
+  switch (yuv_fetch(d)) {
+    case YUV_PACKED: return aa_row_yuv_as<YUV_PACKED, 1>(d, r, sx, ax, ox, g);
+    case YUV_GREY: return aa_row_yuv_as<YUV_GREY, -1>(d, r, sx, ax, ox, g);
+    case YUV_PAIRS: return aa_row_yuv_as<YUV_PAIRS, 1>(d, r, sx, ax, ox, g);  // pairs are NV12: sx = 1
+    default: break;
+  }
+  if (d.sx == 0) return aa_row_yuv_as<YUV_PLANES, 0>(d, r, sx, ax, ox, g);
+  if (d.sx == 1) return aa_row_yuv_as<YUV_PLANES, 1>(d, r, sx, ax, ox, g);
+  aa_row_yuv_as<YUV_PLANES, 2>(d, r, sx, ax, ox, g);
+}
+
 // g of source row r of an image, by the kind of its source
 template <int C>
 __device__ __forceinline__ void aa_src_row(const AaImage& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[C]) {
   aa_row<C>(d.x + size_t(r) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g);
+}
+
+template <int C>
+__device__ __forceinline__ void aa_src_row(const AaYuv& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[C]) {
+  static_assert(C == 3, "a YUV frame converts to three channels");
+  aa_row_yuv(d, r, sx, ax, ox, g);
 }
 
 template <int C>
@@ -402,6 +608,55 @@ __global__ __launch_bounds__(RS_THREADS) void resize_aa_nv12_list_kernel(const N
     aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, list_column<FLIP>(table[i].flip, p.W, q));
 }
 
+// the four pixels of a bilinear tap, fetched one way
+template <int F>
+__device__ __forceinline__ void yuv_quad(const YuvImage& d, const YuvMatrix& m, const YuvRow& w0, const YuvRow& w1,
+                                         const ResizeTap& tx, int (&a)[3], int (&b)[3], int (&c)[3], int (&e)[3]) {
+  yuv_pixel<F>(d, m, w0, tx.i0, a);
+  yuv_pixel<F>(d, m, w0, tx.i1, b);
+  yuv_pixel<F>(d, m, w1, tx.i0, c);
+  yuv_pixel<F>(d, m, w1, tx.i1, e);
+}
+
+// the YUV list kernels: the NV12 pair over the strided-plane descriptor, which is one scalar load per workgroup as there
+template <bool FLIP>
+__global__ __launch_bounds__(RS_THREADS) void resize_yuv_list_kernel(const YuvImage* __restrict__ table, YuvListParams p) {
+  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const YuvImage d = table[i];
+    const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
+    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_column<FLIP>(d.flip, p.W, q));
+    const YuvRow w0 = yuv_row(d, ty.i0), w1 = yuv_row(d, ty.i1);
+    int a[3], b[3], c[3], e[3];
+    switch (yuv_fetch(d)) {
+      case YUV_PACKED: yuv_quad<YUV_PACKED>(d, p.m, w0, w1, tx, a, b, c, e); break;
+      case YUV_PAIRS: yuv_quad<YUV_PAIRS>(d, p.m, w0, w1, tx, a, b, c, e); break;
+      case YUV_PLANES: yuv_quad<YUV_PLANES>(d, p.m, w0, w1, tx, a, b, c, e); break;
+      default: yuv_quad<YUV_GREY>(d, p.m, w0, w1, tx, a, b, c, e); break;
+    }
+    float* yi = p.y + size_t(i) * size_t(p.y_nstride) + px;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
+      const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
+      yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
+    }
+  }
+}
+
+template <bool FLIP>
+__global__ __launch_bounds__(RS_THREADS) void resize_aa_yuv_list_kernel(const YuvImage* __restrict__ table, YuvListParams p) {
+  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
+    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, list_column<FLIP>(table[i].flip, p.W, q));
+}
+
 template <class K, class... A>
 void aa_launch(K k, const dim3& grid, hipStream_t s, A... a) {
   hipLaunchKernelGGL(k, grid, dim3(RS_THREADS), 0, s, a...);
@@ -455,6 +710,20 @@ void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s) {
   const long long hw = (long long)p.H * p.W;
   const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
   aa_launch(p.flips ? resize_aa_nv12_list_kernel<true> : resize_aa_nv12_list_kernel<false>, grid, s, p.table + p.first, p);
+}
+
+void launch_resize_yuv_list(const YuvListParams& p, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  const long long hw = (long long)p.H * p.W;
+  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  aa_launch(p.flips ? resize_yuv_list_kernel<true> : resize_yuv_list_kernel<false>, grid, s, p.table + p.first, p);
+}
+
+void launch_resize_aa_yuv_list(const YuvListParams& p, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  const long long hw = (long long)p.H * p.W;
+  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  aa_launch(p.flips ? resize_aa_yuv_list_kernel<true> : resize_aa_yuv_list_kernel<false>, grid, s, p.table + p.first, p);
 }
 
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s) {

@@ -32,7 +32,9 @@ FILTER_BILINEAR, FILTER_BILINEAR_AA = 0, 1  # ore_resize_filter (the _ex resize 
 AA_MAX_RATIO, AA_MAX_TAPS = 32, 64  # ORE_AA_MAX_RATIO / ORE_AA_MAX_TAPS: the antialiased filter's shrink limit and taps per axis
 YUV_BT601, YUV_BT709, YUV_BT601_FULL = 0, 1, 2  # ore_yuv_matrix (ore_yuv_to_rgb, the NV12 image lists)
 YUV_MATRICES = {"bt601": YUV_BT601, "bt709": YUV_BT709, "bt601_full": YUV_BT601_FULL}
-IMAGE_INTERLEAVED, IMAGE_NV12 = 0, 1  # ore_image_format (ore_image_list_format)
+IMAGE_INTERLEAVED, IMAGE_NV12, IMAGE_YUV = 0, 1, 2  # ore_image_format (ore_image_list_format)
+# ore_yuv_format: the per-descriptor plane layout of a YUV image list (ore_image_yuv.format)
+YUV_FORMATS = {"nv12": 0, "yuyv": 1, "i444": 2, "i440": 3, "i422": 4, "i420": 5, "i411": 6, "gray": 7}
 IMAGE_FLIP_H = 1  # ORE_IMAGE_FLIP_H: the per-descriptor flag of ore_image_list_set_ex / _set_nv12_ex
 MAX_VIEWS = 64  # ORE_MAX_VIEWS (ore_topk_mean_f32, ore_model_set_views)
 PAD = {"NOTSET": 0, "NOT_SET": 0, "SAME_UPPER": 1, "SAME_LOWER": 2, "VALID": 3}
@@ -50,6 +52,7 @@ EXPORTED = [
     "ore_model_set_input_resize_ex", "ore_ctx_set_resize_variant",
     "ore_yuv_to_rgb", "ore_image_check_nv12", "ore_image_list_create_nv12", "ore_image_list_set_nv12", "ore_image_list_format",
     "ore_image_list_matrix",
+    "ore_image_check_yuv", "ore_image_list_create_yuv", "ore_image_list_set_yuv", "ore_image_list_set_yuv_ex",
     "ore_preprocess_list_u8", "ore_model_run_u8_list", "ore_model_classify_u8_list", "ore_model_graph_capture_u8_list",
     "ore_model_graph_capture_classify_u8_list",
     "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
@@ -92,6 +95,16 @@ class ImageNv12(ctypes.Structure):
     from a row to the next of each plane (0: dense) and its own geometry."""
     _fields_ = [("y", ctypes.c_void_p), ("uv", ctypes.c_void_p), ("hs", ctypes.c_int64), ("ws", ctypes.c_int64),
                 ("y_stride", ctypes.c_int64), ("uv_stride", ctypes.c_int64), ("g", Resize)]
+
+
+class ImageYuv(ctypes.Structure):
+    """ore_image_yuv: one frame of a YUV image list: DEVICE pointers to up to three planes (unused ones null), the
+    bytes from a row to the next of each (0: dense), its size, its ore_yuv_format and its own geometry."""
+    _fields_ = [("plane", ctypes.c_void_p * 3), ("stride", ctypes.c_int64 * 3), ("hs", ctypes.c_int64), ("ws", ctypes.c_int64),
+                ("format", ctypes.c_int32), ("reserved", ctypes.c_int32), ("g", Resize)]
+
+
+assert ctypes.sizeof(ImageYuv) == 104
 
 
 class ConvAttrs(ctypes.Structure):
@@ -169,6 +182,10 @@ def load():
         "ore_image_check_nv12": (i32, [ctypes.POINTER(ImageNv12), i64, i64, i64, i32, I64P]),
         "ore_image_list_create_nv12": (i32, [vp, i64, i64, i64, i32, i32, ctypes.POINTER(vp)]),
         "ore_image_list_set_nv12": (i32, [vp, ctypes.POINTER(ImageNv12), i64]),
+        "ore_image_check_yuv": (i32, [ctypes.POINTER(ImageYuv), i64, i64, i64, i32, I64P]),
+        "ore_image_list_create_yuv": (i32, [vp, i64, i64, i64, i32, i32, ctypes.POINTER(vp)]),
+        "ore_image_list_set_yuv": (i32, [vp, ctypes.POINTER(ImageYuv), i64]),
+        "ore_image_list_set_yuv_ex": (i32, [vp, ctypes.POINTER(ImageYuv), ctypes.POINTER(ctypes.c_uint32), i64]),
         "ore_image_list_format": (i32, [vp]),
         "ore_image_list_matrix": (i32, [vp]),
         "ore_model_set_input_resize_ex": (i32, [vp, i64, i64, ctypes.POINTER(Resize), i32]),

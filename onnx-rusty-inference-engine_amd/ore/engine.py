@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "yuv_to_rgb", "nv12_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "center_crop_geometry", "topk", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "center_crop_geometry", "topk", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -621,6 +621,177 @@ class Nv12ImageList(ImageList):
         else:
             words = _flip_words(flips, len(frames))
             check(load().ore_image_list_set_nv12_ex(self.h, arr, words, len(frames)), self.ctx.h)
+        self._images = tuple(frames)
+        return self
+
+
+# ore_yuv_format name -> (planes in use, sx, sy): the chroma shifts of include/ore.h
+_YUV_LAYOUT = {"nv12": (2, 1, 1), "yuyv": (1, 1, 0), "i444": (3, 0, 0), "i440": (3, 0, 1), "i422": (3, 1, 0),
+               "i420": (3, 1, 1), "i411": (3, 2, 0), "gray": (1, 0, 0)}
+
+
+def _yuv_plane_shapes(fmt: str, hs: int, ws: int):
+    """The shapes of the planes of an hs x ws frame of format fmt, as YuvImageList.set and yuv_planes_to_rgb take them."""
+    _, sx, sy = _YUV_LAYOUT[fmt]
+    hc, wc = -(-hs // (1 << sy)), -(-ws // (1 << sx))
+    if fmt == "yuyv":
+        return [(hs, wc, 4)]
+    if fmt == "nv12":
+        return [(hs, ws), (hc, wc, 2)]
+    if fmt == "gray":
+        return [(hs, ws)]
+    return [(hs, ws), (hc, wc), (hc, wc)]
+
+
+def _yuv_frame_parts(frame, name: str):
+    """(fmt, planes, ws or None) of a frame given as (fmt, plane, ...), with a trailing int width for YUYV only."""
+    if not isinstance(frame, (tuple, list)) or not frame or not isinstance(frame[0], str):
+        raise OreError(1, f"{name}: expected (format, plane, ...) with the format's name first")
+    fmt, *planes = frame
+    if fmt.lower() not in _YUV_LAYOUT:
+        raise OreError(1, f"{name}: format {fmt!r} is not one of {sorted(_YUV_LAYOUT)}")
+    fmt = fmt.lower()
+    ws = None
+    if fmt == "yuyv" and len(planes) == 2 and isinstance(planes[1], int):
+        ws = int(planes.pop())
+    if len(planes) != _YUV_LAYOUT[fmt][0]:
+        raise OreError(1, f"{name}: {fmt} has {_YUV_LAYOUT[fmt][0]} plane(s), got {len(planes)}")
+    return fmt, planes, ws
+
+
+def _yuv_frame_size(fmt: str, shape0, ws, name: str):
+    """(hs, ws) of a frame from the shape of its plane 0 (and, for YUYV, the stated width: a packed row of wc groups
+    is 2 wc columns wide, or 2 wc - 1 when the caller says so)."""
+    if fmt == "yuyv":
+        if len(shape0) != 3 or shape0[2] != 4:
+            raise OreError(1, f"{name}: plane 0: expected [Hs, ceil(Ws/2), 4] groups of Y0 U Y1 V, got {tuple(shape0)}")
+        hs, wc = int(shape0[0]), int(shape0[1])
+        if ws is None:
+            ws = 2 * wc
+        if ws not in (2 * wc, 2 * wc - 1):
+            raise OreError(1, f"{name}: a width of {ws} does not have {wc} groups")
+    else:
+        if len(shape0) != 2:
+            raise OreError(1, f"{name}: plane 0: expected [Hs, Ws], got {tuple(shape0)}")
+        hs, ws = int(shape0[0]), int(shape0[1])
+    if hs < 1 or ws < 1:
+        raise OreError(1, f"{name}: plane 0: empty plane {tuple(shape0)}")
+    return hs, ws
+
+
+def yuv_planes_to_rgb(fmt, planes, matrix="bt601_full", ws=None):
+    """A YUV frame on the host -> uint8 [Hs, Ws, 3]: pixel (r, j) takes Y at (r, j) and the chroma sample at
+    (r >> sy, j >> sx) through yuv_to_rgb; a grey frame has U = V = 128.  planes are uint8 arrays shaped as
+    YuvImageList.set takes them (ws: the width of a YUYV frame when it is odd).  These are the bytes a YuvImageList
+    resizes: image i of one equals image i of an ImageList fed this array."""
+    fmt, planes, ws = _yuv_frame_parts((fmt, *planes) + (() if ws is None else (int(ws),)), "planes")
+    planes = [np.asarray(p) for p in planes]
+    hs, ws = _yuv_frame_size(fmt, planes[0].shape, ws, "planes")
+    for k, (p, want) in enumerate(zip(planes, _yuv_plane_shapes(fmt, hs, ws))):
+        if p.dtype != np.uint8:
+            raise OreError(1, f"planes: plane {k}: expected uint8, got {p.dtype}")
+        if p.shape != want:
+            raise OreError(1, f"planes: plane {k}: expected {want} for a {hs} x {ws} {fmt} frame, got {p.shape}")
+    _, sx, sy = _YUV_LAYOUT[fmt]
+    rr, cc = np.arange(hs)[:, None] >> sy, np.arange(ws)[None, :] >> sx
+    if fmt == "yuyv":
+        g = planes[0]
+        y = g[:, :, 0::2].reshape(hs, -1)[:, :ws]
+        u, v = g[rr, cc, 1], g[rr, cc, 3]
+    elif fmt == "nv12":
+        y, u, v = planes[0], planes[1][rr, cc, 0], planes[1][rr, cc, 1]
+    elif fmt == "gray":
+        y = planes[0]
+        u = v = np.full((hs, ws), 128, np.uint8)
+    else:
+        y, u, v = planes[0], planes[1][rr, cc], planes[2][rr, cc]
+    return yuv_to_rgb(y, u, v, matrix)
+
+
+def _check_frame_yuv(frame, device: int, name: str):
+    """One frame of a YUV list, handed to the library as raw device pointers with a pitch each (on the pattern of
+    _check_frame_nv12): -> (format id, planes, hs, ws).  Every plane is a torch.uint8 CUDA tensor on the context's
+    device whose last dimension(s) are dense and whose rows do not overlap; views qualify."""
+    fmt, planes, ws = _yuv_frame_parts(frame, name)
+    for k, p in enumerate(planes):
+        _check_plane_u8(p, device, f"{name}: plane {k}")
+    hs, ws = _yuv_frame_size(fmt, tuple(planes[0].shape), ws, name)
+    for k, (p, want) in enumerate(zip(planes, _yuv_plane_shapes(fmt, hs, ws))):
+        if tuple(p.shape) != want:
+            raise OreError(1, f"{name}: plane {k}: expected {want} for a {hs} x {ws} {fmt} frame, got {tuple(p.shape)}")
+        inner = 1 if len(want) == 2 else want[2]  # bytes of one element of a row: 1, a UV pair, a YUYV group
+        dense = (inner, 1) if len(want) == 3 else (1,)
+        if tuple(p.stride()[1:]) != dense or p.stride(0) < want[1] * inner:
+            raise OreError(1, f"{name}: plane {k}: strides {tuple(p.stride())}: expected dense rows {dense} and a row stride >= {want[1] * inner}")
+    return _lib.YUV_FORMATS[fmt], planes, hs, ws
+
+
+class YuvImageList(ImageList):
+    """An ore_image_list of YUV frames of mixed layouts (ore_image_list_create_yuv): what a JPEG decoder leaves --
+    three planes, a packed YUYV plane, NV12 or a single Y plane, as each file's chroma subsampling dictates --
+    resized, cropped and normalised in ONE launch with the colour conversion inside it.  Image i is bit for bit
+    image i of an ImageList fed yuv_planes_to_rgb of the frame.  Three channels (R, G, B); the matrix (a JPEG's is
+    "bt601_full") and the filter are properties of the list, the layout is each frame's own.  Model.run_u8_list,
+    classify_u8_list, the captures and set_views take it as they take an ImageList."""
+
+    def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601_full", antialias: bool = False):
+        h, w = (int(v) for v in out_hw)
+        self.ctx = ctx
+        self.capacity = int(capacity)
+        self.out_hw = (h, w)
+        self.channels = 3
+        self.antialias = bool(antialias)
+        self.matrix = _yuv_matrix(matrix)
+        self._images = ()
+        self.h = None
+        hnd = ctypes.c_void_p()
+        check(load().ore_image_list_create_yuv(ctx.h, self.capacity, h, w, _filter(antialias), self.matrix,
+                                               ctypes.byref(hnd)), ctx.h)
+        self.h = hnd
+
+    def _descriptors(self, frames, geometries, short):
+        """The host checks of set(): the ore_image_yuv array of `frames`, before any library call."""
+        if geometries is not None and short is not None:
+            raise OreError(1, "set: pass geometries or short, not both")
+        frames = list(frames)
+        if len(frames) > self.capacity:
+            raise OreError(1, f"set: {len(frames)} frames exceed the list's capacity {self.capacity}")
+        if geometries is not None and len(geometries) != len(frames):
+            raise OreError(1, f"set: {len(geometries)} geometries for {len(frames)} frames")
+        arr = (_lib.ImageYuv * max(len(frames), 1))()
+        for i, f in enumerate(frames):
+            fmt, planes, hs, ws = _check_frame_yuv(f, self.ctx.device, f"frames[{i}]")
+            if geometries is not None:
+                resized, origin = geometries[i]
+            elif short is not None:
+                resized, origin = center_crop_geometry((hs, ws), short, self.out_hw)
+            else:
+                resized, origin = None, (0, 0)
+            for k, p in enumerate(planes):
+                arr[i].plane[k] = p.data_ptr()
+                arr[i].stride[k] = int(p.stride(0))
+            arr[i].hs, arr[i].ws = hs, ws
+            arr[i].format = fmt
+            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]")
+        return frames, arr
+
+    def set(self, frames, geometries=None, short=None, flips=None):
+        """ore_image_list_set_yuv: frames is a sequence of (fmt, plane, ...) with fmt one of "nv12" "yuyv" "i444"
+        "i440" "i422" "i420" "i411" "gray" and the planes uint8 CUDA tensors, views included (the pitches are the
+        tensors' row strides):
+            i4xx   y [Hs, Ws], u and v [ceil(Hs / 2^sy), ceil(Ws / 2^sx)]
+            nv12   y [Hs, Ws], uv [ceil(Hs/2), ceil(Ws/2), 2]
+            yuyv   one plane [Hs, ceil(Ws/2), 4] of Y0 U Y1 V groups; the width is twice the groups, or one less
+                   when given: ("yuyv", plane, ws)
+            gray   y [Hs, Ws]
+        A window of a larger frame must start at a row and column that are multiples of (2^sy, 2^sx).  Geometry,
+        flips (ore_image_list_set_yuv_ex), ordering and what a rejected set leaves behind are ImageList.set's."""
+        frames, arr = self._descriptors(frames, geometries, short)
+        if flips is None:
+            check(load().ore_image_list_set_yuv(self.h, arr, len(frames)), self.ctx.h)
+        else:
+            words = _flip_words(flips, len(frames))
+            check(load().ore_image_list_set_yuv_ex(self.h, arr, words, len(frames)), self.ctx.h)
         self._images = tuple(frames)
         return self
 
