@@ -303,6 +303,58 @@ ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, in
 ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter,
                                     ore_image_list** out);
 int32_t ore_image_list_filter(ore_image_list* l);
+/* Cubic resize (extension, the resize_cubic_* kernels in ore_resize.hip): the Keys cubic convolution kernel, plain
+ * and antialiased.  The two filters are values of the `filter` word next to ore_resize_filter, not members of it:
+ * bit 8 (ORE_FILTER_CUBIC_BIT) selects the cubic kernel, bit 0 stays "antialiased".  Every entry that takes a
+ * filter (ore_preprocess_resize_u8_ex, ore_image_check_ex / _nv12 / _yuv, ore_image_list_create_ex / _nv12 / _yuv,
+ * ore_model_set_input_resize_ex) accepts 0, 1, 256 and 257 and nothing else; ore_image_list_filter returns the
+ * whole word.  Geometry, descriptors, flips, NV12 / YUV conversion per tap, ORE_PRE_REVERSE_CHANNELS, output
+ * slices, staging, chunks, captures and views are those of the bilinear filters; ore_ctx_set_resize_variant does
+ * not concern these.  Every float operation below is rounded on its own (no FMA, IEEE division) and every constant
+ * is exact in binary, so numpy float32 reproduces the results bit for bit.
+ *
+ * ORE_FILTER_BICUBIC (a = -0.75: cv2.INTER_CUBIC, F.interpolate(mode="bicubic", align_corners=False) on floats).
+ * Per axis, S samples resized to D, resized index o (top + r for rows, left + q for columns):
+ *     num = (2 o + 1) S - D        (not clamped at 0: it may be negative)
+ *     i = floor(num / 2 D) (>= -1);  rem = num - 2 D i;  t = fdiv_rn((float)rem, (float)(2 D));  s = fsub_rn(1, t)
+ *     taps k = 0..3 read sample clamp(i - 1 + k, 0, S - 1)          (the border is replicated)
+ *     p1(z) = ((1.25 z - 2.25) z) z + 1       p2(z) = ((-0.75 z + 3.75) z - 6) z + 3     (left to right as written)
+ *     w0 = p2(fadd_rn(t, 1));  w1 = p1(t);  w2 = p1(s);  w3 = p2(fadd_rn(s, 1))
+ * Per output element of source channel cs, wx / wy the column / row weights:
+ *     per tap row k in order:  g_k = fmul_rn(wx0, x0);  g_k = fadd_rn(g_k, fmul_rn(wxj, xj)) for j = 1..3
+ *     v = fmul_rn(wy0, g_0);  v = fadd_rn(v, fmul_rn(wyk, g_k)) for k = 1..3
+ *     y = fadd_rn(fmul_rn(v, scale[ch]), shift[ch])
+ * There is no division by a weight sum and NO clamp to [0, 255]: the kernel's negative lobes overshoot at edges and
+ * the overshoot is kept, as F.interpolate keeps it on float tensors (PIL and cv2 clamp because they store bytes).
+ * There is no ratio rule: 16384 -> 1 is accepted, as under ORE_FILTER_BILINEAR.
+ *
+ * ORE_FILTER_BICUBIC_AA (a = -0.5: PIL's BICUBIC up to its rounding to bytes, F.interpolate(mode="bicubic",
+ * antialias=True), torchvision's Resize(interpolation=BICUBIC, antialias=True) on tensors).  Per axis, shrinking
+ * or not, with F = max(S, D), G = 2 F, c = (2 o + 1) S:
+ *     a_j = |(2 j + 1) D - c|;   taps: every j of [0, S - 1] with a_j < 2 G   (a contiguous, never empty run)
+ *     z_j = fdiv_rn((float)a_j, (float)G);   w_j = a_j < G ? q1(z_j) : q2(z_j)
+ *     q1(z) = ((1.5 z - 2.5) z) z + 1         q2(z) = ((-0.5 z + 2.5) z - 4) z + 2
+ *     W = +0; for j ascending: W = fadd_rn(W, w_j)                  (over the clipped run: the edges renormalise)
+ * S <= 16 D is required of every axis (ORE_CUBIC_AA_MAX_RATIO; ORE_ERR_INVALID naming the axis otherwise, in the
+ * position of the 32-times rule): a run is then at most 64 taps (ORE_AA_MAX_TAPS); an axis that does not shrink
+ * has at most 4.  Per output element, u_j, U the column weights and sum, v_r, V the row ones:
+ *     acc = +0;  per tap row r ascending:  g = +0; for j ascending: g = fadd_rn(g, fmul_rn(u_j, x[r,j,cs]));
+ *                                          acc = fadd_rn(acc, fmul_rn(v_r, g))
+ *     w = fdiv_rn(fdiv_rn(acc, V), U);   y = fadd_rn(fmul_rn(w, scale[ch]), shift[ch])
+ * Overshoot is kept here too.  With S == D on both axes either filter returns the source bytes exactly (weights
+ * 0, 1, 0, 0; a run whose weights are a single 1 and zeros, W = 1).
+ *  ore_resize_cubic_taps: one axis's table into HOST arrays (host only, as ore_resize_taps), for filter 256 or 257:
+ *    tap k of resized index origin + i reads source sample clamp(first[i] + k, 0, src - 1), k < ntaps[i].  Plain:
+ *    ntaps is 4, first may be negative (>= -2), sum is 1.0f.  Antialiased: the run lies inside the image and sum
+ *    is W.  weights, when non-null, is [count][ORE_AA_MAX_TAPS], zero padded.  ORE_ERR_INVALID: a null first,
+ *    ntaps or sum; then a filter other than 256 / 257; then a bad axis (as ore_resize_taps); then, under 257,
+ *    src > 16 resized. */
+#define ORE_FILTER_CUBIC_BIT 256
+#define ORE_FILTER_BICUBIC 256
+#define ORE_FILTER_BICUBIC_AA 257
+#define ORE_CUBIC_AA_MAX_RATIO 16
+ore_status ore_resize_cubic_taps(int64_t src, int64_t resized, int64_t origin, int64_t count, int32_t filter,
+                                 int32_t* first, int32_t* ntaps, float* weights, float* sum);
 /* NV12 image lists (extension, the *_nv12_list kernels in ore_resize.hip): frames as a video decoder leaves
  * them -- a full-resolution Y plane and a half-resolution plane of interleaved (U, V) pairs, each with its own
  * pitch -- straight into an image list, without a colour-conversion pass in between.  Chroma is taken nearest:

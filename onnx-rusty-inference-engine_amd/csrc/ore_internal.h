@@ -40,6 +40,7 @@ struct ore_image_list {
   int32_t format = 0;                  // ore_image_format, fixed at creation
   int32_t matrix = 0;                  // ore_yuv_matrix of an NV12 or YUV list, fixed at creation
   bool any_flip = false;               // the last set flipped a descriptor: launches take the kernels' flag-reading instance
+  int taps = 0;                        // ORE_FILTER_BICUBIC_AA: no column run of the last set is longer (sizes the kernels' LDS)
   ore::ResizeImage* table = nullptr;   // device
   ore::ResizeImage* mirror = nullptr;  // pinned host: the source of the stream-ordered upload
   ore::Nv12Image* table_nv12 = nullptr;   // the same two of an NV12 list (table and mirror are then null)

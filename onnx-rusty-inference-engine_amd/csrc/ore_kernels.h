@@ -484,6 +484,7 @@ struct ResizeListParams {
   int plane[4];
   float scale[4], shift[4];
   int flips;                 // 0: no descriptor of the launch is flipped, the flag-free instance of the kernel runs
+  int taps;                  // ORE_FILTER_BICUBIC_AA: no column run of a descriptor is longer (1..RESIZE_AA_MAX_TAPS)
 };
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s);
 // the same two conversions under ORE_FILTER_BILINEAR_AA: axes that shrink take the area-weighted filter of
@@ -515,6 +516,7 @@ struct Nv12ListParams {
   int plane[3];            // indexed by R, G, B as ResizeListParams is by source channel
   float scale[3], shift[3];
   int flips;               // as ResizeListParams::flips
+  int taps;                // as ResizeListParams::taps
 };
 void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s);
 void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s);
@@ -548,9 +550,16 @@ struct YuvListParams {
   int plane[3];            // indexed by R, G, B
   float scale[3], shift[3];
   int flips;               // as ResizeListParams::flips
+  int taps;                // as ResizeListParams::taps
 };
 void launch_resize_yuv_list(const YuvListParams& p, hipStream_t s);
 void launch_resize_aa_yuv_list(const YuvListParams& p, hipStream_t s);
+// every conversion above under the cubic filters (ORE_FILTER_BICUBIC; aa: ORE_FILTER_BICUBIC_AA, every axis within
+// RESIZE_CUBIC_AA_MAX_RATIO, checked by the caller): resize_cubic_kernel and its list forms, one thread per pixel
+void launch_resize_cubic_u8(const ResizeParams& p, bool aa, hipStream_t s);
+void launch_resize_cubic_u8_list(const ResizeListParams& p, bool aa, hipStream_t s);
+void launch_resize_cubic_nv12_list(const Nv12ListParams& p, bool aa, hipStream_t s);
+void launch_resize_cubic_yuv_list(const YuvListParams& p, bool aa, hipStream_t s);
 // row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,

@@ -160,17 +160,29 @@ static void copy_norm(const PreprocParams& q, P* p) {
   }
 }
 
-// the axis on which ORE_FILTER_BILINEAR_AA would shrink by more than ORE_AA_MAX_RATIO, or null
-static const char* aa_bad_axis(int64_t hs, int64_t ws, const ore_resize& g) {
-  if (!resize_axis_aa_ok(hs, g.rh)) return "rows";
-  if (!resize_axis_aa_ok(ws, g.rw)) return "columns";
+static bool filter_known(int32_t filter) {
+  return filter == ORE_FILTER_BILINEAR || filter == ORE_FILTER_BILINEAR_AA || filter == ORE_FILTER_BICUBIC ||
+         filter == ORE_FILTER_BICUBIC_AA;
+}
+
+// the most an antialiasing filter shrinks an axis (ORE_AA_MAX_RATIO, ORE_CUBIC_AA_MAX_RATIO); 0: no ratio rule
+static int filter_max_ratio(int32_t filter) {
+  return filter == ORE_FILTER_BILINEAR_AA ? ORE_AA_MAX_RATIO : filter == ORE_FILTER_BICUBIC_AA ? ORE_CUBIC_AA_MAX_RATIO : 0;
+}
+
+// the axis on which the filter would shrink by more than its ratio, or null
+static const char* aa_bad_axis(int32_t filter, int64_t hs, int64_t ws, const ore_resize& g) {
+  const int ratio = filter_max_ratio(filter);
+  if (!ratio) return nullptr;
+  if (hs > ratio * g.rh) return "rows";
+  if (ws > ratio * g.rw) return "columns";
   return nullptr;
 }
 
 ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
                          const float* scale, const float* shift, int32_t flags, ResizeParams* p, int32_t filter) {
   if (!g) return set_error(ctx, ORE_ERR_INVALID, "null resize geometry");
-  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+  if (!filter_known(filter))
     return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   PreprocParams q;  // c, the flags, the reversal and the output size: the direct conversion's checks
   if (ore_status st = preproc_params(ctx, h, w, c, scale, shift, flags, &q)) return st;
@@ -180,10 +192,9 @@ ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_
   if (!resize_axis_ok(hs, g->rh, g->top, h) || !resize_axis_ok(ws, g->rw, g->left, w))
     return set_error(ctx, ORE_ERR_INVALID, "resize: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
                      (long long)h, (long long)w, (long long)g->top, (long long)g->left, (long long)g->rh, (long long)g->rw);
-  if (filter == ORE_FILTER_BILINEAR_AA)
-    if (const char* axis = aa_bad_axis(hs, ws, *g))
-      return set_error(ctx, ORE_ERR_INVALID, "resize: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                       ORE_AA_MAX_RATIO, axis, (long long)(axis[0] == 'r' ? hs : ws), (long long)(axis[0] == 'r' ? g->rh : g->rw));
+  if (const char* axis = aa_bad_axis(filter, hs, ws, *g))
+    return set_error(ctx, ORE_ERR_INVALID, "resize: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
+                     filter_max_ratio(filter), axis, (long long)(axis[0] == 'r' ? hs : ws), (long long)(axis[0] == 'r' ? g->rh : g->rw));
   *p = ResizeParams{};
   p->Hs = int(hs); p->Ws = int(ws); p->C = int(c);
   p->Rh = int(g->rh); p->Rw = int(g->rw); p->top = int(g->top); p->left = int(g->left);
@@ -211,19 +222,23 @@ void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& 
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   const bool capturing = ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
   p.flips = l->any_flip || capturing;
+  p.taps = capturing || l->taps < 1 ? RESIZE_AA_MAX_TAPS : l->taps;  // likewise: a later set may bring longer runs
   if (l->format == ORE_IMAGE_YUV) {
     YuvListParams q{};
     q.table = l->table_yuv;
     q.first = p.first; q.y = p.y; q.N = p.N; q.y_nstride = p.y_nstride;
     q.H = p.H; q.W = p.W;
     q.flips = p.flips;
+    q.taps = p.taps;
     yuv_matrix(l->matrix, &q.m);  // checked at creation
     for (int s = 0; s < 3; ++s) {
       q.plane[s] = p.plane[s];
       q.scale[s] = p.scale[s];
       q.shift[s] = p.shift[s];
     }
-    if (l->filter == ORE_FILTER_BILINEAR_AA)
+    if (l->filter & ORE_FILTER_CUBIC_BIT)
+      launch_resize_cubic_yuv_list(q, l->filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
+    else if (l->filter == ORE_FILTER_BILINEAR_AA)
       launch_resize_aa_yuv_list(q, ctx->stream);
     else
       launch_resize_yuv_list(q, ctx->stream);
@@ -235,19 +250,24 @@ void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& 
     q.first = p.first; q.y = p.y; q.N = p.N; q.y_nstride = p.y_nstride;
     q.H = p.H; q.W = p.W;
     q.flips = p.flips;
+    q.taps = p.taps;
     yuv_matrix(l->matrix, &q.m);  // checked at creation
     for (int s = 0; s < 3; ++s) {
       q.plane[s] = p.plane[s];
       q.scale[s] = p.scale[s];
       q.shift[s] = p.shift[s];
     }
-    if (l->filter == ORE_FILTER_BILINEAR_AA)
+    if (l->filter & ORE_FILTER_CUBIC_BIT)
+      launch_resize_cubic_nv12_list(q, l->filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
+    else if (l->filter == ORE_FILTER_BILINEAR_AA)
       launch_resize_aa_nv12_list(q, ctx->stream);
     else
       launch_resize_nv12_list(q, ctx->stream);
     return;
   }
-  if (l->filter == ORE_FILTER_BILINEAR_AA)
+  if (l->filter & ORE_FILTER_CUBIC_BIT)
+    launch_resize_cubic_u8_list(p, l->filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
+  else if (l->filter == ORE_FILTER_BILINEAR_AA)
     launch_resize_aa_u8_list(p, ctx->stream);
   else
     launch_resize_u8_list(p, ctx->stream);
@@ -1044,6 +1064,46 @@ ore_status ore_resize_aa_taps(int64_t src, int64_t resized, int64_t origin, int6
   return ORE_OK;
 }
 
+ore_status ore_resize_cubic_taps(int64_t src, int64_t resized, int64_t origin, int64_t count, int32_t filter, int32_t* first,
+                                 int32_t* ntaps, float* weights, float* sum) {
+  if (!first || !ntaps || !sum) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  if (filter != ORE_FILTER_BICUBIC && filter != ORE_FILTER_BICUBIC_AA)
+    return set_error(nullptr, ORE_ERR_INVALID, "resize taps: filter %d is not a cubic filter", int(filter));
+  if (!resize_axis_ok(src, resized, origin, count))
+    return set_error(nullptr, ORE_ERR_INVALID, "resize taps: %lld samples resized to %lld (each 1..%d), [%lld, %lld + %lld) of them",
+                     (long long)src, (long long)resized, RESIZE_MAX, (long long)origin, (long long)origin, (long long)count);
+  if (filter == ORE_FILTER_BICUBIC_AA && !resize_axis_cubic_aa_ok(src, resized))
+    return set_error(nullptr, ORE_ERR_INVALID, "resize taps: the antialiasing filter shrinks an axis at most %d times, not %lld -> %lld",
+                     ORE_CUBIC_AA_MAX_RATIO, (long long)src, (long long)resized);
+  const int S = int(src), D = int(resized);
+  for (int64_t k = 0; k < count; ++k) {
+    const int o = int(origin + k);
+    float* w = weights ? weights + k * ORE_AA_MAX_TAPS : nullptr;
+    if (w)
+      for (int j = 0; j < ORE_AA_MAX_TAPS; ++j) w[j] = 0.f;
+    if (filter == ORE_FILTER_BICUBIC) {
+      const ResizeCubicTap r = resize_cubic_tap(S, D, o);
+      first[k] = r.first;
+      ntaps[k] = 4;
+      sum[k] = 1.0f;
+      if (w)
+        for (int j = 0; j < 4; ++j) w[j] = r.w[j];
+    } else {
+      const ResizeCubicSpan r = resize_cubic_aa_span(S, D, o);
+      first[k] = r.first;
+      ntaps[k] = r.n;
+      float W = 0.f;  // one rounded addition per tap, in ascending order
+      for (int j = 0; j < r.n; ++j) {
+        const float u = resize_cubic_aa_weight(S, D, o, r.first + j);
+        if (w) w[j] = u;
+        W = W + u;
+      }
+      sum[k] = W;
+    }
+  }
+  return ORE_OK;
+}
+
 ore_status ore_preprocess_resize_u8(ore_ctx* ctx, const uint8_t* x, int64_t n, int64_t hs, int64_t ws, int64_t c,
                                     const ore_resize* g, const float* scale, const float* shift, int32_t flags, ore_tensor* y) {
   return ore_preprocess_resize_u8_ex(ctx, x, n, hs, ws, c, g, ORE_FILTER_BILINEAR, scale, shift, flags, y);
@@ -1068,7 +1128,9 @@ ore_status ore_preprocess_resize_u8_ex(ore_ctx* ctx, const uint8_t* x, int64_t n
   p.N = n;
   p.y_nstride = nstride_of(y);
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (filter == ORE_FILTER_BILINEAR_AA)
+  if (filter & ORE_FILTER_CUBIC_BIT)
+    launch_resize_cubic_u8(p, filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
+  else if (filter == ORE_FILTER_BILINEAR_AA)
     launch_resize_aa_u8(p, ctx->stream);
   else
     launch_resize_u8(p, ctx->stream);
@@ -1082,7 +1144,7 @@ ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64
 
 ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int32_t filter,
                               int64_t* bad_index) {
-  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+  if (!filter_known(filter))
     return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
   PreprocParams q;  // c and the output size: the direct conversion's checks
@@ -1106,9 +1168,9 @@ ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, in
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: row stride %lld below ws*c = %lld", (long long)i, rs, ws * (long long)c);
     else if (hs > 1 && (!fits_i32(rs) || !fits_i32((hs - 1) * (rs ? rs : ws * c) + ws * c)))  // a one-row image never steps a row
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hs, rs);
-    else if (const char* axis = filter == ORE_FILTER_BILINEAR_AA ? aa_bad_axis(hs, ws, g) : nullptr)
+    else if (const char* axis = aa_bad_axis(filter, hs, ws, g))
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                     (long long)i, ORE_AA_MAX_RATIO, axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
+                     (long long)i, filter_max_ratio(filter), axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
     if (st) {
       if (bad_index) *bad_index = i;
       return st;
@@ -1132,7 +1194,7 @@ ore_status ore_yuv_to_rgb(int32_t matrix, const uint8_t* y, const uint8_t* u, co
 }
 
 ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
-  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+  if (!filter_known(filter))
     return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
   PreprocParams q;  // the output size: the direct conversion's checks, with the three channels a frame converts to
@@ -1161,9 +1223,9 @@ ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld y rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hs, ys);
     else if (hc > 1 && (!fits_i32(us) || !fits_i32((hc - 1) * (us ? us : wc2) + wc2)))
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld uv rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hc, us);
-    else if (const char* axis = filter == ORE_FILTER_BILINEAR_AA ? aa_bad_axis(hs, ws, g) : nullptr)
+    else if (const char* axis = aa_bad_axis(filter, hs, ws, g))
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                     (long long)i, ORE_AA_MAX_RATIO, axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
+                     (long long)i, filter_max_ratio(filter), axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
     if (st) {
       if (bad_index) *bad_index = i;
       return st;
@@ -1197,7 +1259,7 @@ static long long yuv_plane_row_bytes(const YuvLayout& f, int k, long long ws) {
 }
 
 ore_status ore_image_check_yuv(const ore_image_yuv* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
-  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+  if (!filter_known(filter))
     return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
   PreprocParams q;  // the output size: the direct conversion's checks, with the three channels a frame converts to
@@ -1239,9 +1301,9 @@ ore_status ore_image_check_yuv(const ore_image_yuv* imgs, int64_t n, int64_t h, 
                        (long long)i, k, rows, ps);
     }
     if (!st)
-      if (const char* axis = filter == ORE_FILTER_BILINEAR_AA ? aa_bad_axis(hs, ws, g) : nullptr)
+      if (const char* axis = aa_bad_axis(filter, hs, ws, g))
         st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                       (long long)i, ORE_AA_MAX_RATIO, axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
+                       (long long)i, filter_max_ratio(filter), axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
     if (st) {
       if (bad_index) *bad_index = i;
       return st;
@@ -1260,7 +1322,7 @@ int32_t ore_image_list_filter(ore_image_list* l) { return l ? l->filter : ORE_FI
 static ore_status list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter, int32_t format,
                               int32_t matrix, ore_image_list** out) {
   if (!ctx || !out) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (filter != ORE_FILTER_BILINEAR && filter != ORE_FILTER_BILINEAR_AA)
+  if (!filter_known(filter))
     return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   YuvMatrix ym;
   if (format != ORE_IMAGE_INTERLEAVED && !yuv_matrix(matrix, &ym))
@@ -1378,6 +1440,7 @@ ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* i
   if (ore_status st = list_set_begin(l, n)) return st;
   if (n == 0) return ORE_OK;
   bool any_flip = false;
+  int taps = 0;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_nv12& d = imgs[i];
     const int64_t hc = (d.hs + 1) / 2, wc = (d.ws + 1) / 2;
@@ -1390,11 +1453,13 @@ ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* i
     r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
     r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
     any_flip |= r.flip != 0;
+    if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
   }
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_nv12, l->mirror_nv12, size_t(n) * sizeof(Nv12Image), hipMemcpyHostToDevice, ctx->stream));
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
   l->any_flip = any_flip;
+  l->taps = taps;
   return ORE_OK;
 }
 
@@ -1421,6 +1486,7 @@ ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* img
   if (ore_status st = list_set_begin(l, n)) return st;
   if (n == 0) return ORE_OK;
   bool any_flip = false;
+  int taps = 0;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_yuv& d = imgs[i];
     const YuvLayout& f = *yuv_layout(d.format);  // checked
@@ -1448,11 +1514,13 @@ ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* img
     r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
     r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
     any_flip |= r.flip != 0;
+    if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
   }
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_yuv, l->mirror_yuv, size_t(n) * sizeof(YuvImage), hipMemcpyHostToDevice, ctx->stream));
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
   l->any_flip = any_flip;
+  l->taps = taps;
   return ORE_OK;
 }
 
@@ -1476,6 +1544,7 @@ ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, co
   if (ore_status st = list_set_begin(l, n)) return st;
   if (n == 0) return ORE_OK;
   bool any_flip = false;
+  int taps = 0;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_u8& d = imgs[i];
     ResizeImage& r = l->mirror[i];
@@ -1486,12 +1555,14 @@ ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, co
     r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
     r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
     any_flip |= r.flip != 0;
+    if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
   }
   // stream-ordered: launches submitted earlier read the old table, later ones the new
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table, l->mirror, size_t(n) * sizeof(ResizeImage), hipMemcpyHostToDevice, ctx->stream));
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
   l->any_flip = any_flip;
+  l->taps = taps;
   return ORE_OK;
 }
 

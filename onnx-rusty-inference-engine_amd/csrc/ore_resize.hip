@@ -662,7 +662,335 @@ void aa_launch(K k, const dim3& grid, hipStream_t s, A... a) {
   hipLaunchKernelGGL(k, grid, dim3(RS_THREADS), 0, s, a...);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// ORE_FILTER_BICUBIC and ORE_FILTER_BICUBIC_AA (include/ore.h has the arithmetic, ore_resize_geom.h the taps and
+// weights): float weights, every operation rounded on its own, no integer sums -- so nothing of the triangle
+// filter's run code above applies.  One thread per output pixel; one device body per filter over a source (Src):
+// where a row starts (at), the C ints of one of its pixels (px) and of four neighbours at once (px4: interleaved
+// bytes as C dwords).  The three kinds of source differ in nothing else.
+//
+// The antialiased filter's column weights are the same for every tap row of a pixel: they are computed once per
+// pixel into LDS, laid out [tap][thread] (stride 1 in the thread index: conflict-free; a thread reads only what it
+// wrote, so there is no barrier), while the row weight costs one division and one cubic per tap row.  The launch
+// sizes the LDS to the longest run its geometry can have (resize_cubic_aa_max_taps); workgroups are 128 threads so
+// that 64 taps are 32 KB.  DESIGN.md 3.8g has the variants measured.
+
+constexpr int CUBIC_AA_THREADS = 128;
+
+struct CubicGeom {
+  int Hs, Ws, Rh, Rw, top, left;
+};
+
+template <class T>
+__device__ __forceinline__ CubicGeom cubic_geom(const T& t) {
+  CubicGeom g;
+  g.Hs = t.Hs; g.Ws = t.Ws; g.Rh = t.Rh; g.Rw = t.Rw; g.top = t.top; g.left = t.left;
+  return g;
+}
+
+template <int C>
+struct CubicSrcU8 {
+  const unsigned char* x;
+  int row;  // bytes between rows
+  using Row = const unsigned char*;
+  __device__ __forceinline__ Row at(int r) const { return x + size_t(r) * size_t(row); }
+  __device__ __forceinline__ void px(Row w, int j, int (&v)[C]) const {
+#pragma unroll
+    for (int s = 0; s < C; ++s) v[s] = int(w[j * C + s]);
+  }
+  // pixels j .. j + 3, all inside the row: their 4 C bytes as C dword loads at the pixels' own (any) alignment
+  __device__ __forceinline__ void px4(Row w, int j, int (&v)[4][C]) const {
+    unsigned d[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) __builtin_memcpy(&d[i], w + j * C + 4 * i, 4);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int s = 0; s < C; ++s) {
+        const int k = t * C + s;
+        v[t][s] = int((d[k >> 2] >> (8 * (k & 3))) & 0xffu);
+      }
+  }
+};
+
+struct CubicSrcNv12 {
+  const unsigned char* y;
+  const unsigned char* uv;
+  int yrow, uvrow;
+  YuvMatrix m;
+  struct Row {
+    const unsigned char* yr;
+    const unsigned char* ur;
+  };
+  __device__ __forceinline__ Row at(int r) const {
+    return Row{y + size_t(r) * size_t(yrow), uv + size_t(r >> 1) * size_t(uvrow)};
+  }
+  __device__ __forceinline__ void px(const Row& w, int j, int (&v)[3]) const { nv12_pixel(m, w.yr, w.ur, j, v); }
+  __device__ __forceinline__ void px4(const Row& w, int j, int (&v)[4][3]) const {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) px(w, j + t, v[t]);
+  }
+};
+
+template <int F>
+struct CubicSrcYuv {
+  YuvImage d;
+  YuvMatrix m;
+  using Row = YuvRow;
+  __device__ __forceinline__ Row at(int r) const { return yuv_row(d, r); }
+  __device__ __forceinline__ void px(const Row& w, int j, int (&v)[3]) const { yuv_pixel<F>(d, m, w, j, v); }
+  __device__ __forceinline__ void px4(const Row& w, int j, int (&v)[4][3]) const {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) px(w, j + t, v[t]);
+  }
+};
+
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// ORE_FILTER_BICUBIC: 4 x 4 taps, the border replicated; the tap columns are clamped once, outside the rows
+template <int C, class Src, class P>
+__device__ __forceinline__ void cubic_pixel(const Src& src, const CubicGeom& g, const P& p, float* __restrict__ yi, int HW,
+                                            int px, int r, int q) {
+  const ResizeCubicTap ty = resize_cubic_tap(g.Hs, g.Rh, g.top + r);
+  const ResizeCubicTap tx = resize_cubic_tap(g.Ws, g.Rw, g.left + q);
+  int cj[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cj[j] = resize_clamp(tx.first + j, g.Ws);
+  float v[C];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const typename Src::Row w = src.at(resize_clamp(ty.first + k, g.Hs));
+    float gk[C];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int x[C];
+      src.px(w, cj[j], x);
+#pragma unroll
+      for (int s = 0; s < C; ++s) gk[s] = j == 0 ? mul_rn(tx.w[0], float(x[s])) : macc_rn(gk[s], tx.w[j], float(x[s]));
+    }
+#pragma unroll
+    for (int s = 0; s < C; ++s) v[s] = k == 0 ? mul_rn(ty.w[0], gk[s]) : macc_rn(v[s], ty.w[k], gk[s]);
+  }
+#pragma unroll
+  for (int s = 0; s < C; ++s) yi[size_t(p.plane[s]) * size_t(HW) + px] = norm_rn(v[s], p.scale[s], p.shift[s]);
+}
+
+// ORE_FILTER_BICUBIC_AA: u is this thread's column of the LDS weight table, tap j at u[j * CUBIC_AA_THREADS]
+template <int C, class Src, class P>
+__device__ __forceinline__ void cubic_aa_pixel(const Src& src, const CubicGeom& g, const P& p, float* __restrict__ yi, int HW,
+                                               int px, int r, int q, float* __restrict__ u) {
+  const int oy = g.top + r, ox = g.left + q;
+  const ResizeCubicSpan sx = resize_cubic_aa_span(g.Ws, g.Rw, ox);
+  const ResizeCubicSpan sy = resize_cubic_aa_span(g.Hs, g.Rh, oy);
+  float U = 0.f;
+  for (int j = 0; j < sx.n; ++j) {
+    const float w = resize_cubic_aa_weight(g.Ws, g.Rw, ox, sx.first + j);
+    u[j * CUBIC_AA_THREADS] = w;
+    U = add_rn(U, w);
+  }
+  float acc[C];
+#pragma unroll
+  for (int s = 0; s < C; ++s) acc[s] = 0.f;
+  float V = 0.f;
+  for (int i = 0; i < sy.n; ++i) {
+    const typename Src::Row w = src.at(sy.first + i);
+    const float v = resize_cubic_aa_weight(g.Hs, g.Rh, oy, sy.first + i);
+    V = add_rn(V, v);
+    float gs[C];
+#pragma unroll
+    for (int s = 0; s < C; ++s) gs[s] = 0.f;
+    int j = 0;
+    for (; j + 4 <= sx.n; j += 4) {  // four taps' fetches issue together; the sums stay in ascending order
+      int x[4][C];
+      src.px4(w, sx.first + j, x);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float uj = u[(j + t) * CUBIC_AA_THREADS];
+#pragma unroll
+        for (int s = 0; s < C; ++s) gs[s] = macc_rn(gs[s], uj, float(x[t][s]));
+      }
+    }
+    for (; j < sx.n; ++j) {
+      int x[C];
+      src.px(w, sx.first + j, x);
+      const float uj = u[j * CUBIC_AA_THREADS];
+#pragma unroll
+      for (int s = 0; s < C; ++s) gs[s] = macc_rn(gs[s], uj, float(x[s]));
+    }
+#pragma unroll
+    for (int s = 0; s < C; ++s) acc[s] = macc_rn(acc[s], v, gs[s]);
+  }
+#pragma unroll
+  for (int s = 0; s < C; ++s) {
+    const float t = acc[s] / V;
+    yi[size_t(p.plane[s]) * size_t(HW) + px] = norm_rn(t / U, p.scale[s], p.shift[s]);
+  }
+}
+
+// one pixel under either filter: AA selects the body (and with it the workgroup's size, cubic_threads)
+template <bool AA, int C, class Src, class P>
+__device__ __forceinline__ void cubic_any(const Src& src, const CubicGeom& g, const P& p, float* __restrict__ yi, int HW, int px,
+                                          int r, int q, float* __restrict__ u) {
+  if constexpr (AA)
+    cubic_aa_pixel<C>(src, g, p, yi, HW, px, r, q, u);
+  else
+    cubic_pixel<C>(src, g, p, yi, HW, px, r, q);
+}
+
+template <bool AA>
+constexpr int cubic_threads() { return AA ? CUBIC_AA_THREADS : RS_THREADS; }
+
+template <bool AA, int C>
+__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_kernel(ResizeParams p) {
+  extern __shared__ float cubic_lds[];
+  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  const CubicGeom g = cubic_geom(p);
+  const int row = p.Ws * p.C;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const CubicSrcU8<C> src{p.x + size_t(i) * size_t(p.Hs) * size_t(row), row};
+    cubic_any<AA, C>(src, g, p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, q, cubic_lds + threadIdx.x);
+  }
+}
+
+// the list descriptor is one scalar load per workgroup, as in resize_u8_list_kernel
+template <bool AA, int C, bool FLIP>
+__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_list_kernel(const ResizeImage* __restrict__ table,
+                                                                                ResizeListParams p) {
+  extern __shared__ float cubic_lds[];
+  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const ResizeImage d = table[i];
+    const CubicSrcU8<C> src{d.x, d.row};
+    cubic_any<AA, C>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r,
+                     list_column<FLIP>(d.flip, p.W, q), cubic_lds + threadIdx.x);
+  }
+}
+
+template <bool AA, bool FLIP>
+__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_nv12_list_kernel(const Nv12Image* __restrict__ table,
+                                                                                     Nv12ListParams p) {
+  extern __shared__ float cubic_lds[];
+  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const Nv12Image d = table[i];
+    const CubicSrcNv12 src{d.y, d.uv, d.yrow, d.uvrow, p.m};
+    cubic_any<AA, 3>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r,
+                     list_column<FLIP>(d.flip, p.W, q), cubic_lds + threadIdx.x);
+  }
+}
+
+// the way to fetch is chosen once per image from the descriptor (wave-uniform), as in resize_yuv_list_kernel
+template <bool AA, bool FLIP>
+__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_yuv_list_kernel(const YuvImage* __restrict__ table,
+                                                                                    YuvListParams p) {
+  extern __shared__ float cubic_lds[];
+  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const YuvImage d = table[i];
+    const CubicGeom g = cubic_geom(d);
+    float* yi = p.y + size_t(i) * size_t(p.y_nstride);
+    const int qq = list_column<FLIP>(d.flip, p.W, q);
+    float* u = cubic_lds + threadIdx.x;
+    switch (yuv_fetch(d)) {
+      case YUV_PACKED: cubic_any<AA, 3>(CubicSrcYuv<YUV_PACKED>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
+      case YUV_PAIRS: cubic_any<AA, 3>(CubicSrcYuv<YUV_PAIRS>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
+      case YUV_PLANES: cubic_any<AA, 3>(CubicSrcYuv<YUV_PLANES>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
+      default: cubic_any<AA, 3>(CubicSrcYuv<YUV_GREY>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
+    }
+  }
+}
+
+// grid, workgroup and LDS of a cubic launch: the plain filter takes no LDS; `taps` bounds the antialiased runs' columns
+template <bool AA, class K, class... A>
+void cubic_launch(K k, int H, int W, long long N, int taps, hipStream_t s, A... a) {
+  constexpr int T = cubic_threads<AA>();
+  const long long hw = (long long)H * W;
+  const dim3 grid(unsigned((hw + T - 1) / T), unsigned(N < 65535 ? N : 65535));
+  const size_t lds = AA ? size_t(taps) * T * sizeof(float) : 0;
+  hipLaunchKernelGGL(k, grid, dim3(T), lds, s, a...);
+}
+
+template <bool AA>
+void cubic_u8(const ResizeParams& p, hipStream_t s) {
+  const int taps = resize_cubic_aa_max_taps(p.Ws, p.Rw);
+  switch (p.C) {
+    case 1: return cubic_launch<AA>(resize_cubic_kernel<AA, 1>, p.H, p.W, p.N, taps, s, p);
+    case 2: return cubic_launch<AA>(resize_cubic_kernel<AA, 2>, p.H, p.W, p.N, taps, s, p);
+    case 3: return cubic_launch<AA>(resize_cubic_kernel<AA, 3>, p.H, p.W, p.N, taps, s, p);
+    default: return cubic_launch<AA>(resize_cubic_kernel<AA, 4>, p.H, p.W, p.N, taps, s, p);
+  }
+}
+
+template <bool AA, bool FLIP>
+void cubic_u8_list(const ResizeListParams& p, hipStream_t s) {
+  const ResizeImage* table = p.table + p.first;
+  switch (p.C) {
+    case 1: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 1, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
+    case 2: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 2, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
+    case 3: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 3, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
+    default: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 4, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
+  }
+}
+
 }  // namespace
+
+void launch_resize_cubic_u8(const ResizeParams& p, bool aa, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  aa ? cubic_u8<true>(p, s) : cubic_u8<false>(p, s);
+}
+
+// The list launches size the LDS by ResizeListParams::taps: the longest column run of the list's last set, or, where
+// a captured launch may meet the descriptors of a later set, the longest the ratio rule allows.
+
+void launch_resize_cubic_u8_list(const ResizeListParams& p, bool aa, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  if (aa)
+    p.flips ? cubic_u8_list<true, true>(p, s) : cubic_u8_list<true, false>(p, s);
+  else
+    p.flips ? cubic_u8_list<false, true>(p, s) : cubic_u8_list<false, false>(p, s);
+}
+
+void launch_resize_cubic_nv12_list(const Nv12ListParams& p, bool aa, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  const Nv12Image* table = p.table + p.first;
+  if (aa)
+    cubic_launch<true>(p.flips ? resize_cubic_nv12_list_kernel<true, true> : resize_cubic_nv12_list_kernel<true, false>, p.H, p.W,
+                       p.N, p.taps, s, table, p);
+  else
+    cubic_launch<false>(p.flips ? resize_cubic_nv12_list_kernel<false, true> : resize_cubic_nv12_list_kernel<false, false>, p.H,
+                        p.W, p.N, 0, s, table, p);
+}
+
+void launch_resize_cubic_yuv_list(const YuvListParams& p, bool aa, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  const YuvImage* table = p.table + p.first;
+  if (aa)
+    cubic_launch<true>(p.flips ? resize_cubic_yuv_list_kernel<true, true> : resize_cubic_yuv_list_kernel<true, false>, p.H, p.W,
+                       p.N, p.taps, s, table, p);
+  else
+    cubic_launch<false>(p.flips ? resize_cubic_yuv_list_kernel<false, true> : resize_cubic_yuv_list_kernel<false, false>, p.H,
+                        p.W, p.N, 0, s, table, p);
+}
 
 void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;

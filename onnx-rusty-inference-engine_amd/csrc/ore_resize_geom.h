@@ -98,4 +98,100 @@ ORE_RS_HD inline ResizeSpan resize_aa_span(int S, int D, int o) {
   return r;
 }
 
+// ---------------------------------------------------------------- cubic axes (ORE_FILTER_BICUBIC / _BICUBIC_AA)
+// The Keys cubic convolution kernel, its weights in float32 with every operation rounded on its own (never an
+// FMA, IEEE division), so that the kernels, ore_resize_cubic_taps and a numpy restatement agree bit for bit.
+// include/ore.h states both filters; the integer part and the weights are here for host and device alike.
+constexpr int RESIZE_CUBIC_AA_MAX_RATIO = 16;  // ORE_CUBIC_AA_MAX_RATIO: a run is then at most RESIZE_AA_MAX_TAPS
+
+// |z| <= 1 and 1 <= |z| <= 2 of the kernel, in Horner form: ((a z + b) z) z + 1 and ((a z + b) z + c) z + d
+ORE_RS_HD inline float cubic_near_rn(float a, float b, float z) {
+#pragma clang fp contract(off)
+  float r = a * z;
+  r = r + b;
+  r = r * z;
+  r = r * z;
+  return r + 1.0f;
+}
+
+ORE_RS_HD inline float cubic_far_rn(float a, float b, float c, float d, float z) {
+#pragma clang fp contract(off)
+  float r = a * z;
+  r = r + b;
+  r = r * z;
+  r = r + c;
+  r = r * z;
+  return r + d;
+}
+
+// ORE_FILTER_BICUBIC (a = -0.75; cv2.INTER_CUBIC, F.interpolate(mode="bicubic")): resized index o reads the four
+// samples clamp(first + k, 0, S - 1), k = 0..3, with weights w[k].  The source coordinate is that of resize_tap,
+// NOT clamped at 0: its floor i is -1 where (2 o + 1) S < D, so first = i - 1 lies in [-2, S - 2].
+struct ResizeCubicTap {
+  int first;
+  float w[4];
+};
+
+ORE_RS_HD inline ResizeCubicTap resize_cubic_tap(int S, int D, int o) {
+  const int num = (2 * o + 1) * S - D;  // > -2 D
+  const unsigned d2 = 2u * unsigned(D);
+  const int i = num < 0 ? -1 : int(unsigned(num) / d2);
+  const int rem = num - int(d2) * i;
+  const float t = float(rem) / float(d2);
+  const float s = 1.0f - t;
+  ResizeCubicTap r;
+  r.first = i - 1;
+  r.w[0] = cubic_far_rn(-0.75f, 3.75f, -6.0f, 3.0f, t + 1.0f);
+  r.w[1] = cubic_near_rn(1.25f, -2.25f, t);
+  r.w[2] = cubic_near_rn(1.25f, -2.25f, s);
+  r.w[3] = cubic_far_rn(-0.75f, 3.75f, -6.0f, 3.0f, s + 1.0f);
+  return r;
+}
+
+ORE_RS_HD inline int resize_clamp(int j, int S) { return j < 0 ? 0 : (j > S - 1 ? S - 1 : j); }
+
+// ORE_FILTER_BICUBIC_AA (a = -0.5; PIL's BICUBIC, F.interpolate(mode="bicubic", antialias=True)): with
+// F = max(S, D), G = 2 F and c = (2 o + 1) S the taps of resized index o are the samples j of [0, S - 1] with
+// a_j = |(2 j + 1) D - c| < 2 G, tap j weighing the kernel at a_j / G; the weights are divided by their sum over
+// the clipped run, so the edges renormalise.  S <= 16 D bounds a run at 64 taps; an axis that does not shrink
+// has at most 4.
+struct ResizeCubicSpan {
+  int first, n;  // taps first .. first + n - 1, 1 <= n <= resize_cubic_aa_max_taps(S, D)
+};
+
+ORE_RS_HD inline bool resize_axis_cubic_aa_ok(long long S, long long D) { return S <= RESIZE_CUBIC_AA_MAX_RATIO * D; }
+
+// The run in closed form, as resize_aa_span: (2 j + 1) D > c - 4 F gives first = floor((c - 4 F - D) / 2 D) + 1,
+// at least 0 (a negative numerator starts the run at sample 0); (2 j + 1) D < c + 4 F gives
+// last = floor((c + 4 F - D - 1) / 2 D), clipped to S - 1.
+ORE_RS_HD inline ResizeCubicSpan resize_cubic_aa_span(int S, int D, int o) {
+  const int F = S > D ? S : D;
+  const int c = (2 * o + 1) * S;
+  const unsigned d2 = 2u * unsigned(D);
+  const int lo = c - 4 * F - D;
+  const int first = lo < 0 ? 0 : int(unsigned(lo) / d2) + 1;
+  int last = int(unsigned(c + 4 * F - D - 1) / d2);
+  if (last > S - 1) last = S - 1;
+  ResizeCubicSpan r;
+  r.first = first;
+  r.n = last - first + 1;
+  return r;
+}
+
+// no run of the axis is longer: the odd numbers 2 j + 1 of an open interval of length 8 F / D
+ORE_RS_HD inline int resize_cubic_aa_max_taps(int S, int D) {
+  const int F = S > D ? S : D;
+  const int n = (4 * F + D - 1) / D;
+  return n < RESIZE_AA_MAX_TAPS ? n : RESIZE_AA_MAX_TAPS;
+}
+
+// weight of source sample j (a tap of o) before the division by the run's sum
+ORE_RS_HD inline float resize_cubic_aa_weight(int S, int D, int o, int j) {
+  const int G = 2 * (S > D ? S : D);
+  const int d = (2 * j + 1) * D - (2 * o + 1) * S;
+  const int a = d < 0 ? -d : d;
+  const float z = float(a) / float(G);
+  return a < G ? cubic_near_rn(1.5f, -2.5f, z) : cubic_far_rn(-0.5f, 2.5f, -4.0f, 2.0f, z);
+}
+
 }  // namespace ore

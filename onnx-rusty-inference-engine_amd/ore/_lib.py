@@ -29,6 +29,8 @@ ABI_VERSION = 2  # ORE_ABI_VERSION this binding was written against
 CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD = 0, 1  # ore_ctx_set_conv_algo (per-op ore_conv2d_f32)
 PRE_REVERSE_CHANNELS = 1  # ore_preprocess_u8 / _resize_u8 / ore_model_set_input_norm flag: RGB <-> BGR
 FILTER_BILINEAR, FILTER_BILINEAR_AA = 0, 1  # ore_resize_filter (the _ex resize entries)
+FILTER_CUBIC_BIT, FILTER_BICUBIC, FILTER_BICUBIC_AA = 256, 256, 257  # ORE_FILTER_BICUBIC*: values of the filter word beside the enum
+CUBIC_AA_MAX_RATIO = 16  # ORE_CUBIC_AA_MAX_RATIO: the antialiased cubic filter's shrink limit
 AA_MAX_RATIO, AA_MAX_TAPS = 32, 64  # ORE_AA_MAX_RATIO / ORE_AA_MAX_TAPS: the antialiased filter's shrink limit and taps per axis
 YUV_BT601, YUV_BT709, YUV_BT601_FULL = 0, 1, 2  # ore_yuv_matrix (ore_yuv_to_rgb, the NV12 image lists)
 YUV_MATRICES = {"bt601": YUV_BT601, "bt709": YUV_BT709, "bt601_full": YUV_BT601_FULL}
@@ -49,7 +51,7 @@ EXPORTED = [
     "ore_resize_taps", "ore_preprocess_resize_u8", "ore_model_set_input_resize",
     "ore_image_check", "ore_image_list_create", "ore_image_list_destroy", "ore_image_list_set", "ore_image_list_count",
     "ore_resize_aa_taps", "ore_preprocess_resize_u8_ex", "ore_image_check_ex", "ore_image_list_create_ex", "ore_image_list_filter",
-    "ore_model_set_input_resize_ex", "ore_ctx_set_resize_variant",
+    "ore_model_set_input_resize_ex", "ore_ctx_set_resize_variant", "ore_resize_cubic_taps",
     "ore_yuv_to_rgb", "ore_image_check_nv12", "ore_image_list_create_nv12", "ore_image_list_set_nv12", "ore_image_list_format",
     "ore_image_list_matrix",
     "ore_image_check_yuv", "ore_image_list_create_yuv", "ore_image_list_set_yuv", "ore_image_list_set_yuv_ex",
@@ -174,6 +176,7 @@ def load():
         "ore_image_list_count": (i64, [vp]),
         "ore_preprocess_list_u8": (i32, [vp, vp, F32P, F32P, i32, T]),
         "ore_resize_aa_taps": (i32, [i64, i64, i64, i64, vp, vp, vp, vp]),
+        "ore_resize_cubic_taps": (i32, [i64, i64, i64, i64, i32, vp, vp, vp, vp]),
         "ore_preprocess_resize_u8_ex": (i32, [vp, vp, i64, i64, i64, i64, ctypes.POINTER(Resize), i32, F32P, F32P, i32, T]),
         "ore_image_check_ex": (i32, [ctypes.POINTER(ImageU8), i64, i64, i64, i64, i32, I64P]),
         "ore_image_list_create_ex": (i32, [vp, i64, i64, i64, i64, i32, ctypes.POINTER(vp)]),

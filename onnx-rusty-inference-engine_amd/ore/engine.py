@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "center_crop_geometry", "topk", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -342,29 +342,48 @@ def resize_aa_taps(src: int, resized: int, origin: int, count: int):
     return first, ntaps, total, weights
 
 
-def _resize_arg(src_hw, out_hw, resized_hw, origin, antialias=False, name="resize"):
+def _resize_arg(src_hw, out_hw, resized_hw, origin, antialias=False, name="resize", cubic=False):
     """The ore_resize of a [hs, ws] -> resized_hw (None: out_hw, a plain resize) -> out_hw window at origin.
-    Under antialias the ratio rule is checked here as the library checks it."""
+    Under antialias the ratio rule (32 times; 16 under cubic) is checked here as the library checks it."""
     rh, rw = (int(v) for v in (out_hw if resized_hw is None else resized_hw))
     top, left = (int(v) for v in origin)
     if antialias:
+        ratio = _lib.CUBIC_AA_MAX_RATIO if cubic else _lib.AA_MAX_RATIO
         for axis, s, d in (("rows", int(src_hw[0]), rh), ("columns", int(src_hw[1]), rw)):
-            if d >= 1 and s > _lib.AA_MAX_RATIO * d:
-                raise OreError(1, f"{name}: the antialiasing filter shrinks an axis at most {_lib.AA_MAX_RATIO} times, "
+            if d >= 1 and s > ratio * d:
+                raise OreError(1, f"{name}: the antialiasing filter shrinks an axis at most {ratio} times, "
                                   f"the {axis} go {s} -> {d}")
     return Resize(rh, rw, top, left)
 
 
-def _filter(antialias) -> int:
-    return _lib.FILTER_BILINEAR_AA if antialias else _lib.FILTER_BILINEAR
+def _filter(antialias, cubic=False) -> int:
+    """The filter word of the _ex entries: bit 0 antialiased, bit 8 the cubic kernel."""
+    return (_lib.FILTER_CUBIC_BIT if cubic else 0) | (_lib.FILTER_BILINEAR_AA if antialias else _lib.FILTER_BILINEAR)
+
+
+def resize_cubic_taps(src: int, resized: int, origin: int, count: int, antialias: bool = False):
+    """ore_resize_cubic_taps (host only): the cubic filters' table of one axis for the `count` resized indices from
+    `origin`: (first int32, ntaps int32, weights float32 [count, 64] zero padded, sum float32).  Tap k of index i
+    reads source sample clamp(first[i] + k, 0, src - 1) with weight weights[i, k]; plain: 4 taps, first may be
+    negative, sum 1; antialiased: the run lies inside the image, its weights are divided by sum."""
+    n = min(max(int(count), 0), 16384)  # the library rejects anything outside 1..16384
+    first, ntaps, total = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+    weights = np.empty((n, _lib.AA_MAX_TAPS), np.float32)
+    check(load().ore_resize_cubic_taps(int(src), int(resized), int(origin), int(count), _filter(antialias, True),
+                                       first.ctypes.data_as(ctypes.c_void_p), ntaps.ctypes.data_as(ctypes.c_void_p),
+                                       weights.ctypes.data_as(ctypes.c_void_p), total.ctypes.data_as(ctypes.c_void_p)))
+    return first, ntaps, weights, total
 
 
 def preprocess_resize_u8(ctx: Context, x, out_hw, resized_hw=None, origin=(0, 0), scale=None, shift=None,
-                         reverse_channels: bool = False, antialias: bool = False):
+                         reverse_channels: bool = False, antialias: bool = False, cubic: bool = False):
     """ore_preprocess_resize_u8_ex (extension): uint8 [n, Hs, Ws, C] -> float32 [n, C, H, W] = out_hw: the images
     bilinearly resized to resized_hw (None: out_hw), of which the window at `origin` is kept, then normalised
     as preprocess_u8 does, in one launch.  antialias=True: axes that shrink take the area-weighted filter of
-    F.interpolate(antialias=True) / PIL's BILINEAR (each by at most 32 times)."""
+    F.interpolate(antialias=True) / PIL's BILINEAR (each by at most 32 times).  cubic=True: the bicubic filters
+    instead -- a = -0.75 with 4 x 4 taps (F.interpolate(mode="bicubic"), cv2.INTER_CUBIC), or under antialias
+    a = -0.5 with the support widened by the shrink ratio (PIL's BICUBIC; each axis by at most 16 times).  Overshoot
+    is kept: the result is not clamped to the bytes' range."""
     torch = _torch()
     _check_u8(x, ctx.device)
     n, hs, ws, c = (int(d) for d in x.shape)
@@ -373,11 +392,11 @@ def preprocess_resize_u8(ctx: Context, x, out_hw, resized_hw=None, origin=(0, 0)
     h, w = (int(v) for v in out_hw)
     if h < 1 or w < 1:
         raise OreError(1, f"out_hw: {(h, w)}")
-    g = _resize_arg((hs, ws), (h, w), resized_hw, origin, antialias)
+    g = _resize_arg((hs, ws), (h, w), resized_hw, origin, antialias, cubic=cubic)
     y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
     flags = PRE_REVERSE_CHANNELS if reverse_channels else 0
     check(load().ore_preprocess_resize_u8_ex(ctx.h, ctypes.c_void_p(x.data_ptr()), n, hs, ws, c, ctypes.byref(g),
-                                             _filter(antialias), _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift"),
+                                             _filter(antialias, cubic), _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift"),
                                              flags, ctypes.byref(_desc(y))), ctx.h)
     return y
 
@@ -417,19 +436,21 @@ class ImageList:
     """ore_image_list: up to `capacity` uint8 images of their own sizes and row strides, each resized and
     cropped to out_hw by its own geometry in ONE launch (preprocess_list_u8, Model.run_u8_list, ...).  The
     device table and its pinned mirror are allocated here; set() only fills and uploads them.  antialias=True
-    makes it a list of the antialiased filter (see preprocess_resize_u8): a property of the list."""
+    makes it a list of the antialiased filter, cubic=True of the bicubic ones (see preprocess_resize_u8): properties
+    of the list."""
 
-    def __init__(self, ctx: Context, capacity: int, out_hw, channels: int = 3, antialias: bool = False):
+    def __init__(self, ctx: Context, capacity: int, out_hw, channels: int = 3, antialias: bool = False, cubic: bool = False):
         h, w = (int(v) for v in out_hw)
         self.ctx = ctx
         self.capacity = int(capacity)
         self.out_hw = (h, w)
         self.channels = int(channels)
         self.antialias = bool(antialias)
+        self.cubic = bool(cubic)
         self._images = ()
         self.h = None
         hnd = ctypes.c_void_p()
-        check(load().ore_image_list_create_ex(ctx.h, self.capacity, self.channels, h, w, _filter(antialias),
+        check(load().ore_image_list_create_ex(ctx.h, self.capacity, self.channels, h, w, _filter(antialias, cubic),
                                               ctypes.byref(hnd)), ctx.h)
         self.h = hnd
 
@@ -455,7 +476,8 @@ class ImageList:
             arr[i].data = x.data_ptr()
             arr[i].hs, arr[i].ws = hs, ws
             arr[i].row_stride = int(x.stride(0))
-            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"images[{i}]")
+            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"images[{i}]",
+                                   getattr(self, "cubic", False))
         return images, arr
 
     def set(self, images, geometries=None, short=None, flips=None):
@@ -571,18 +593,19 @@ class Nv12ImageList(ImageList):
     frame.  Three channels (R, G, B); the matrix ("bt601", "bt709", "bt601_full") and the filter are properties of
     the list.  Model.run_u8_list, classify_u8_list and the captures take it as they take an ImageList."""
 
-    def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601", antialias: bool = False):
+    def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601", antialias: bool = False, cubic: bool = False):
         h, w = (int(v) for v in out_hw)
         self.ctx = ctx
         self.capacity = int(capacity)
         self.out_hw = (h, w)
         self.channels = 3
         self.antialias = bool(antialias)
+        self.cubic = bool(cubic)
         self.matrix = _yuv_matrix(matrix)
         self._images = ()
         self.h = None
         hnd = ctypes.c_void_p()
-        check(load().ore_image_list_create_nv12(ctx.h, self.capacity, h, w, _filter(antialias), self.matrix,
+        check(load().ore_image_list_create_nv12(ctx.h, self.capacity, h, w, _filter(antialias, cubic), self.matrix,
                                                 ctypes.byref(hnd)), ctx.h)
         self.h = hnd
 
@@ -607,7 +630,8 @@ class Nv12ImageList(ImageList):
             arr[i].y, arr[i].uv = y.data_ptr(), uv.data_ptr()
             arr[i].hs, arr[i].ws = hs, ws
             arr[i].y_stride, arr[i].uv_stride = int(y.stride(0)), int(uv.stride(0))
-            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]")
+            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]",
+                                   getattr(self, "cubic", False))
         return frames, arr
 
     def set(self, frames, geometries=None, short=None, flips=None):
@@ -734,18 +758,19 @@ class YuvImageList(ImageList):
     "bt601_full") and the filter are properties of the list, the layout is each frame's own.  Model.run_u8_list,
     classify_u8_list, the captures and set_views take it as they take an ImageList."""
 
-    def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601_full", antialias: bool = False):
+    def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601_full", antialias: bool = False, cubic: bool = False):
         h, w = (int(v) for v in out_hw)
         self.ctx = ctx
         self.capacity = int(capacity)
         self.out_hw = (h, w)
         self.channels = 3
         self.antialias = bool(antialias)
+        self.cubic = bool(cubic)
         self.matrix = _yuv_matrix(matrix)
         self._images = ()
         self.h = None
         hnd = ctypes.c_void_p()
-        check(load().ore_image_list_create_yuv(ctx.h, self.capacity, h, w, _filter(antialias), self.matrix,
+        check(load().ore_image_list_create_yuv(ctx.h, self.capacity, h, w, _filter(antialias, cubic), self.matrix,
                                                ctypes.byref(hnd)), ctx.h)
         self.h = hnd
 
@@ -772,7 +797,8 @@ class YuvImageList(ImageList):
                 arr[i].stride[k] = int(p.stride(0))
             arr[i].hs, arr[i].ws = hs, ws
             arr[i].format = fmt
-            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]")
+            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]",
+                                   getattr(self, "cubic", False))
         return frames, arr
 
     def set(self, frames, geometries=None, short=None, flips=None):
@@ -948,18 +974,18 @@ class Model:
         sc, sh = _norm_arg(scale, c, "scale"), _norm_arg(shift, c, "shift")
         check(load().ore_model_set_input_norm(self.h, sc, sh, c, flags), self.ctx.h)
 
-    def set_input_resize(self, src_hw, resized_hw=None, origin=(0, 0), antialias: bool = False):
+    def set_input_resize(self, src_hw, resized_hw=None, origin=(0, 0), antialias: bool = False, cubic: bool = False):
         """ore_model_set_input_resize_ex: from now on run_u8 / classify_u8 / capture_u8 / capture_classify_u8 take
         uint8 [n, Hs, Ws, C] batches with (Hs, Ws) = src_hw, resized to resized_hw (None: the model's H x W) and
-        cropped to the model's H x W at `origin` on the device (see preprocess_resize_u8, also for antialias),
+        cropped to the model's H x W at `origin` on the device (see preprocess_resize_u8, also for antialias and cubic),
         with the normalisation of set_input_norm.  src_hw None: back to [n, H, W, C]."""
         if src_hw is None:
             check(load().ore_model_set_input_resize(self.h, 0, 0, None), self.ctx.h)
             self.input_src_hw = None
             return
         hs, ws = (int(v) for v in src_hw)
-        g = _resize_arg((hs, ws), self.input_dims[1:], resized_hw, origin, antialias, "set_input_resize")
-        check(load().ore_model_set_input_resize_ex(self.h, hs, ws, ctypes.byref(g), _filter(antialias)), self.ctx.h)
+        g = _resize_arg((hs, ws), self.input_dims[1:], resized_hw, origin, antialias, "set_input_resize", cubic)
+        check(load().ore_model_set_input_resize_ex(self.h, hs, ws, ctypes.byref(g), _filter(antialias, cubic)), self.ctx.h)
         self.input_src_hw = (hs, ws)
 
     def _check_u8_dims(self, x):
