@@ -513,6 +513,69 @@ ore_status ore_topk_f32(ore_ctx* ctx, const ore_tensor* x, int32_t k, float* val
 ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, int64_t n);
 ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, int64_t n);
 ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, int32_t k, float* values, int32_t* indices);
+/* Oriented list images (extension): what a hardware decoder leaves undone -- a JPEG's EXIF
+ * orientation tag, a video container's display rotation -- applied inside the list's one launch.  An orientation is
+ * an EXIF code 1..8 per descriptor.  hs, ws and the plane pointers still describe the STORED image; the geometry
+ * g = {rh, rw, top, left} and the list's h x w describe the DISPLAYED image, which for codes 5..8 is ws x hs.  With
+ * D the displayed and S the stored image (hs x ws), as PIL's ImageOps.exif_transpose shows it:
+ *     1  D[r,c] = S[r, c]            5  D[r,c] = S[c, r]
+ *     2  D[r,c] = S[r, ws-1-c]       6  D[r,c] = S[hs-1-c, r]        (rotate 90 degrees clockwise to display)
+ *     3  D[r,c] = S[hs-1-r, ws-1-c]  7  D[r,c] = S[hs-1-c, ws-1-r]
+ *     4  D[r,c] = S[hs-1-r, c]       8  D[r,c] = S[c, ws-1-r]        (rotate 270 degrees clockwise to display)
+ * The resized image obeys the same table: the stored image is resized to rh_s x rw_s = (rh, rw) for codes 1..4 and
+ * (rw, rh) for codes 5..8, and output element (ch, i, j) of the descriptor, with r = top + i and c = left + j, is the
+ * filter's value at resized row a and resized column b of the STORED image, (a, b) the table's index pair for (r, c)
+ * with rh_s, rw_s in place of hs, ws.  Row taps come from a, column taps from b, every float operation in the order
+ * given above for the list's filter (columns inside, rows outside, in stored coordinates).  A tap depends only on
+ * the absolute resized index, so the result is, bit for bit: the output of the unoriented descriptor of a list of
+ * output shape (hz, wz) = (h, w) for codes 1..4 and (w, h) for codes 5..8 with the stored-space window
+ * ore_orient_geometry gives, its rows reversed (codes 3 4 6 7) and / or its columns reversed (codes 2 3 7 8) and then
+ * transposed (codes 5..8).  It is a permutation of the resized stored image, NOT a resize of the rotated bytes: the
+ * two differ in the last bits for the reason given under ORE_IMAGE_FLIP_H, and because the separable passes run in
+ * the other order.  An image that is not resized comes out as the oriented bytes exactly.  ORE_IMAGE_FLIP_H composes
+ * on top: a flagged oriented descriptor is the oriented output with its columns reversed.  Of an NV12 or YUV frame the
+ * chroma pairing stays in stored coordinates, so oriented image i of such a list equals, bit for bit, what an
+ * interleaved list gives for the converted stored bytes with the same orientation, flag, geometry and filter.  The
+ * ratio rules (ORE_AA_MAX_RATIO, ORE_CUBIC_AA_MAX_RATIO) apply to the stored axes: hs against rh_s, ws against rw_s.
+ *  ore_orient_geometry: host only; the map above, the one the kernels use.  For a code 1..8, a displayed geometry g
+ *    and the list's h x w: *stored_g = {rh_s, rw_s, top_s, left_s} with top_s = rev_rows ? rh_s - hz - a0 : a0, a0 =
+ *    top for codes 1..4 and left for 5..8, and the analogous column rule; *hz, *wz; and the three permutation bits.
+ *    Any output pointer may be NULL.  A code outside 1..8 or a NULL g is ORE_ERR_INVALID; nothing else is checked.
+ *  ore_image_check_oriented / _check_nv12_oriented / _check_yuv_oriented: the _ex checks with a HOST array of n codes
+ *    (NULL: all 1, the _ex check exactly).  A code outside 1..8 is ORE_ERR_INVALID with the descriptor's index and
+ *    the word `orientation` in the message, checked before that descriptor's geometry.  The crop is checked in
+ *    displayed space (top + h <= rh, left + w <= rw), which is the stored-space window's check; the ratio rules in
+ *    stored space.  Messages about a descriptor's geometry quote its stored-space numbers.
+ *  ore_image_list_set_oriented / _set_nv12_oriented / _set_yuv_oriented: _set_ex with the codes array, read before
+ *    return; NULL means all 1.  Everything else is _set_ex's: the check first, the previous content, count and
+ *    orientations kept on any failure, the upload stream-ordered from the pinned mirror, ORE_ERR_INVALID inside a
+ *    capture or on a list of another kind, n == 0 empties the list.  The _ex sets still reject every flag bit other
+ *    than ORE_IMAGE_FLIP_H; ore_image_u8, ore_image_nv12 and ore_image_yuv keep their layouts.
+ *  ore_image_list_oriented: 1 once an oriented set has succeeded on the list (n == 0 and all-1 codes included), for
+ *    good; 0 before.  The mark decides which kernels a CAPTURE of the list records: a marked list records the
+ *    orientation-reading instances, which serve whatever a later set uploads; an unmarked list records the instances
+ *    it records today, and ore_model_graph_launch of such a graph is ORE_ERR_INVALID ("re-capture") once the list
+ *    holds a code other than 1.  A caller that captures ore_preprocess_list_u8 into a graph of its own and means to
+ *    set orientations later MUST mark the list first (one ore_image_list_set_oriented call, n == 0 will do): the
+ *    library cannot check a graph it does not own, and an unmarked capture ignores the orientation bits.  Outside a
+ *    capture the kernels follow the list's last set: all codes 1 launches exactly what a list without orientations
+ *    launches, flags included.  The dense entries (ore_preprocess_resize_u8*, ore_model_set_input_resize*) take no
+ *    orientation, as they take no flip. */
+ore_status ore_orient_geometry(int32_t orientation, const ore_resize* g, int64_t h, int64_t w, ore_resize* stored_g,
+                               int64_t* hz, int64_t* wz, int32_t* rev_rows, int32_t* rev_cols, int32_t* transpose);
+ore_status ore_image_check_oriented(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int32_t filter,
+                                    const uint8_t* orientations, int64_t* bad_index);
+ore_status ore_image_check_nv12_oriented(const ore_image_nv12* imgs, int64_t n, int64_t h, int64_t w, int32_t filter,
+                                         const uint8_t* orientations, int64_t* bad_index);
+ore_status ore_image_check_yuv_oriented(const ore_image_yuv* imgs, int64_t n, int64_t h, int64_t w, int32_t filter,
+                                        const uint8_t* orientations, int64_t* bad_index);
+ore_status ore_image_list_set_oriented(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags,
+                                       const uint8_t* orientations, int64_t n);
+ore_status ore_image_list_set_nv12_oriented(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags,
+                                            const uint8_t* orientations, int64_t n);
+ore_status ore_image_list_set_yuv_oriented(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags,
+                                           const uint8_t* orientations, int64_t n);
+int32_t ore_image_list_oriented(ore_image_list* l);
 
 /* ------------------------------------------------------------------ graph walker (inference()) */
 /* Parse an ONNX ModelProto (bytes), upload every initializer to HBM once, plan the value

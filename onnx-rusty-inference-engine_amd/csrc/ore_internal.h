@@ -40,6 +40,8 @@ struct ore_image_list {
   int32_t format = 0;                  // ore_image_format, fixed at creation
   int32_t matrix = 0;                  // ore_yuv_matrix of an NV12 or YUV list, fixed at creation
   bool any_flip = false;               // the last set flipped a descriptor: launches take the kernels' flag-reading instance
+  bool any_orient = false;             // the last set held an orientation other than 1: launches take the orientation-reading instance
+  bool oriented = false;               // ore_image_list_oriented: an oriented set has succeeded once; captures record that instance
   int taps = 0;                        // ORE_FILTER_BICUBIC_AA: no column run of the last set is longer (sizes the kernels' LDS)
   ore::ResizeImage* table = nullptr;   // device
   ore::ResizeImage* mirror = nullptr;  // pinned host: the source of the stream-ordered upload

@@ -472,8 +472,13 @@ struct ResizeImage {
   int Hs, Ws;              // <= RESIZE_MAX
   int row;                 // bytes between rows, >= Ws * C; (Hs - 1) * row + Ws * C < 2^31
   int Rh, Rw, top, left;
-  int flip;                // ORE_IMAGE_FLIP_H or 0: output column q shows resized column left + W - 1 - q
+  int flip;                // ORE_IMAGE_FLIP_H or 0: output column q shows resized column left + W - 1 - q; an oriented
+                           // descriptor (ore_image_list_set_oriented) adds LIST_* bits, and Rh .. left are then the
+                           // STORED image's geometry (ore_orient_geometry)
 };                         // 40 bytes: an 8-byte multiple, so the pointers of a table stay aligned
+// the bits of a descriptor's flip word: the flag, and the orientation as ore_orient_geometry resolves an EXIF code
+// (rows reversed: 3 4 6 7, columns reversed: 2 3 7 8, transpose: 5..8); code 1 sets none
+enum : int { LIST_FLIP_H = 1, LIST_REV_ROWS = 0x100, LIST_REV_COLS = 0x200, LIST_TRANSPOSE = 0x400 };
 struct ResizeListParams {
   const ResizeImage* table;  // image i of the launch is table[first + i]
   long long first;
@@ -483,7 +488,8 @@ struct ResizeListParams {
   int C, H, W;
   int plane[4];
   float scale[4], shift[4];
-  int flips;                 // 0: no descriptor of the launch is flipped, the flag-free instance of the kernel runs
+  int flips;                 // 0: no descriptor of the launch is flipped, the flag-free instance of the kernel runs;
+                             // 1: the flag-reading instance; 2: the one that reads the orientation bits as well
   int taps;                  // ORE_FILTER_BICUBIC_AA: no column run of a descriptor is longer (1..RESIZE_AA_MAX_TAPS)
 };
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s);

@@ -1369,6 +1369,7 @@ static ore_status capture_run(ore_model* m, const float* d_input, const uint8_t*
   ORE_HIP_CHECK(ctx, hipGraphInstantiate(&m->graph_exec, m->graph, nullptr, nullptr, 0));
   m->graph_list = lst;  // the graph reads lst's table at replay: descriptors [0, n)
   m->graph_list_count = n;
+  m->graph_list_oriented = lst && lst->oriented;
   return ORE_OK;
 }
 
@@ -1412,6 +1413,9 @@ ore_status ore_model_graph_launch(ore_model* m) {
   if (m->graph_list && m->graph_list->count != m->graph_list_count)
     return set_error(m->ctx, ORE_ERR_INVALID, "the graph was captured on a list of %lld images, the list now holds %lld",
                      (long long)m->graph_list_count, (long long)m->graph_list->count);
+  if (m->graph_list && !m->graph_list_oriented && m->graph_list->any_orient)
+    return set_error(m->ctx, ORE_ERR_INVALID, "the graph was captured before the list's first oriented set and runs kernels that "
+                                              "read no orientation, the list now holds one: re-capture");
   ORE_HIP_CHECK(m->ctx, hipGraphLaunch(m->graph_exec, m->ctx->stream));
   return ORE_OK;
 }

@@ -171,6 +171,7 @@ struct ore_model {
   hipGraphExec_t graph_exec = nullptr;
   ore_image_list* graph_list = nullptr;  // a _u8_list capture: the list whose table the graph reads at replay,
   int64_t graph_list_count = 0;          // and the count it was captured with (ore_model_graph_launch checks it)
+  bool graph_list_oriented = false;      // the list was marked (ore_image_list_oriented) at the capture: the graph reads orientations
   int timed_chunks = 0;          // image chunks of the last timed run (events: chunk x (exec_steps + 1))
   std::vector<int> exec_steps;   // indices into steps of launched (non-NOP) steps
   // run-time binding

@@ -5,7 +5,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <cstdlib>
 
 #include "ore_chunk.h"
 #include "ore_internal.h"
@@ -221,7 +220,9 @@ void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& 
   ResizeListParams p = p0;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   const bool capturing = ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-  p.flips = l->any_flip || capturing;
+  // The orientation-reading instance when the last set held a code other than 1; a capture records it for a list
+  // that an oriented set has marked, and otherwise what it recorded before there were orientations.
+  p.flips = capturing ? (l->oriented ? 2 : 1) : l->any_orient ? 2 : l->any_flip ? 1 : 0;
   p.taps = capturing || l->taps < 1 ? RESIZE_AA_MAX_TAPS : l->taps;  // likewise: a later set may bring longer runs
   if (l->format == ORE_IMAGE_YUV) {
     YuvListParams q{};
@@ -1138,12 +1139,69 @@ ore_status ore_preprocess_resize_u8_ex(ore_ctx* ctx, const uint8_t* x, int64_t n
   return ORE_OK;
 }
 
+// An EXIF orientation code 1..8 as the three permutation bits of ore_orient_geometry; false: not a code
+static bool orient_bits(int code, bool* rev_rows, bool* rev_cols, bool* transpose) {
+  if (code < 1 || code > 8) return false;
+  *rev_rows = code == 3 || code == 4 || code == 6 || code == 7;
+  *rev_cols = code == 2 || code == 3 || code == 7 || code == 8;
+  *transpose = code >= 5;
+  return true;
+}
+
+// the descriptor's geometry and the list's output shape in stored space (include/ore.h: ore_orient_geometry);
+// returns the LIST_* bits of the kernels' descriptor word
+static int orient_stored(int code, const ore_resize& g, int64_t h, int64_t w, ore_resize* sg, int64_t* hz, int64_t* wz) {
+  bool rr = false, rc = false, tr = false;
+  orient_bits(code, &rr, &rc, &tr);
+  *hz = tr ? w : h;
+  *wz = tr ? h : w;
+  sg->rh = tr ? g.rw : g.rh;
+  sg->rw = tr ? g.rh : g.rw;
+  const int64_t a0 = tr ? g.left : g.top, b0 = tr ? g.top : g.left;
+  sg->top = rr ? sg->rh - *hz - a0 : a0;
+  sg->left = rc ? sg->rw - *wz - b0 : b0;
+  return (rr ? LIST_REV_ROWS : 0) | (rc ? LIST_REV_COLS : 0) | (tr ? LIST_TRANSPOSE : 0);
+}
+
+ore_status ore_orient_geometry(int32_t orientation, const ore_resize* g, int64_t h, int64_t w, ore_resize* stored_g, int64_t* hz,
+                               int64_t* wz, int32_t* rev_rows, int32_t* rev_cols, int32_t* transpose) {
+  bool rr, rc, tr;
+  if (!orient_bits(orientation, &rr, &rc, &tr))
+    return set_error(nullptr, ORE_ERR_INVALID, "orientation %d is not an EXIF code 1..8", int(orientation));
+  if (!g) return set_error(nullptr, ORE_ERR_INVALID, "null resize geometry");
+  ore_resize sg;
+  int64_t hh, ww;
+  orient_stored(orientation, *g, h, w, &sg, &hh, &ww);
+  if (stored_g) *stored_g = sg;
+  if (hz) *hz = hh;
+  if (wz) *wz = ww;
+  if (rev_rows) *rev_rows = rr;
+  if (rev_cols) *rev_cols = rc;
+  if (transpose) *transpose = tr;
+  return ORE_OK;
+}
+
+// a descriptor's code in the checks: null orientations are all 1
+static ore_status check_orientation(const uint8_t* orientations, int64_t i) {
+  if (orientations && (orientations[i] < 1 || orientations[i] > 8))
+    return set_error(nullptr, ORE_ERR_INVALID, "image %lld: orientation %d is not an EXIF code 1..8", (long long)i, int(orientations[i]));
+  return ORE_OK;
+}
+
 ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int64_t* bad_index) {
   return ore_image_check_ex(imgs, n, c, h, w, ORE_FILTER_BILINEAR, bad_index);
 }
 
 ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int32_t filter,
                               int64_t* bad_index) {
+  return ore_image_check_oriented(imgs, n, c, h, w, filter, nullptr, bad_index);
+}
+
+// Every check below judges a descriptor in stored space: its geometry and the output shape as orient_stored gives
+// them.  The crop rule there is the displayed-space rule (top_s + hz <= rh_s is top + h <= rh or left + w <= rw).
+ore_status ore_image_check_oriented(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h0, int64_t w0, int32_t filter,
+                                    const uint8_t* orientations, int64_t* bad_index) {
+  int64_t h = h0, w = w0;
   if (!filter_known(filter))
     return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
@@ -1153,10 +1211,12 @@ ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, in
   if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_u8& d = imgs[i];
-    const ore_resize& g = d.g;
+    ore_resize g = d.g;
+    ore_status st = check_orientation(orientations, i);
+    if (!st && orientations) orient_stored(orientations[i], d.g, h0, w0, &g, &h, &w);
     const long long hs = d.hs, ws = d.ws, rs = d.row_stride;
-    ore_status st = ORE_OK;
-    if (!d.data)
+    if (st) {  // a bad code: the descriptor's geometry is not looked at
+    } else if (!d.data)
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null data pointer", (long long)i);
     else if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX)
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
@@ -1194,6 +1254,12 @@ ore_status ore_yuv_to_rgb(int32_t matrix, const uint8_t* y, const uint8_t* u, co
 }
 
 ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
+  return ore_image_check_nv12_oriented(imgs, n, h, w, filter, nullptr, bad_index);
+}
+
+ore_status ore_image_check_nv12_oriented(const ore_image_nv12* imgs, int64_t n, int64_t h0, int64_t w0, int32_t filter,
+                                         const uint8_t* orientations, int64_t* bad_index) {
+  int64_t h = h0, w = w0;
   if (!filter_known(filter))
     return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
@@ -1203,11 +1269,13 @@ ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h
   if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_nv12& d = imgs[i];
-    const ore_resize& g = d.g;
+    ore_resize g = d.g;
+    ore_status st = check_orientation(orientations, i);
+    if (!st && orientations) orient_stored(orientations[i], d.g, h0, w0, &g, &h, &w);
     const long long hs = d.hs, ws = d.ws, ys = d.y_stride, us = d.uv_stride;
     const long long hc = (hs + 1) / 2, wc2 = 2 * ((ws + 1) / 2);  // UV rows, and the bytes of one
-    ore_status st = ORE_OK;
-    if (!d.y || !d.uv)
+    if (st) {  // a bad code: the descriptor's geometry is not looked at
+    } else if (!d.y || !d.uv)
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null %s pointer", (long long)i, d.y ? "uv" : "y");
     else if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX)
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
@@ -1259,6 +1327,12 @@ static long long yuv_plane_row_bytes(const YuvLayout& f, int k, long long ws) {
 }
 
 ore_status ore_image_check_yuv(const ore_image_yuv* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
+  return ore_image_check_yuv_oriented(imgs, n, h, w, filter, nullptr, bad_index);
+}
+
+ore_status ore_image_check_yuv_oriented(const ore_image_yuv* imgs, int64_t n, int64_t h0, int64_t w0, int32_t filter,
+                                        const uint8_t* orientations, int64_t* bad_index) {
+  int64_t h = h0, w = w0;
   if (!filter_known(filter))
     return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
@@ -1268,11 +1342,13 @@ ore_status ore_image_check_yuv(const ore_image_yuv* imgs, int64_t n, int64_t h, 
   if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_yuv& d = imgs[i];
-    const ore_resize& g = d.g;
+    ore_resize g = d.g;
+    ore_status st = check_orientation(orientations, i);
+    if (!st && orientations) orient_stored(orientations[i], d.g, h0, w0, &g, &h, &w);
     const long long hs = d.hs, ws = d.ws;
     const YuvLayout* f = yuv_layout(d.format);
-    ore_status st = ORE_OK;
-    if (!f)
+    if (st) {  // a bad code: the descriptor's geometry is not looked at
+    } else if (!f)
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: unknown YUV format %d", (long long)i, int(d.format));
     else if (d.reserved != 0)
       st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: reserved is %d, it must be 0", (long long)i, int(d.reserved));
@@ -1392,6 +1468,8 @@ ore_status ore_image_list_destroy(ore_image_list* l) {
 
 int64_t ore_image_list_count(ore_image_list* l) { return l ? l->count : 0; }
 
+int32_t ore_image_list_oriented(ore_image_list* l) { return l && l->oriented ? 1 : 0; }
+
 // The two sets between the descriptors' check and the mirror's rewrite: the capacity, the capture rule, and the
 // wait for the previous upload to have read the mirror.  n == 0 empties the list here.
 static ore_status list_set_begin(ore_image_list* l, int64_t n) {
@@ -1424,7 +1502,8 @@ ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs
   return ore_image_list_set_nv12_ex(l, imgs, nullptr, n);
 }
 
-ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, int64_t n) {
+static ore_status list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, const uint8_t* orientations, int64_t n,
+                                bool oriented_entry) {
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
   if (l->format == ORE_IMAGE_YUV)
@@ -1432,14 +1511,15 @@ ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* i
   if (l->format != ORE_IMAGE_NV12)
     return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_nv12 on a list of interleaved images: ore_image_list_set is its entry");
   int64_t bad = -1;
-  if (ore_image_check_nv12(imgs, n, l->h, l->w, l->filter, &bad)) {
+  if (ore_image_check_nv12_oriented(imgs, n, l->h, l->w, l->filter, orientations, &bad)) {
     ctx->err = ore_last_error(nullptr);
     return ORE_ERR_INVALID;
   }
   if (ore_status st = list_check_flags(ctx, flags, n)) return st;
   if (ore_status st = list_set_begin(l, n)) return st;
+  if (oriented_entry) l->oriented = true;  // for good: captures of the list record the orientation-reading kernels
   if (n == 0) return ORE_OK;
-  bool any_flip = false;
+  bool any_flip = false, any_orient = false;
   int taps = 0;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_nv12& d = imgs[i];
@@ -1450,17 +1530,31 @@ ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* i
     r.Hs = int(d.hs); r.Ws = int(d.ws);
     r.yrow = int(d.hs > 1 && d.y_stride ? d.y_stride : d.ws);  // dense where 0, and where no row is ever stepped
     r.uvrow = int(hc > 1 && d.uv_stride ? d.uv_stride : 2 * wc);
-    r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
-    r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
+    ore_resize g = d.g;  // an oriented descriptor carries the stored image's geometry and the permutation bits
+    int64_t hz, wz;
+    const int bits = orientations ? orient_stored(orientations[i], d.g, l->h, l->w, &g, &hz, &wz) : 0;
+    r.Rh = int(g.rh); r.Rw = int(g.rw); r.top = int(g.top); r.left = int(g.left);
+    r.flip = (flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0) | bits;
     any_flip |= r.flip != 0;
+    any_orient |= bits != 0;
     if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
   }
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_nv12, l->mirror_nv12, size_t(n) * sizeof(Nv12Image), hipMemcpyHostToDevice, ctx->stream));
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
   l->any_flip = any_flip;
+  l->any_orient = any_orient;
   l->taps = taps;
   return ORE_OK;
+}
+
+ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, int64_t n) {
+  return list_set_nv12(l, imgs, flags, nullptr, n, false);
+}
+
+ore_status ore_image_list_set_nv12_oriented(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags,
+                                            const uint8_t* orientations, int64_t n) {
+  return list_set_nv12(l, imgs, flags, orientations, n, true);
 }
 
 static_assert(sizeof(ore_image_yuv) == 104, "ore_image_yuv is part of the ABI");
@@ -1470,7 +1564,8 @@ ore_status ore_image_list_set_yuv(ore_image_list* l, const ore_image_yuv* imgs, 
   return ore_image_list_set_yuv_ex(l, imgs, nullptr, n);
 }
 
-ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags, int64_t n) {
+static ore_status list_set_yuv(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags, const uint8_t* orientations, int64_t n,
+                               bool oriented_entry) {
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
   if (l->format == ORE_IMAGE_NV12)
@@ -1478,14 +1573,15 @@ ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* img
   if (l->format != ORE_IMAGE_YUV)
     return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_yuv on a list of interleaved images: ore_image_list_set is its entry");
   int64_t bad = -1;
-  if (ore_image_check_yuv(imgs, n, l->h, l->w, l->filter, &bad)) {
+  if (ore_image_check_yuv_oriented(imgs, n, l->h, l->w, l->filter, orientations, &bad)) {
     ctx->err = ore_last_error(nullptr);
     return ORE_ERR_INVALID;
   }
   if (ore_status st = list_check_flags(ctx, flags, n)) return st;
   if (ore_status st = list_set_begin(l, n)) return st;
+  if (oriented_entry) l->oriented = true;  // for good: captures of the list record the orientation-reading kernels
   if (n == 0) return ORE_OK;
-  bool any_flip = false;
+  bool any_flip = false, any_orient = false;
   int taps = 0;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_yuv& d = imgs[i];
@@ -1511,24 +1607,39 @@ ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* img
     r.Hs = int(d.hs); r.Ws = int(d.ws);
     r.ystep = f.ystep; r.cstep = f.cstep;
     r.sx = f.sx; r.sy = f.sy;
-    r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
-    r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
+    ore_resize g = d.g;  // an oriented descriptor carries the stored image's geometry and the permutation bits
+    int64_t hz, wz;
+    const int bits = orientations ? orient_stored(orientations[i], d.g, l->h, l->w, &g, &hz, &wz) : 0;
+    r.Rh = int(g.rh); r.Rw = int(g.rw); r.top = int(g.top); r.left = int(g.left);
+    r.flip = (flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0) | bits;
     any_flip |= r.flip != 0;
+    any_orient |= bits != 0;
     if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
   }
   ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_yuv, l->mirror_yuv, size_t(n) * sizeof(YuvImage), hipMemcpyHostToDevice, ctx->stream));
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
   l->any_flip = any_flip;
+  l->any_orient = any_orient;
   l->taps = taps;
   return ORE_OK;
+}
+
+ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags, int64_t n) {
+  return list_set_yuv(l, imgs, flags, nullptr, n, false);
+}
+
+ore_status ore_image_list_set_yuv_oriented(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags,
+                                           const uint8_t* orientations, int64_t n) {
+  return list_set_yuv(l, imgs, flags, orientations, n, true);
 }
 
 ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n) {
   return ore_image_list_set_ex(l, imgs, nullptr, n);
 }
 
-ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, int64_t n) {
+static ore_status list_set_u8(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, const uint8_t* orientations, int64_t n,
+                              bool oriented_entry) {
   if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
   ore_ctx* ctx = l->ctx;
   if (l->format == ORE_IMAGE_YUV)
@@ -1536,14 +1647,15 @@ ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, co
   if (l->format != ORE_IMAGE_INTERLEAVED)
     return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set on an NV12 list: ore_image_list_set_nv12 is its entry");
   int64_t bad = -1;
-  if (ore_image_check_ex(imgs, n, l->c, l->h, l->w, l->filter, &bad)) {
+  if (ore_image_check_oriented(imgs, n, l->c, l->h, l->w, l->filter, orientations, &bad)) {
     ctx->err = ore_last_error(nullptr);
     return ORE_ERR_INVALID;
   }
   if (ore_status st = list_check_flags(ctx, flags, n)) return st;
   if (ore_status st = list_set_begin(l, n)) return st;
+  if (oriented_entry) l->oriented = true;  // for good: captures of the list record the orientation-reading kernels
   if (n == 0) return ORE_OK;
-  bool any_flip = false;
+  bool any_flip = false, any_orient = false;
   int taps = 0;
   for (int64_t i = 0; i < n; ++i) {
     const ore_image_u8& d = imgs[i];
@@ -1552,9 +1664,13 @@ ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, co
     r.x = d.data;
     r.Hs = int(d.hs); r.Ws = int(d.ws);
     r.row = int(d.hs > 1 && d.row_stride ? d.row_stride : d.ws * l->c);  // dense where 0, and where no row is ever stepped
-    r.Rh = int(d.g.rh); r.Rw = int(d.g.rw); r.top = int(d.g.top); r.left = int(d.g.left);
-    r.flip = flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0;
+    ore_resize g = d.g;  // an oriented descriptor carries the stored image's geometry and the permutation bits
+    int64_t hz, wz;
+    const int bits = orientations ? orient_stored(orientations[i], d.g, l->h, l->w, &g, &hz, &wz) : 0;
+    r.Rh = int(g.rh); r.Rw = int(g.rw); r.top = int(g.top); r.left = int(g.left);
+    r.flip = (flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0) | bits;
     any_flip |= r.flip != 0;
+    any_orient |= bits != 0;
     if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
   }
   // stream-ordered: launches submitted earlier read the old table, later ones the new
@@ -1562,8 +1678,18 @@ ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, co
   ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
   l->count = n;
   l->any_flip = any_flip;
+  l->any_orient = any_orient;
   l->taps = taps;
   return ORE_OK;
+}
+
+ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, int64_t n) {
+  return list_set_u8(l, imgs, flags, nullptr, n, false);
+}
+
+ore_status ore_image_list_set_oriented(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags,
+                                       const uint8_t* orientations, int64_t n) {
+  return list_set_u8(l, imgs, flags, orientations, n, true);
 }
 
 ore_status ore_preprocess_list_u8(ore_ctx* ctx, ore_image_list* l, const float* scale, const float* shift, int32_t flags,

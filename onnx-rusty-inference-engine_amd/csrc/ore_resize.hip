@@ -69,24 +69,125 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_generic_kernel(ResizePar
 // A descriptor's flip (ORE_IMAGE_FLIP_H, ore_image_list_set_ex) mirrors its window: output column q takes resized
 // column left + W - 1 - q, the store position stays q, so the image is the unflipped one with its columns
 // reversed, bit for bit.  The flag comes with the descriptor: wave-uniform, one scalar select per image.  Each
-// list kernel exists twice: FLIP reads the flag; the other instance does not, and is the one launched when no
+// list kernel exists per ListMode: LIST_FLIP reads the flag; LIST_PLAIN does not, and is the one launched when no
 // descriptor of the list is flipped (ResizeListParams::flips), so that such a launch pays nothing for the feature.
-template <bool FLIP>
-__device__ __forceinline__ int list_column(int flip, int W, int q) {
-  return FLIP && flip ? W - 1 - q : q;
+//
+// A descriptor's orientation (ore_image_list_set_oriented, EXIF codes 1..8) is three more bits of the same word
+// (LIST_REV_ROWS / LIST_REV_COLS / LIST_TRANSPOSE, ore_kernels.h); the descriptor's geometry is then the STORED
+// image's (ore_orient_geometry).  Output pixel (r, q) -- after the flip -- takes row u and column v of the stored
+// window of Hz x Wz = (H, W), or (W, H) under the transpose: (u, v) = (r, q) or (q, r), each reversed in its extent
+// where its bit is set.  The taps and every float operation stay those of the stored window, so the image is the
+// unoriented one of shape (Hz, Wz) permuted, bit for bit.  The bits are wave-uniform like the flag; a third instance
+// of each kernel (LIST_ORIENT) reads them, launched only for a list that holds a code other than 1 (or, inside a
+// capture, a list marked by a first oriented set), so the two instances above run what they ran.
+enum ListMode { LIST_PLAIN = 0, LIST_FLIP = 1, LIST_ORIENT = 2 };
+
+struct ListRQ {
+  int r, q;  // row and column of the descriptor's (stored) window
+};
+
+template <int MODE>
+__device__ __forceinline__ ListRQ list_rq(int word, int H, int W, int r, int q) {
+  if constexpr (MODE == LIST_PLAIN) return ListRQ{r, q};
+  if constexpr (MODE == LIST_FLIP) return ListRQ{r, word ? W - 1 - q : q};
+  if (word & LIST_FLIP_H) q = W - 1 - q;
+  const bool tr = (word & LIST_TRANSPOSE) != 0;
+  const int u = tr ? q : r, v = tr ? r : q;
+  const int Hz = tr ? W : H, Wz = tr ? H : W;
+  return ListRQ{word & LIST_REV_ROWS ? Hz - 1 - u : u, word & LIST_REV_COLS ? Wz - 1 - v : v};
 }
 
-template <bool FLIP>
+// Under the transpose a wave's 64 adjacent output columns are 64 stored rows: with the index map alone every tap
+// read of a wave scatters over 64 rows, which measured 2.6 - 10 times the upright launch (that instance
+// was removed).  LIST_ORIENT therefore maps transposing descriptors by tiles.  A workgroup of T threads takes a tile of
+// T / 16 output rows x 16 output columns.  Its lanes compute adjacent along the output ROW index, which under the
+// transpose is the stored column, so a wave's tap reads cover 4 stored rows (8 where T = 128) instead of 64; the results pass through
+// LDS ([plane][column][row], pitch rows + 1: both the writes and the reads are conflict-free) and are stored with
+// lanes adjacent along the output column.  Descriptors that do not transpose keep the line mapping (block b: pixels
+// b T ..), so the branch is per descriptor: block- and wave-uniform, and every thread of the block reaches the two
+// barriers.  The grid has one block per tile, which is never fewer than the line mapping needs.
+// pixel(pp, yo, hw, px, r, q) computes output pixel (r, q) of the image and stores channel s at
+// yo[pp.plane[s] * hw + px]: the tile path hands it the LDS tile, which is therefore laid out by OUTPUT plane (the
+// plane map is a permutation of 0 .. C-1).
+constexpr int TILE_W = 16;
+
+template <int T, class P, class F>
+__device__ __forceinline__ void list_image(int word, const P& p, int C, float* __restrict__ yimg, F&& pixel) {
+  const int HW = p.H * p.W;
+  const int tid = threadIdx.x;
+  if (!(word & LIST_TRANSPOSE)) {
+    const int px = blockIdx.x * T + tid;
+    if (px < HW) {
+      const int r = px / p.W;
+      pixel(p, yimg, HW, px, r, px - r * p.W);
+    }
+    return;
+  }
+  constexpr int TH = T / TILE_W, PITCH = TH + 1, PLANE = TILE_W * PITCH;
+  __shared__ float tile[4 * PLANE];
+  const int tw = (p.W + TILE_W - 1) / TILE_W;
+  const int tr = blockIdx.x / tw, tc = blockIdx.x - tr * tw;  // the grid is exactly the tiles: tr * TH < H
+  if (tr * TH >= p.H) return;  // block-uniform, as everything up to here
+  {
+    const int il = tid % TH, jl = tid / TH;
+    const int r = tr * TH + il, q = tc * TILE_W + jl;
+    if (r < p.H && q < p.W) pixel(p, tile, PLANE, jl * PITCH + il, r, q);
+  }
+  __syncthreads();
+  {
+    const int jl = tid % TILE_W, il = tid / TILE_W;
+    const int r = tr * TH + il, q = tc * TILE_W + jl;
+    if (r < p.H && q < p.W)  // ragged tile edges: nothing outside the image's H x W elements is stored
+      for (int k = 0; k < C; ++k) yimg[size_t(k) * size_t(HW) + size_t(r) * p.W + q] = tile[k * PLANE + jl * PITCH + il];
+  }
+  __syncthreads();  // the tile is free for the next image of this block
+}
+
+// a list kernel's LIST_ORIENT form: every image of the block through list_image.  body(d, pp, yo, hw, px, r, q) is the
+// kernel's pixel: row r and column q of descriptor d's window, stored at yo[pp.plane[s] * hw + px]
+template <int T, class D, class P, class F>
+__device__ __forceinline__ void list_tiled(const D* __restrict__ table, const P& p, int C, F&& body) {
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const D d = table[i];
+    list_image<T>(d.flip, p, C, p.y + size_t(i) * size_t(p.y_nstride), [&](const P& pp, float* yo, int hw, int px, int r, int q) {
+      const ListRQ m = list_rq<LIST_ORIENT>(d.flip, p.H, p.W, r, q);
+      body(d, pp, yo, hw, px, m.r, m.q);
+    });
+  }
+}
+
+// one output pixel of descriptor d: row r and column q of its window, stored at yi[plane * HW] (yi: the pixel in plane 0)
+__device__ __forceinline__ void u8_list_pixel(const ResizeImage& d, const ResizeListParams& p, float* yi, int HW,
+                                              int r, int q) {
+  const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
+  const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
+  const size_t r0 = size_t(ty.i0) * size_t(d.row), r1 = size_t(ty.i1) * size_t(d.row);
+  const size_t c0 = size_t(tx.i0) * p.C, c1 = size_t(tx.i1) * p.C;
+  const unsigned char* xi = d.x;
+  for (int s = 0; s < p.C; ++s) {
+    const float up = lerp_rn(float(xi[r0 + c0 + s]), float(xi[r0 + c1 + s]), tx.t);
+    const float lo = lerp_rn(float(xi[r1 + c0 + s]), float(xi[r1 + c1 + s]), tx.t);
+    yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
+  }
+}
+
+template <int MODE>
 __global__ __launch_bounds__(RS_THREADS) void resize_u8_list_kernel(const ResizeImage* __restrict__ table,
                                                                     ResizeListParams p) {
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<RS_THREADS>(table, p, p.C, [](const ResizeImage& d, const ResizeListParams& pp, float* yo, int hw, int px, int r, int q) {
+      u8_list_pixel(d, pp, yo + px, hw, r, q);
+    });
+    return;
+  }
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {  // u8_list_pixel, kept inline: these two instances' code is the parent's
     const ResizeImage d = table[i];
     const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_column<FLIP>(d.flip, p.W, q));
+    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_rq<MODE>(d.flip, p.H, p.W, r, q).q);
     const size_t r0 = size_t(ty.i0) * size_t(d.row), r1 = size_t(ty.i1) * size_t(d.row);
     const size_t c0 = size_t(tx.i0) * p.C, c1 = size_t(tx.i1) * p.C;
     const unsigned char* xi = d.x;
@@ -497,7 +598,7 @@ __device__ __forceinline__ void aa_src_row(const AaNv12& d, int r, bool sx, cons
 }
 
 // output pixel px of image d (AaImage: interleaved bytes; AaNv12) from global memory: row r and column q of the
-// window (q is not px's column where a list descriptor is flipped)
+// window (not px's row and column where a list descriptor is flipped or oriented)
 template <int C, class D, class P>
 __device__ __forceinline__ void aa_pixel(const D& d, const P& p, float* __restrict__ yi, int HW, int px, int r, int q) {
   const bool sx = d.Ws > d.Rw, sy = d.Hs > d.Rh;
@@ -556,29 +657,65 @@ __global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_kernel(ResizeParam
 }
 
 // the list descriptor is one scalar load per workgroup, as in resize_u8_list_kernel
-template <int C, bool FLIP>
+template <int C, int MODE>
 __global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_list_kernel(const ResizeImage* __restrict__ table,
                                                                           ResizeListParams p) {
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
-    aa_pixel<C>(aa_image(table[i]), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, list_column<FLIP>(table[i].flip, p.W, q));
-}
-
-// the NV12 list kernels: resize_u8_list_kernel and resize_aa_pixel_list_kernel<3> over converted pixels; the
-// descriptor is one scalar load per workgroup as there
-template <bool FLIP>
-__global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<RS_THREADS>(table, p, C, [&](const ResizeImage& d, const ResizeListParams& pp, float* yo, int hw, int px, int r, int q) {
+      aa_pixel<C>(aa_image(d), pp, yo, hw, px, r, q);
+    });
+    return;
+  }
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const ListRQ m = list_rq<MODE>(table[i].flip, p.H, p.W, r, q);
+    aa_pixel<C>(aa_image(table[i]), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q);
+  }
+}
+
+// the NV12 list kernels: resize_u8_list_kernel and resize_aa_pixel_list_kernel<3> over converted pixels; the
+// descriptor is one scalar load per workgroup as there
+// one output pixel of descriptor d, as u8_list_pixel
+__device__ __forceinline__ void nv12_list_pixel(const Nv12Image& d, const Nv12ListParams& p, float* yi, int HW,
+                                                int r, int q) {
+  const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
+  const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
+  const unsigned char* y0 = d.y + size_t(ty.i0) * size_t(d.yrow);
+  const unsigned char* y1 = d.y + size_t(ty.i1) * size_t(d.yrow);
+  const unsigned char* u0 = d.uv + size_t(ty.i0 >> 1) * size_t(d.uvrow);
+  const unsigned char* u1 = d.uv + size_t(ty.i1 >> 1) * size_t(d.uvrow);
+  int a[3], b[3], c[3], e[3];
+  nv12_pixel(p.m, y0, u0, tx.i0, a);
+  nv12_pixel(p.m, y0, u0, tx.i1, b);
+  nv12_pixel(p.m, y1, u1, tx.i0, c);
+  nv12_pixel(p.m, y1, u1, tx.i1, e);
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
+    const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
+    yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<RS_THREADS>(table, p, 3, [](const Nv12Image& d, const Nv12ListParams& pp, float* yo, int hw, int px, int r, int q) {
+      nv12_list_pixel(d, pp, yo + px, hw, r, q);
+    });
+    return;
+  }
+  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
+  const int HW = p.H * p.W;
+  if (px >= HW) return;
+  const int r = px / p.W, q = px - r * p.W;
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {  // nv12_list_pixel, kept inline as in resize_u8_list_kernel
     const Nv12Image d = table[i];
     const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_column<FLIP>(d.flip, p.W, q));
+    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_rq<MODE>(d.flip, p.H, p.W, r, q).q);
     const unsigned char* y0 = d.y + size_t(ty.i0) * size_t(d.yrow);
     const unsigned char* y1 = d.y + size_t(ty.i1) * size_t(d.yrow);
     const unsigned char* u0 = d.uv + size_t(ty.i0 >> 1) * size_t(d.uvrow);
@@ -598,14 +735,22 @@ __global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12
   }
 }
 
-template <bool FLIP>
+template <int MODE>
 __global__ __launch_bounds__(RS_THREADS) void resize_aa_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<RS_THREADS>(table, p, 3, [&](const Nv12Image& d, const Nv12ListParams& pp, float* yo, int hw, int px, int r, int q) {
+      aa_pixel<3>(aa_image(d, p.m), pp, yo, hw, px, r, q);
+    });
+    return;
+  }
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
-    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, list_column<FLIP>(table[i].flip, p.W, q));
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const ListRQ m = list_rq<MODE>(table[i].flip, p.H, p.W, r, q);
+    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q);
+  }
 }
 
 // the four pixels of a bilinear tap, fetched one way
@@ -619,16 +764,43 @@ __device__ __forceinline__ void yuv_quad(const YuvImage& d, const YuvMatrix& m, 
 }
 
 // the YUV list kernels: the NV12 pair over the strided-plane descriptor, which is one scalar load per workgroup as there
-template <bool FLIP>
+// one output pixel of descriptor d, as u8_list_pixel
+__device__ __forceinline__ void yuv_list_pixel(const YuvImage& d, const YuvListParams& p, float* yi, int HW,
+                                               int r, int q) {
+  const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
+  const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
+  const YuvRow w0 = yuv_row(d, ty.i0), w1 = yuv_row(d, ty.i1);
+  int a[3], b[3], c[3], e[3];
+  switch (yuv_fetch(d)) {
+    case YUV_PACKED: yuv_quad<YUV_PACKED>(d, p.m, w0, w1, tx, a, b, c, e); break;
+    case YUV_PAIRS: yuv_quad<YUV_PAIRS>(d, p.m, w0, w1, tx, a, b, c, e); break;
+    case YUV_PLANES: yuv_quad<YUV_PLANES>(d, p.m, w0, w1, tx, a, b, c, e); break;
+    default: yuv_quad<YUV_GREY>(d, p.m, w0, w1, tx, a, b, c, e); break;
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
+    const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
+    yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
+  }
+}
+
+template <int MODE>
 __global__ __launch_bounds__(RS_THREADS) void resize_yuv_list_kernel(const YuvImage* __restrict__ table, YuvListParams p) {
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<RS_THREADS>(table, p, 3, [](const YuvImage& d, const YuvListParams& pp, float* yo, int hw, int px, int r, int q) {
+      yuv_list_pixel(d, pp, yo + px, hw, r, q);
+    });
+    return;
+  }
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {  // yuv_list_pixel, kept inline as in resize_u8_list_kernel
     const YuvImage d = table[i];
     const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_column<FLIP>(d.flip, p.W, q));
+    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_rq<MODE>(d.flip, p.H, p.W, r, q).q);
     const YuvRow w0 = yuv_row(d, ty.i0), w1 = yuv_row(d, ty.i1);
     int a[3], b[3], c[3], e[3];
     switch (yuv_fetch(d)) {
@@ -647,14 +819,22 @@ __global__ __launch_bounds__(RS_THREADS) void resize_yuv_list_kernel(const YuvIm
   }
 }
 
-template <bool FLIP>
+template <int MODE>
 __global__ __launch_bounds__(RS_THREADS) void resize_aa_yuv_list_kernel(const YuvImage* __restrict__ table, YuvListParams p) {
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<RS_THREADS>(table, p, 3, [&](const YuvImage& d, const YuvListParams& pp, float* yo, int hw, int px, int r, int q) {
+      aa_pixel<3>(aa_image(d, p.m), pp, yo, hw, px, r, q);
+    });
+    return;
+  }
   const int px = blockIdx.x * RS_THREADS + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
-    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, list_column<FLIP>(table[i].flip, p.W, q));
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+    const ListRQ m = list_rq<MODE>(table[i].flip, p.H, p.W, r, q);
+    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q);
+  }
 }
 
 template <class K, class... A>
@@ -864,10 +1044,16 @@ __global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_kernel(Resiz
 }
 
 // the list descriptor is one scalar load per workgroup, as in resize_u8_list_kernel
-template <bool AA, int C, bool FLIP>
+template <bool AA, int C, int MODE>
 __global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_list_kernel(const ResizeImage* __restrict__ table,
                                                                                 ResizeListParams p) {
   extern __shared__ float cubic_lds[];
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<cubic_threads<AA>()>(table, p, C, [&](const ResizeImage& d, const ResizeListParams& pp, float* yo, int hw, int px, int r, int q) {
+      cubic_any<AA, C>(CubicSrcU8<C>{d.x, d.row}, cubic_geom(d), pp, yo, hw, px, r, q, cubic_lds + threadIdx.x);
+    });
+    return;
+  }
   const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
@@ -875,15 +1061,21 @@ __global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_list_kernel(
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
     const ResizeImage d = table[i];
     const CubicSrcU8<C> src{d.x, d.row};
-    cubic_any<AA, C>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r,
-                     list_column<FLIP>(d.flip, p.W, q), cubic_lds + threadIdx.x);
+    const ListRQ m = list_rq<MODE>(d.flip, p.H, p.W, r, q);
+    cubic_any<AA, C>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q, cubic_lds + threadIdx.x);
   }
 }
 
-template <bool AA, bool FLIP>
+template <bool AA, int MODE>
 __global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_nv12_list_kernel(const Nv12Image* __restrict__ table,
                                                                                      Nv12ListParams p) {
   extern __shared__ float cubic_lds[];
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<cubic_threads<AA>()>(table, p, 3, [&](const Nv12Image& d, const Nv12ListParams& pp, float* yo, int hw, int px, int r, int q) {
+      cubic_any<AA, 3>(CubicSrcNv12{d.y, d.uv, d.yrow, d.uvrow, p.m}, cubic_geom(d), pp, yo, hw, px, r, q, cubic_lds + threadIdx.x);
+    });
+    return;
+  }
   const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
@@ -891,64 +1083,84 @@ __global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_nv12_list_ke
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
     const Nv12Image d = table[i];
     const CubicSrcNv12 src{d.y, d.uv, d.yrow, d.uvrow, p.m};
-    cubic_any<AA, 3>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r,
-                     list_column<FLIP>(d.flip, p.W, q), cubic_lds + threadIdx.x);
+    const ListRQ m = list_rq<MODE>(d.flip, p.H, p.W, r, q);
+    cubic_any<AA, 3>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q, cubic_lds + threadIdx.x);
   }
 }
 
 // the way to fetch is chosen once per image from the descriptor (wave-uniform), as in resize_yuv_list_kernel
-template <bool AA, bool FLIP>
+template <bool AA>
+__device__ __forceinline__ void cubic_yuv_pixel(const YuvImage& d, const YuvListParams& p, float* __restrict__ yi, int HW, int px,
+                                                int r, int q, float* __restrict__ u) {
+  const CubicGeom g = cubic_geom(d);
+  switch (yuv_fetch(d)) {
+    case YUV_PACKED: cubic_any<AA, 3>(CubicSrcYuv<YUV_PACKED>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
+    case YUV_PAIRS: cubic_any<AA, 3>(CubicSrcYuv<YUV_PAIRS>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
+    case YUV_PLANES: cubic_any<AA, 3>(CubicSrcYuv<YUV_PLANES>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
+    default: cubic_any<AA, 3>(CubicSrcYuv<YUV_GREY>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
+  }
+}
+
+template <bool AA, int MODE>
 __global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_yuv_list_kernel(const YuvImage* __restrict__ table,
                                                                                     YuvListParams p) {
   extern __shared__ float cubic_lds[];
+  if constexpr (MODE == LIST_ORIENT) {
+    list_tiled<cubic_threads<AA>()>(table, p, 3, [&](const YuvImage& d, const YuvListParams& pp, float* yo, int hw, int px, int r, int q) {
+      cubic_yuv_pixel<AA>(d, pp, yo, hw, px, r, q, cubic_lds + threadIdx.x);
+    });
+    return;
+  }
   const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
   for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
     const YuvImage d = table[i];
-    const CubicGeom g = cubic_geom(d);
-    float* yi = p.y + size_t(i) * size_t(p.y_nstride);
-    const int qq = list_column<FLIP>(d.flip, p.W, q);
-    float* u = cubic_lds + threadIdx.x;
-    switch (yuv_fetch(d)) {
-      case YUV_PACKED: cubic_any<AA, 3>(CubicSrcYuv<YUV_PACKED>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
-      case YUV_PAIRS: cubic_any<AA, 3>(CubicSrcYuv<YUV_PAIRS>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
-      case YUV_PLANES: cubic_any<AA, 3>(CubicSrcYuv<YUV_PLANES>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
-      default: cubic_any<AA, 3>(CubicSrcYuv<YUV_GREY>{d, p.m}, g, p, yi, HW, px, r, qq, u); break;
-    }
+    const ListRQ m = list_rq<MODE>(d.flip, p.H, p.W, r, q);
+    cubic_yuv_pixel<AA>(d, p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q, cubic_lds + threadIdx.x);
   }
 }
 
+// blocks of T threads for an H x W output: one per T pixels, or under LIST_ORIENT one per tile of T / 16 rows x 16 columns
+inline dim3 list_grid(int H, int W, long long N, int T, int mode = LIST_PLAIN) {
+  const unsigned gy = unsigned(N < 65535 ? N : 65535);
+  if (mode == LIST_ORIENT) return dim3(unsigned(((H + T / TILE_W - 1) / (T / TILE_W)) * ((W + TILE_W - 1) / TILE_W)), gy);
+  return dim3(unsigned(((long long)H * W + T - 1) / T), gy);
+}
+
+// the instance of a list kernel template K<..., MODE> for ResizeListParams::flips (a ListMode)
+#define ORE_LIST_KERNEL(mode, K, ...) \
+  ((mode) == LIST_ORIENT ? K<__VA_ARGS__ LIST_ORIENT> : (mode) ? K<__VA_ARGS__ LIST_FLIP> : K<__VA_ARGS__ LIST_PLAIN>)
+
 // grid, workgroup and LDS of a cubic launch: the plain filter takes no LDS; `taps` bounds the antialiased runs' columns
 template <bool AA, class K, class... A>
-void cubic_launch(K k, int H, int W, long long N, int taps, hipStream_t s, A... a) {
+void cubic_launch(K k, int H, int W, long long N, int taps, int mode, hipStream_t s, A... a) {
   constexpr int T = cubic_threads<AA>();
-  const long long hw = (long long)H * W;
-  const dim3 grid(unsigned((hw + T - 1) / T), unsigned(N < 65535 ? N : 65535));
   const size_t lds = AA ? size_t(taps) * T * sizeof(float) : 0;
-  hipLaunchKernelGGL(k, grid, dim3(T), lds, s, a...);
+  hipLaunchKernelGGL(k, list_grid(H, W, N, T, mode), dim3(T), lds, s, a...);
 }
 
 template <bool AA>
 void cubic_u8(const ResizeParams& p, hipStream_t s) {
   const int taps = resize_cubic_aa_max_taps(p.Ws, p.Rw);
   switch (p.C) {
-    case 1: return cubic_launch<AA>(resize_cubic_kernel<AA, 1>, p.H, p.W, p.N, taps, s, p);
-    case 2: return cubic_launch<AA>(resize_cubic_kernel<AA, 2>, p.H, p.W, p.N, taps, s, p);
-    case 3: return cubic_launch<AA>(resize_cubic_kernel<AA, 3>, p.H, p.W, p.N, taps, s, p);
-    default: return cubic_launch<AA>(resize_cubic_kernel<AA, 4>, p.H, p.W, p.N, taps, s, p);
+    case 1: return cubic_launch<AA>(resize_cubic_kernel<AA, 1>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
+    case 2: return cubic_launch<AA>(resize_cubic_kernel<AA, 2>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
+    case 3: return cubic_launch<AA>(resize_cubic_kernel<AA, 3>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
+    default: return cubic_launch<AA>(resize_cubic_kernel<AA, 4>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
   }
 }
 
-template <bool AA, bool FLIP>
+template <bool AA>
 void cubic_u8_list(const ResizeListParams& p, hipStream_t s) {
   const ResizeImage* table = p.table + p.first;
+  const int m = p.flips;
   switch (p.C) {
-    case 1: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 1, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
-    case 2: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 2, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
-    case 3: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 3, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
-    default: return cubic_launch<AA>(resize_cubic_list_kernel<AA, 4, FLIP>, p.H, p.W, p.N, p.taps, s, table, p);
+    case 1: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 1,), p.H, p.W, p.N, p.taps, m, s, table, p);
+    case 2: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 2,), p.H, p.W, p.N, p.taps, m, s, table, p);
+    case 3: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 3,), p.H, p.W, p.N, p.taps, m, s, table, p);
+    default: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 4,), p.H, p.W, p.N, p.taps, m, s, table, p);
   }
 }
 
@@ -964,39 +1176,31 @@ void launch_resize_cubic_u8(const ResizeParams& p, bool aa, hipStream_t s) {
 
 void launch_resize_cubic_u8_list(const ResizeListParams& p, bool aa, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  if (aa)
-    p.flips ? cubic_u8_list<true, true>(p, s) : cubic_u8_list<true, false>(p, s);
-  else
-    p.flips ? cubic_u8_list<false, true>(p, s) : cubic_u8_list<false, false>(p, s);
+  aa ? cubic_u8_list<true>(p, s) : cubic_u8_list<false>(p, s);
 }
 
 void launch_resize_cubic_nv12_list(const Nv12ListParams& p, bool aa, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
   const Nv12Image* table = p.table + p.first;
   if (aa)
-    cubic_launch<true>(p.flips ? resize_cubic_nv12_list_kernel<true, true> : resize_cubic_nv12_list_kernel<true, false>, p.H, p.W,
-                       p.N, p.taps, s, table, p);
+    cubic_launch<true>(ORE_LIST_KERNEL(p.flips, resize_cubic_nv12_list_kernel, true,), p.H, p.W, p.N, p.taps, p.flips, s, table, p);
   else
-    cubic_launch<false>(p.flips ? resize_cubic_nv12_list_kernel<false, true> : resize_cubic_nv12_list_kernel<false, false>, p.H,
-                        p.W, p.N, 0, s, table, p);
+    cubic_launch<false>(ORE_LIST_KERNEL(p.flips, resize_cubic_nv12_list_kernel, false,), p.H, p.W, p.N, 0, p.flips, s, table, p);
 }
 
 void launch_resize_cubic_yuv_list(const YuvListParams& p, bool aa, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
   const YuvImage* table = p.table + p.first;
   if (aa)
-    cubic_launch<true>(p.flips ? resize_cubic_yuv_list_kernel<true, true> : resize_cubic_yuv_list_kernel<true, false>, p.H, p.W,
-                       p.N, p.taps, s, table, p);
+    cubic_launch<true>(ORE_LIST_KERNEL(p.flips, resize_cubic_yuv_list_kernel, true,), p.H, p.W, p.N, p.taps, p.flips, s, table, p);
   else
-    cubic_launch<false>(p.flips ? resize_cubic_yuv_list_kernel<false, true> : resize_cubic_yuv_list_kernel<false, false>, p.H,
-                        p.W, p.N, 0, s, table, p);
+    cubic_launch<false>(ORE_LIST_KERNEL(p.flips, resize_cubic_yuv_list_kernel, false,), p.H, p.W, p.N, 0, p.flips, s, table, p);
 }
 
 void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
   if (p.Hs <= p.Rh && p.Ws <= p.Rw) return launch_resize_u8(p, s);  // nothing shrinks: the plain filter, bit for bit
-  const long long hw = (long long)p.H * p.W;
-  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
+  const dim3 grid = list_grid(p.H, p.W, p.N, RS_THREADS);
   switch (p.C) {
     case 1: return aa_launch(resize_aa_pixel_kernel<1>, grid, s, p);
     case 2: return aa_launch(resize_aa_pixel_kernel<2>, grid, s, p);
@@ -1008,65 +1212,43 @@ void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s) {
 void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
   const ResizeImage* table = p.table + p.first;
-  const long long hw = (long long)p.H * p.W;
-  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
-  if (p.flips) {
-    switch (p.C) {
-      case 1: return aa_launch(resize_aa_pixel_list_kernel<1, true>, grid, s, table, p);
-      case 2: return aa_launch(resize_aa_pixel_list_kernel<2, true>, grid, s, table, p);
-      case 3: return aa_launch(resize_aa_pixel_list_kernel<3, true>, grid, s, table, p);
-      default: return aa_launch(resize_aa_pixel_list_kernel<4, true>, grid, s, table, p);
-    }
-  }
+  const dim3 grid = list_grid(p.H, p.W, p.N, RS_THREADS, p.flips);
   switch (p.C) {
-    case 1: return aa_launch(resize_aa_pixel_list_kernel<1, false>, grid, s, table, p);
-    case 2: return aa_launch(resize_aa_pixel_list_kernel<2, false>, grid, s, table, p);
-    case 3: return aa_launch(resize_aa_pixel_list_kernel<3, false>, grid, s, table, p);
-    default: return aa_launch(resize_aa_pixel_list_kernel<4, false>, grid, s, table, p);
+    case 1: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 1,), grid, s, table, p);
+    case 2: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 2,), grid, s, table, p);
+    case 3: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 3,), grid, s, table, p);
+    default: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 4,), grid, s, table, p);
   }
 }
 
 void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  const long long hw = (long long)p.H * p.W;
-  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
-  aa_launch(p.flips ? resize_nv12_list_kernel<true> : resize_nv12_list_kernel<false>, grid, s, p.table + p.first, p);
+  aa_launch(ORE_LIST_KERNEL(p.flips, resize_nv12_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
 void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  const long long hw = (long long)p.H * p.W;
-  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
-  aa_launch(p.flips ? resize_aa_nv12_list_kernel<true> : resize_aa_nv12_list_kernel<false>, grid, s, p.table + p.first, p);
+  aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_nv12_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
 void launch_resize_yuv_list(const YuvListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  const long long hw = (long long)p.H * p.W;
-  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
-  aa_launch(p.flips ? resize_yuv_list_kernel<true> : resize_yuv_list_kernel<false>, grid, s, p.table + p.first, p);
+  aa_launch(ORE_LIST_KERNEL(p.flips, resize_yuv_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
 void launch_resize_aa_yuv_list(const YuvListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  const long long hw = (long long)p.H * p.W;
-  const dim3 grid(unsigned((hw + RS_THREADS - 1) / RS_THREADS), unsigned(p.N < 65535 ? p.N : 65535));
-  aa_launch(p.flips ? resize_aa_yuv_list_kernel<true> : resize_aa_yuv_list_kernel<false>, grid, s, p.table + p.first, p);
+  aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_yuv_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
 void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  const unsigned gy = unsigned(p.N < 65535 ? p.N : 65535);
-  const long long hw = (long long)p.H * p.W;
-  aa_launch(p.flips ? resize_u8_list_kernel<true> : resize_u8_list_kernel<false>,
-            dim3(unsigned((hw + RS_THREADS - 1) / RS_THREADS), gy), s, p.table + p.first, p);
+  aa_launch(ORE_LIST_KERNEL(p.flips, resize_u8_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
 void launch_resize_u8(const ResizeParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  const unsigned gy = unsigned(p.N < 65535 ? p.N : 65535);
-  const long long hw = (long long)p.H * p.W;
-  hipLaunchKernelGGL(resize_u8_generic_kernel, dim3(unsigned((hw + RS_THREADS - 1) / RS_THREADS), gy), dim3(RS_THREADS), 0, s, p);
+  hipLaunchKernelGGL(resize_u8_generic_kernel, list_grid(p.H, p.W, p.N, RS_THREADS), dim3(RS_THREADS), 0, s, p);
 }
 
 }  // namespace ore

@@ -60,6 +60,8 @@ EXPORTED = [
     "ore_topk_f32", "ore_model_set_topk", "ore_model_classify", "ore_model_classify_u8",
     "ore_model_graph_capture_classify", "ore_model_graph_capture_classify_u8",
     "ore_image_list_set_ex", "ore_image_list_set_nv12_ex", "ore_topk_mean_f32", "ore_model_set_views",
+    "ore_orient_geometry", "ore_image_check_oriented", "ore_image_check_nv12_oriented", "ore_image_check_yuv_oriented",
+    "ore_image_list_set_oriented", "ore_image_list_set_nv12_oriented", "ore_image_list_set_yuv_oriented", "ore_image_list_oriented",
     "ore_model_parse", "ore_model_load", "ore_model_load_ex", "ore_model_destroy", "ore_model_set_fusion", "ore_model_input_dims",
     "ore_model_output_elems", "ore_model_run", "ore_model_read_value", "ore_model_autotune",
     "ore_model_step_tile", "ore_model_set_step_tile", "ore_model_step_mfma_flops", "ore_model_set_streams",
@@ -135,6 +137,7 @@ def load():
     T = ctypes.POINTER(Tensor)
     I64P = ctypes.POINTER(ctypes.c_int64)
     F32P = ctypes.POINTER(ctypes.c_float)
+    U8P = ctypes.POINTER(ctypes.c_uint8)
     sig = {
         "ore_abi_version": (i32, []),
         "ore_ctx_create": (i32, [i32, ctypes.POINTER(vp)]),
@@ -205,6 +208,15 @@ def load():
         "ore_model_graph_capture_classify_u8": (i32, [vp, vp, i64, vp, vp]),
         "ore_image_list_set_ex": (i32, [vp, ctypes.POINTER(ImageU8), ctypes.POINTER(ctypes.c_uint32), i64]),
         "ore_image_list_set_nv12_ex": (i32, [vp, ctypes.POINTER(ImageNv12), ctypes.POINTER(ctypes.c_uint32), i64]),
+        "ore_orient_geometry": (i32, [i32, ctypes.POINTER(Resize), i64, i64, ctypes.POINTER(Resize), I64P, I64P,
+                                      ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "ore_image_check_oriented": (i32, [ctypes.POINTER(ImageU8), i64, i64, i64, i64, i32, U8P, I64P]),
+        "ore_image_check_nv12_oriented": (i32, [ctypes.POINTER(ImageNv12), i64, i64, i64, i32, U8P, I64P]),
+        "ore_image_check_yuv_oriented": (i32, [ctypes.POINTER(ImageYuv), i64, i64, i64, i32, U8P, I64P]),
+        "ore_image_list_set_oriented": (i32, [vp, ctypes.POINTER(ImageU8), ctypes.POINTER(ctypes.c_uint32), U8P, i64]),
+        "ore_image_list_set_nv12_oriented": (i32, [vp, ctypes.POINTER(ImageNv12), ctypes.POINTER(ctypes.c_uint32), U8P, i64]),
+        "ore_image_list_set_yuv_oriented": (i32, [vp, ctypes.POINTER(ImageYuv), ctypes.POINTER(ctypes.c_uint32), U8P, i64]),
+        "ore_image_list_oriented": (i32, [vp]),
         "ore_topk_mean_f32": (i32, [vp, T, i32, i32, vp, vp]),
         "ore_model_set_views": (i32, [vp, i32]),
         "ore_model_parse": (i32, [ctypes.c_char_p, ctypes.c_size_t]),

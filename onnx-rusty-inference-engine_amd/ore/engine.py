@@ -432,6 +432,79 @@ def _flip_words(flips, n: int):
     return words
 
 
+# EXIF orientation code -> (rows reversed, columns reversed, transposed): include/ore.h, ore_orient_geometry
+_ORIENT_BITS = {1: (False, False, False), 2: (False, True, False), 3: (True, True, False), 4: (True, False, False),
+                5: (False, False, True), 6: (True, False, True), 7: (True, True, True), 8: (False, True, True)}
+
+
+def _orient_code(code, name: str = "orientation") -> int:
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or int(code) not in _ORIENT_BITS:
+        raise OreError(1, f"{name}: orientation {code!r} is not an EXIF code 1..8")
+    return int(code)
+
+
+def oriented_hw(src_hw, code):
+    """The displayed size of a stored image of `src_hw` under EXIF orientation `code`: (ws, hs) for codes 5..8."""
+    hs, ws = (int(v) for v in src_hw)
+    return (ws, hs) if _ORIENT_BITS[_orient_code(code)][2] else (hs, ws)
+
+
+def apply_orientation(x, code):
+    """The displayed image of a stored [H, W, ...] numpy array or torch tensor under EXIF orientation `code`
+    (include/ore.h has the pixel table; it is PIL's ImageOps.exif_transpose): rows and / or columns reversed, then
+    transposed.  A view of a numpy array; torch reverses by copying.  For references and tests: the oriented lists
+    never materialise it."""
+    rev_rows, rev_cols, transpose = _ORIENT_BITS[_orient_code(code)]
+    if len(x.shape) < 2:
+        raise OreError(1, f"apply_orientation: expected [H, W, ...], got {tuple(x.shape)}")
+    if isinstance(x, np.ndarray):
+        if rev_rows:
+            x = x[::-1]
+        if rev_cols:
+            x = x[:, ::-1]
+        return x.swapaxes(0, 1) if transpose else x
+    dims = [d for d, on in ((0, rev_rows), (1, rev_cols)) if on]
+    if dims:
+        x = x.flip(dims)
+    return x.transpose(0, 1) if transpose else x
+
+
+def rotation_orientation(degrees_clockwise) -> int:
+    """The EXIF code of a video display matrix's rotation: the frame is to be rotated `degrees_clockwise` to be
+    displayed.  0 -> 1, 90 -> 6, 180 -> 3, 270 -> 8; other angles are not orientations."""
+    table = {0: 1, 90: 6, 180: 3, 270: 8}
+    if isinstance(degrees_clockwise, bool) or not isinstance(degrees_clockwise, (int, np.integer)) or int(degrees_clockwise) % 360 not in table:
+        raise OreError(1, f"rotation_orientation: {degrees_clockwise!r} degrees (a multiple of 90)")
+    return table[int(degrees_clockwise) % 360]
+
+
+def orient_geometry(code, resized_hw, origin, out_hw):
+    """ore_orient_geometry (host only): a displayed-space geometry (resized_hw, origin) of an `out_hw` list under EXIF
+    orientation `code`, in stored space: ((rh_s, rw_s), (top_s, left_s), (hz, wz), rev_rows, rev_cols, transpose).
+    Oriented image = the unoriented image of an (hz, wz) list with that stored geometry, its rows and / or columns
+    reversed and then transposed as the three flags say.  The map the kernels use."""
+    g = Resize(int(resized_hw[0]), int(resized_hw[1]), int(origin[0]), int(origin[1]))
+    sg = Resize()
+    hz, wz = ctypes.c_int64(), ctypes.c_int64()
+    rr, rc, tr = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    check(load().ore_orient_geometry(int(code), ctypes.byref(g), int(out_hw[0]), int(out_hw[1]), ctypes.byref(sg), ctypes.byref(hz),
+                                     ctypes.byref(wz), ctypes.byref(rr), ctypes.byref(rc), ctypes.byref(tr)))
+    return (sg.rh, sg.rw), (sg.top, sg.left), (hz.value, wz.value), bool(rr.value), bool(rc.value), bool(tr.value)
+
+
+def _orient_bytes(orientations, n: int):
+    """The HOST code array of the _set_oriented entries from `orientations`, one EXIF code per image."""
+    if orientations is None:
+        raise OreError(1, "set_oriented: orientations is None (set() is the entry without them)")
+    codes = list(orientations)
+    if len(codes) != n:
+        raise OreError(1, f"set_oriented: {len(codes)} orientations for {n} images")
+    arr = (ctypes.c_uint8 * max(n, 1))()
+    for i, c in enumerate(codes):
+        arr[i] = _orient_code(c, f"orientations[{i}]")
+    return arr
+
+
 class ImageList:
     """ore_image_list: up to `capacity` uint8 images of their own sizes and row strides, each resized and
     cropped to out_hw by its own geometry in ONE launch (preprocess_list_u8, Model.run_u8_list, ...).  The
@@ -467,17 +540,10 @@ class ImageList:
         for i, x in enumerate(images):
             _check_image_u8(x, self.ctx.device, self.channels, f"images[{i}]")
             hs, ws = int(x.shape[0]), int(x.shape[1])
-            if geometries is not None:
-                resized, origin = geometries[i]
-            elif short is not None:
-                resized, origin = center_crop_geometry((hs, ws), short, self.out_hw)
-            else:
-                resized, origin = None, (0, 0)
             arr[i].data = x.data_ptr()
             arr[i].hs, arr[i].ws = hs, ws
             arr[i].row_stride = int(x.stride(0))
-            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"images[{i}]",
-                                   getattr(self, "cubic", False))
+            arr[i].g = self._geometry(i, hs, ws, geometries, short, f"images[{i}]")
         return images, arr
 
     def set(self, images, geometries=None, short=None, flips=None):
@@ -496,6 +562,44 @@ class ImageList:
             check(load().ore_image_list_set_ex(self.h, arr, words, len(images)), self.ctx.h)
         self._images = tuple(images)
         return self
+
+    _SET_ORIENTED = "ore_image_list_set_oriented"
+    _codes = None  # the EXIF codes of the set_oriented call in progress: _descriptors sizes its geometries by them
+
+    def _geometry(self, i, hs, ws, geometries, short, name):
+        """The ore_resize of image i of a set: in displayed space, which under set_oriented is the oriented size."""
+        shown = (hs, ws) if self._codes is None else oriented_hw((hs, ws), self._codes[i])
+        if geometries is not None:
+            resized, origin = geometries[i]
+        elif short is not None:
+            resized, origin = center_crop_geometry(shown, short, self.out_hw)
+        else:
+            resized, origin = None, (0, 0)
+        return _resize_arg(shown, self.out_hw, resized, origin, getattr(self, "antialias", False), name, getattr(self, "cubic", False))
+
+    def set_oriented(self, images, orientations, geometries=None, short=None, flips=None):
+        """set() with one EXIF orientation code 1..8 per image (the _set_oriented entries; rotation_orientation maps a
+        video's display rotation): what the decoder left undone.  The tensors stay the STORED images; geometries,
+        short= and the default plain resize are in DISPLAYED space (oriented_hw), as out_hw is.  Image i is, bit for
+        bit, the unoriented image of the stored-space window orient_geometry gives, permuted -- a permutation of the
+        resized stored image, not a resize of apply_orientation's bytes (last bits differ).  flips compose on top.
+        The first call marks the list (include/ore.h: captures of a marked list serve later orientations)."""
+        images = list(images)
+        codes = _orient_bytes(orientations, len(images))
+        self._codes = list(codes)[:len(images)]
+        try:
+            images, arr = self._descriptors(images, geometries, short)
+        finally:
+            self._codes = None
+        words = None if flips is None else _flip_words(flips, len(images))
+        check(getattr(load(), self._SET_ORIENTED)(self.h, arr, words, codes, len(images)), self.ctx.h)
+        self._images = tuple(images)
+        return self
+
+    @property
+    def oriented(self) -> bool:
+        """ore_image_list_oriented: an oriented set has succeeded on the list."""
+        return bool(load().ore_image_list_oriented(self.h))
 
     @property
     def count(self) -> int:
@@ -609,6 +713,8 @@ class Nv12ImageList(ImageList):
                                                 ctypes.byref(hnd)), ctx.h)
         self.h = hnd
 
+    _SET_ORIENTED = "ore_image_list_set_nv12_oriented"
+
     def _descriptors(self, frames, geometries, short):
         """The host checks of set(): the ore_image_nv12 array of `frames`, before any library call."""
         if geometries is not None and short is not None:
@@ -621,17 +727,10 @@ class Nv12ImageList(ImageList):
         arr = (_lib.ImageNv12 * max(len(frames), 1))()
         for i, f in enumerate(frames):
             y, uv, hs, ws = _check_frame_nv12(f, self.ctx.device, f"frames[{i}]")
-            if geometries is not None:
-                resized, origin = geometries[i]
-            elif short is not None:
-                resized, origin = center_crop_geometry((hs, ws), short, self.out_hw)
-            else:
-                resized, origin = None, (0, 0)
             arr[i].y, arr[i].uv = y.data_ptr(), uv.data_ptr()
             arr[i].hs, arr[i].ws = hs, ws
             arr[i].y_stride, arr[i].uv_stride = int(y.stride(0)), int(uv.stride(0))
-            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]",
-                                   getattr(self, "cubic", False))
+            arr[i].g = self._geometry(i, hs, ws, geometries, short, f"frames[{i}]")
         return frames, arr
 
     def set(self, frames, geometries=None, short=None, flips=None):
@@ -774,6 +873,8 @@ class YuvImageList(ImageList):
                                                ctypes.byref(hnd)), ctx.h)
         self.h = hnd
 
+    _SET_ORIENTED = "ore_image_list_set_yuv_oriented"
+
     def _descriptors(self, frames, geometries, short):
         """The host checks of set(): the ore_image_yuv array of `frames`, before any library call."""
         if geometries is not None and short is not None:
@@ -786,19 +887,12 @@ class YuvImageList(ImageList):
         arr = (_lib.ImageYuv * max(len(frames), 1))()
         for i, f in enumerate(frames):
             fmt, planes, hs, ws = _check_frame_yuv(f, self.ctx.device, f"frames[{i}]")
-            if geometries is not None:
-                resized, origin = geometries[i]
-            elif short is not None:
-                resized, origin = center_crop_geometry((hs, ws), short, self.out_hw)
-            else:
-                resized, origin = None, (0, 0)
             for k, p in enumerate(planes):
                 arr[i].plane[k] = p.data_ptr()
                 arr[i].stride[k] = int(p.stride(0))
             arr[i].hs, arr[i].ws = hs, ws
             arr[i].format = fmt
-            arr[i].g = _resize_arg((hs, ws), self.out_hw, resized, origin, getattr(self, "antialias", False), f"frames[{i}]",
-                                   getattr(self, "cubic", False))
+            arr[i].g = self._geometry(i, hs, ws, geometries, short, f"frames[{i}]")
         return frames, arr
 
     def set(self, frames, geometries=None, short=None, flips=None):
