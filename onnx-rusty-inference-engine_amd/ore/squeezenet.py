@@ -35,9 +35,19 @@ def _conv_params(rng, cout, cin, k):
     return wt, b
 
 
-def build(input_hw: int = 224, seed: int = 1234, num_classes: int = 1000, logit_gain: float = 1.0,
+def _hw(input_hw):
+    """An input size given as one integer (square) or an (H, W) pair -> (H, W)."""
+    if isinstance(input_hw, (int, np.integer)):
+        return int(input_hw), int(input_hw)
+    h, w = input_hw
+    return int(h), int(w)
+
+
+def build(input_hw=224, seed: int = 1234, num_classes: int = 1000, logit_gain: float = 1.0,
           pool4_ceil: bool = True) -> bytes:
-    """Return the ONNX ModelProto bytes of a SqueezeNet-1.0 with seeded weights."""
+    """Return the ONNX ModelProto bytes of a SqueezeNet-1.0 with seeded weights.  input_hw: the input
+    height and width, one integer for a square input or an (H, W) pair (the weights do not depend on it)."""
+    in_h, in_w = _hw(input_hw)
     rng = np.random.default_rng(seed)
     nodes, inits, inputs = [], [], []
 
@@ -86,12 +96,12 @@ def build(input_hw: int = 224, seed: int = 1234, num_classes: int = 1000, logit_
     nodes.append(w.encode_node("GlobalAveragePool", [x], ["pool10_1"], name="pool10"))
     nodes.append(w.encode_node("Softmax", ["pool10_1"], ["softmaxout_1"], name="softmax"))
 
-    graph_inputs = [w.encode_value_info("data_0", (1, 3, input_hw, input_hw))] + inputs
+    graph_inputs = [w.encode_value_info("data_0", (1, 3, in_h, in_w))] + inputs
     outputs = [w.encode_value_info("softmaxout_1", (1, num_classes, 1, 1))]
     return w.encode_model("squeezenet1.0-synthetic", nodes, inits, graph_inputs, outputs, opset=8)
 
 
-def build_calibrated(input_hw: int = 224) -> bytes:
+def build_calibrated(input_hw=224) -> bytes:
     """The zoo-calibrated SqueezeNet-1.0: build() with conv10's weights scaled by ZOO_LOGIT_GAIN (same
     topology, same work per image; bench.py's model and the strict-parity fixtures)."""
     return build(input_hw, logit_gain=ZOO_LOGIT_GAIN)
@@ -116,7 +126,8 @@ def macs_per_image(input_hw: int = 224) -> int:
     return total
 
 
-def synthetic_input(n: int, input_hw: int = 224, seed: int = 0) -> np.ndarray:
-    """U(-50, 50) images: the range of the zoo's squeezenet_data_0.pb (-48.9 .. 44.1)."""
+def synthetic_input(n: int, input_hw=224, seed: int = 0) -> np.ndarray:
+    """U(-50, 50) images: the range of the zoo's squeezenet_data_0.pb (-48.9 .. 44.1).  input_hw as in build()."""
+    h, w = _hw(input_hw)
     rng = np.random.default_rng(seed)
-    return rng.uniform(-50.0, 50.0, size=(n, 3, input_hw, input_hw)).astype(np.float32)
+    return rng.uniform(-50.0, 50.0, size=(n, 3, h, w)).astype(np.float32)
