@@ -30,8 +30,9 @@ struct ore_ctx {
 };
 
 // ore_image_list: a device table of `capacity` packed descriptors for one output shape and its pinned host
-// mirror, both allocated at creation; table[0, count) is what ore_image_list_set uploaded last.  An NV12 list
-// (format ORE_IMAGE_NV12, c = 3) has the pair of its own descriptor type instead, set by ore_image_list_set_nv12
+// mirror, both allocated at creation; table[0, count) is what the list's set entry uploaded last.  The descriptors
+// are of the list's format, desc_bytes each: ResizeImage (ORE_IMAGE_INTERLEAVED), Nv12Image (ORE_IMAGE_NV12, c = 3)
+// or YuvImage (ORE_IMAGE_YUV, c = 3); only the format's own set entry writes them (ore_image_list.cpp)
 struct ore_image_list {
   ore_ctx* ctx = nullptr;
   int64_t capacity = 0, count = 0;
@@ -43,12 +44,9 @@ struct ore_image_list {
   bool any_orient = false;             // the last set held an orientation other than 1: launches take the orientation-reading instance
   bool oriented = false;               // ore_image_list_oriented: an oriented set has succeeded once; captures record that instance
   int taps = 0;                        // ORE_FILTER_BICUBIC_AA: no column run of the last set is longer (sizes the kernels' LDS)
-  ore::ResizeImage* table = nullptr;   // device
-  ore::ResizeImage* mirror = nullptr;  // pinned host: the source of the stream-ordered upload
-  ore::Nv12Image* table_nv12 = nullptr;   // the same two of an NV12 list (table and mirror are then null)
-  ore::Nv12Image* mirror_nv12 = nullptr;
-  ore::YuvImage* table_yuv = nullptr;     // and of a YUV list (ORE_IMAGE_YUV, ore_image_list_set_yuv)
-  ore::YuvImage* mirror_yuv = nullptr;
+  size_t desc_bytes = 0;               // of one descriptor of the list's format
+  void* table = nullptr;               // device
+  void* mirror = nullptr;              // pinned host: the source of the stream-ordered upload
   hipEvent_t uploaded = nullptr;       // recorded after each upload; the next set waits on it before it rewrites the mirror
 };
 
@@ -233,6 +231,24 @@ ore_status run_maxpool(ore_ctx* ctx, const Ref& x, const Ref& y, int64_t N, int6
 // scale / shift: host arrays of c floats or null (1 / 0).  x, y, N and y_nstride are the caller's to set.
 ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const float* scale, const float* shift,
                           int32_t flags, PreprocParams* p);
+// the plane map, scale and shift preproc_params resolved, for the resizing conversions' parameter structs
+template <class P>
+void copy_norm(const PreprocParams& q, P* p) {
+  for (int s = 0; s < q.C; ++s) {
+    p->plane[s] = q.plane[s];
+    p->scale[s] = q.scale[s];
+    p->shift[s] = q.shift[s];
+  }
+}
+inline bool fits_i32(int64_t v) { return v >= 0 && v < (int64_t(1) << 31); }
+// elements between the images of t: its nstride, or dense
+int64_t nstride_of(const ore_tensor* t);
+bool filter_known(int32_t filter);  // an ore_resize_filter
+// The geometry rules every resizing conversion shares, each message written once: the sizes within RESIZE_MAX and
+// the h x w crop inside the resized image; then, after the caller's own rules, the antialiasing filter's ratio.
+// i: the descriptor of an image list the messages name ("image i: ..."); below 0 a dense conversion ("resize: ...")
+ore_status check_resize_window(ore_ctx* ctx, int64_t i, int64_t hs, int64_t ws, int64_t h, int64_t w, const ore_resize& g);
+ore_status check_resize_ratio(ore_ctx* ctx, int64_t i, int32_t filter, int64_t hs, int64_t ws, const ore_resize& g);
 // as preproc_params for the resizing conversion of [.,hs,ws,c] images to h x w (ore_preprocess_resize_u8 and
 // the model's _u8 entries after ore_model_set_input_resize): also checks the sizes against RESIZE_MAX and
 // that the crop lies inside the resized image

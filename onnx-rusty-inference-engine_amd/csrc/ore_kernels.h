@@ -1,5 +1,5 @@
 // Internal kernel launch interface (device pointers, resolved integer geometry).  The public
-// C ABI (include/ore.h) sits on top of this in ore_ops.cpp.
+// C ABI (include/ore.h) sits on top of this in ore_ops.cpp and ore_image_list.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -492,13 +492,11 @@ struct ResizeListParams {
                              // 1: the flag-reading instance; 2: the one that reads the orientation bits as well
   int taps;                  // ORE_FILTER_BICUBIC_AA: no column run of a descriptor is longer (1..RESIZE_AA_MAX_TAPS)
 };
-void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s);
 // the same two conversions under ORE_FILTER_BILINEAR_AA: axes that shrink take the area-weighted filter of
 // ore_resize_geom.h (every such axis within RESIZE_AA_MAX_RATIO, checked by the caller), the others resize_tap.
 // One thread per output pixel (resize_aa_pixel_kernel and its list form); a dense launch in which nothing
 // shrinks goes to launch_resize_u8.
 void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s);
-void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s);
 // the list conversions over NV12 frames (ore_image_list_create_nv12): a full-resolution Y plane and a
 // half-resolution interleaved UV plane, each with its own pitch; source pixel (r, j) is Y at (r, j) and the UV
 // pair at (r >> 1, j >> 1), converted to R, G, B bytes by ore_yuv.h under the list's matrix.  The result is
@@ -524,8 +522,6 @@ struct Nv12ListParams {
   int flips;               // as ResizeListParams::flips
   int taps;                // as ResizeListParams::taps
 };
-void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s);
-void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s);
 // the list conversions over YUV frames of any ore_yuv_format (ore_image_list_create_yuv): every format reduced by
 // ore_image_list_set_yuv to strided planes, so that the kernels never see the format.  Source pixel (r, j) is
 //     Y = y[r * yrow + j * ystep],  U = u[(r >> sy) * urow + (j >> sx) * cstep],  V = v[(r >> sy) * vrow + (j >> sx) * cstep]
@@ -558,14 +554,14 @@ struct YuvListParams {
   int flips;               // as ResizeListParams::flips
   int taps;                // as ResizeListParams::taps
 };
-void launch_resize_yuv_list(const YuvListParams& p, hipStream_t s);
-void launch_resize_aa_yuv_list(const YuvListParams& p, hipStream_t s);
-// every conversion above under the cubic filters (ORE_FILTER_BICUBIC; aa: ORE_FILTER_BICUBIC_AA, every axis within
-// RESIZE_CUBIC_AA_MAX_RATIO, checked by the caller): resize_cubic_kernel and its list forms, one thread per pixel
+// the dense conversion under the cubic filters (ORE_FILTER_BICUBIC; aa: ORE_FILTER_BICUBIC_AA, every axis within
+// RESIZE_CUBIC_AA_MAX_RATIO, checked by the caller): resize_cubic_kernel, one thread per pixel
 void launch_resize_cubic_u8(const ResizeParams& p, bool aa, hipStream_t s);
-void launch_resize_cubic_u8_list(const ResizeListParams& p, bool aa, hipStream_t s);
-void launch_resize_cubic_nv12_list(const Nv12ListParams& p, bool aa, hipStream_t s);
-void launch_resize_cubic_yuv_list(const YuvListParams& p, bool aa, hipStream_t s);
+// The list conversions, one overload per descriptor format: the kernel of `filter` (an ore_resize_filter, known to
+// the caller's checks: bilinear, its antialiased form, or the cubic pair in their list forms) and of p.flips.
+void launch_resize_list(const ResizeListParams& p, int32_t filter, hipStream_t s);
+void launch_resize_list(const Nv12ListParams& p, int32_t filter, hipStream_t s);
+void launch_resize_list(const YuvListParams& p, int32_t filter, hipStream_t s);
 // row-wise top-k (ore_topk.hip): row r of x starts at x + r * stride (stride >= D); values / indices are
 // contiguous [rows][k], 1 <= k <= min(D, 64).  Order: larger first, ties by lower index, NaNs last.
 void launch_topk(const float* x, long long stride, long long rows, int D, int k, float* values, int* indices,

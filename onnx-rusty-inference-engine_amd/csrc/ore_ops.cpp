@@ -77,7 +77,7 @@ ore_status resolve_window(ore_ctx* ctx, int auto_pad, const int64_t* pads, int n
   }
 }
 
-static int64_t nstride_of(const ore_tensor* t) {
+int64_t nstride_of(const ore_tensor* t) {
   if (t->nstride) return t->nstride;
   int64_t s = 1;
   for (int i = 1; i < t->ndim; ++i) s *= t->dims[i];
@@ -99,8 +99,6 @@ static bool contiguous(const ore_tensor* t) {
   for (int i = 1; i < t->ndim; ++i) s *= t->dims[i];
   return t->nstride == s;
 }
-
-static bool fits_i32(int64_t v) { return v >= 0 && v < (int64_t(1) << 31); }
 
 // The image stride of a 4-D activation that may be a slice (Conv's and MaxPool's x and y): 0 (contiguous) or at
 // least one image's elements -- below that the images overlap and one image's outputs overwrite another's --
@@ -149,17 +147,7 @@ ore_status preproc_params(ore_ctx* ctx, int64_t h, int64_t w, int64_t c, const f
   return ORE_OK;
 }
 
-// the plane map, scale and shift preproc_params resolved, for the resizing conversions' parameter structs
-template <class P>
-static void copy_norm(const PreprocParams& q, P* p) {
-  for (int s = 0; s < q.C; ++s) {
-    p->plane[s] = q.plane[s];
-    p->scale[s] = q.scale[s];
-    p->shift[s] = q.shift[s];
-  }
-}
-
-static bool filter_known(int32_t filter) {
+bool filter_known(int32_t filter) {
   return filter == ORE_FILTER_BILINEAR || filter == ORE_FILTER_BILINEAR_AA || filter == ORE_FILTER_BICUBIC ||
          filter == ORE_FILTER_BICUBIC_AA;
 }
@@ -178,6 +166,33 @@ static const char* aa_bad_axis(int32_t filter, int64_t hs, int64_t ws, const ore
   return nullptr;
 }
 
+// what a geometry message opens with: "resize" of a dense conversion (i < 0), "image i" of a list's descriptor
+struct Subject {
+  char s[32];
+  explicit Subject(int64_t i) {
+    if (i < 0) snprintf(s, sizeof s, "resize");
+    else snprintf(s, sizeof s, "image %lld", (long long)i);
+  }
+};
+
+ore_status check_resize_window(ore_ctx* ctx, int64_t i, int64_t hs, int64_t ws, int64_t h, int64_t w, const ore_resize& g) {
+  if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX)
+    return set_error(ctx, ORE_ERR_INVALID, "%s: source %lld x %lld resized to %lld x %lld (each 1..%d)", Subject(i).s, (long long)hs,
+                     (long long)ws, (long long)g.rh, (long long)g.rw, RESIZE_MAX);
+  if (!resize_axis_ok(hs, g.rh, g.top, h) || !resize_axis_ok(ws, g.rw, g.left, w))
+    return set_error(ctx, ORE_ERR_INVALID, "%s: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
+                     Subject(i).s, (long long)h, (long long)w, (long long)g.top, (long long)g.left, (long long)g.rh, (long long)g.rw);
+  return ORE_OK;
+}
+
+ore_status check_resize_ratio(ore_ctx* ctx, int64_t i, int32_t filter, int64_t hs, int64_t ws, const ore_resize& g) {
+  if (const char* axis = aa_bad_axis(filter, hs, ws, g))
+    return set_error(ctx, ORE_ERR_INVALID, "%s: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
+                     Subject(i).s, filter_max_ratio(filter), axis, (long long)(axis[0] == 'r' ? hs : ws),
+                     (long long)(axis[0] == 'r' ? g.rh : g.rw));
+  return ORE_OK;
+}
+
 ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_t h, int64_t w, const ore_resize* g,
                          const float* scale, const float* shift, int32_t flags, ResizeParams* p, int32_t filter) {
   if (!g) return set_error(ctx, ORE_ERR_INVALID, "null resize geometry");
@@ -185,93 +200,14 @@ ore_status resize_params(ore_ctx* ctx, int64_t hs, int64_t ws, int64_t c, int64_
     return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
   PreprocParams q;  // c, the flags, the reversal and the output size: the direct conversion's checks
   if (ore_status st = preproc_params(ctx, h, w, c, scale, shift, flags, &q)) return st;
-  if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g->rh < 1 || g->rw < 1 || g->rh > RESIZE_MAX || g->rw > RESIZE_MAX)
-    return set_error(ctx, ORE_ERR_INVALID, "resize: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)hs,
-                     (long long)ws, (long long)g->rh, (long long)g->rw, RESIZE_MAX);
-  if (!resize_axis_ok(hs, g->rh, g->top, h) || !resize_axis_ok(ws, g->rw, g->left, w))
-    return set_error(ctx, ORE_ERR_INVALID, "resize: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
-                     (long long)h, (long long)w, (long long)g->top, (long long)g->left, (long long)g->rh, (long long)g->rw);
-  if (const char* axis = aa_bad_axis(filter, hs, ws, *g))
-    return set_error(ctx, ORE_ERR_INVALID, "resize: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                     filter_max_ratio(filter), axis, (long long)(axis[0] == 'r' ? hs : ws), (long long)(axis[0] == 'r' ? g->rh : g->rw));
+  if (ore_status st = check_resize_window(ctx, -1, hs, ws, h, w, *g)) return st;
+  if (ore_status st = check_resize_ratio(ctx, -1, filter, hs, ws, *g)) return st;
   *p = ResizeParams{};
   p->Hs = int(hs); p->Ws = int(ws); p->C = int(c);
   p->Rh = int(g->rh); p->Rw = int(g->rw); p->top = int(g->top); p->left = int(g->left);
   p->H = int(h); p->W = int(w);
   copy_norm(q, p);
   return ORE_OK;
-}
-
-ore_status list_params(ore_ctx* ctx, const ore_image_list* l, const float* scale, const float* shift, int32_t flags,
-                       ResizeListParams* p) {
-  PreprocParams q;
-  if (ore_status st = preproc_params(ctx, l->h, l->w, l->c, scale, shift, flags, &q)) return st;
-  *p = ResizeListParams{};
-  p->table = l->table;
-  p->N = l->count;
-  p->C = int(l->c); p->H = int(l->h); p->W = int(l->w);
-  copy_norm(q, p);
-  return ORE_OK;
-}
-
-void launch_list(ore_ctx* ctx, const ore_image_list* l, const ResizeListParams& p0) {
-  // The flag-free instance of the kernel when no descriptor of the list is flipped.  Not inside a stream capture:
-  // a captured graph reads at replay whatever table a later set uploaded, flags included.
-  ResizeListParams p = p0;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool capturing = ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-  // The orientation-reading instance when the last set held a code other than 1; a capture records it for a list
-  // that an oriented set has marked, and otherwise what it recorded before there were orientations.
-  p.flips = capturing ? (l->oriented ? 2 : 1) : l->any_orient ? 2 : l->any_flip ? 1 : 0;
-  p.taps = capturing || l->taps < 1 ? RESIZE_AA_MAX_TAPS : l->taps;  // likewise: a later set may bring longer runs
-  if (l->format == ORE_IMAGE_YUV) {
-    YuvListParams q{};
-    q.table = l->table_yuv;
-    q.first = p.first; q.y = p.y; q.N = p.N; q.y_nstride = p.y_nstride;
-    q.H = p.H; q.W = p.W;
-    q.flips = p.flips;
-    q.taps = p.taps;
-    yuv_matrix(l->matrix, &q.m);  // checked at creation
-    for (int s = 0; s < 3; ++s) {
-      q.plane[s] = p.plane[s];
-      q.scale[s] = p.scale[s];
-      q.shift[s] = p.shift[s];
-    }
-    if (l->filter & ORE_FILTER_CUBIC_BIT)
-      launch_resize_cubic_yuv_list(q, l->filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
-    else if (l->filter == ORE_FILTER_BILINEAR_AA)
-      launch_resize_aa_yuv_list(q, ctx->stream);
-    else
-      launch_resize_yuv_list(q, ctx->stream);
-    return;
-  }
-  if (l->format == ORE_IMAGE_NV12) {
-    Nv12ListParams q{};
-    q.table = l->table_nv12;
-    q.first = p.first; q.y = p.y; q.N = p.N; q.y_nstride = p.y_nstride;
-    q.H = p.H; q.W = p.W;
-    q.flips = p.flips;
-    q.taps = p.taps;
-    yuv_matrix(l->matrix, &q.m);  // checked at creation
-    for (int s = 0; s < 3; ++s) {
-      q.plane[s] = p.plane[s];
-      q.scale[s] = p.scale[s];
-      q.shift[s] = p.shift[s];
-    }
-    if (l->filter & ORE_FILTER_CUBIC_BIT)
-      launch_resize_cubic_nv12_list(q, l->filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
-    else if (l->filter == ORE_FILTER_BILINEAR_AA)
-      launch_resize_aa_nv12_list(q, ctx->stream);
-    else
-      launch_resize_nv12_list(q, ctx->stream);
-    return;
-  }
-  if (l->filter & ORE_FILTER_CUBIC_BIT)
-    launch_resize_cubic_u8_list(p, l->filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
-  else if (l->filter == ORE_FILTER_BILINEAR_AA)
-    launch_resize_aa_u8_list(p, ctx->stream);
-  else
-    launch_resize_u8_list(p, ctx->stream);
 }
 
 ConvPlan conv_plan(int64_t M, int64_t C, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
@@ -1135,581 +1071,6 @@ ore_status ore_preprocess_resize_u8_ex(ore_ctx* ctx, const uint8_t* x, int64_t n
     launch_resize_aa_u8(p, ctx->stream);
   else
     launch_resize_u8(p, ctx->stream);
-  ORE_HIP_CHECK(ctx, hipGetLastError());
-  return ORE_OK;
-}
-
-// An EXIF orientation code 1..8 as the three permutation bits of ore_orient_geometry; false: not a code
-static bool orient_bits(int code, bool* rev_rows, bool* rev_cols, bool* transpose) {
-  if (code < 1 || code > 8) return false;
-  *rev_rows = code == 3 || code == 4 || code == 6 || code == 7;
-  *rev_cols = code == 2 || code == 3 || code == 7 || code == 8;
-  *transpose = code >= 5;
-  return true;
-}
-
-// the descriptor's geometry and the list's output shape in stored space (include/ore.h: ore_orient_geometry);
-// returns the LIST_* bits of the kernels' descriptor word
-static int orient_stored(int code, const ore_resize& g, int64_t h, int64_t w, ore_resize* sg, int64_t* hz, int64_t* wz) {
-  bool rr = false, rc = false, tr = false;
-  orient_bits(code, &rr, &rc, &tr);
-  *hz = tr ? w : h;
-  *wz = tr ? h : w;
-  sg->rh = tr ? g.rw : g.rh;
-  sg->rw = tr ? g.rh : g.rw;
-  const int64_t a0 = tr ? g.left : g.top, b0 = tr ? g.top : g.left;
-  sg->top = rr ? sg->rh - *hz - a0 : a0;
-  sg->left = rc ? sg->rw - *wz - b0 : b0;
-  return (rr ? LIST_REV_ROWS : 0) | (rc ? LIST_REV_COLS : 0) | (tr ? LIST_TRANSPOSE : 0);
-}
-
-ore_status ore_orient_geometry(int32_t orientation, const ore_resize* g, int64_t h, int64_t w, ore_resize* stored_g, int64_t* hz,
-                               int64_t* wz, int32_t* rev_rows, int32_t* rev_cols, int32_t* transpose) {
-  bool rr, rc, tr;
-  if (!orient_bits(orientation, &rr, &rc, &tr))
-    return set_error(nullptr, ORE_ERR_INVALID, "orientation %d is not an EXIF code 1..8", int(orientation));
-  if (!g) return set_error(nullptr, ORE_ERR_INVALID, "null resize geometry");
-  ore_resize sg;
-  int64_t hh, ww;
-  orient_stored(orientation, *g, h, w, &sg, &hh, &ww);
-  if (stored_g) *stored_g = sg;
-  if (hz) *hz = hh;
-  if (wz) *wz = ww;
-  if (rev_rows) *rev_rows = rr;
-  if (rev_cols) *rev_cols = rc;
-  if (transpose) *transpose = tr;
-  return ORE_OK;
-}
-
-// a descriptor's code in the checks: null orientations are all 1
-static ore_status check_orientation(const uint8_t* orientations, int64_t i) {
-  if (orientations && (orientations[i] < 1 || orientations[i] > 8))
-    return set_error(nullptr, ORE_ERR_INVALID, "image %lld: orientation %d is not an EXIF code 1..8", (long long)i, int(orientations[i]));
-  return ORE_OK;
-}
-
-ore_status ore_image_check(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int64_t* bad_index) {
-  return ore_image_check_ex(imgs, n, c, h, w, ORE_FILTER_BILINEAR, bad_index);
-}
-
-ore_status ore_image_check_ex(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h, int64_t w, int32_t filter,
-                              int64_t* bad_index) {
-  return ore_image_check_oriented(imgs, n, c, h, w, filter, nullptr, bad_index);
-}
-
-// Every check below judges a descriptor in stored space: its geometry and the output shape as orient_stored gives
-// them.  The crop rule there is the displayed-space rule (top_s + hz <= rh_s is top + h <= rh or left + w <= rw).
-ore_status ore_image_check_oriented(const ore_image_u8* imgs, int64_t n, int64_t c, int64_t h0, int64_t w0, int32_t filter,
-                                    const uint8_t* orientations, int64_t* bad_index) {
-  int64_t h = h0, w = w0;
-  if (!filter_known(filter))
-    return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
-  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
-  PreprocParams q;  // c and the output size: the direct conversion's checks
-  if (ore_status st = preproc_params(nullptr, h, w, c, nullptr, nullptr, 0, &q)) return st;
-  if (n == 0) return ORE_OK;
-  if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
-  for (int64_t i = 0; i < n; ++i) {
-    const ore_image_u8& d = imgs[i];
-    ore_resize g = d.g;
-    ore_status st = check_orientation(orientations, i);
-    if (!st && orientations) orient_stored(orientations[i], d.g, h0, w0, &g, &h, &w);
-    const long long hs = d.hs, ws = d.ws, rs = d.row_stride;
-    if (st) {  // a bad code: the descriptor's geometry is not looked at
-    } else if (!d.data)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null data pointer", (long long)i);
-    else if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
-                     ws, (long long)g.rh, (long long)g.rw, RESIZE_MAX);
-    else if (!resize_axis_ok(hs, g.rh, g.top, h) || !resize_axis_ok(ws, g.rw, g.left, w))
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
-                     (long long)i, (long long)h, (long long)w, (long long)g.top, (long long)g.left, (long long)g.rh, (long long)g.rw);
-    else if (rs != 0 && rs < ws * c)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: row stride %lld below ws*c = %lld", (long long)i, rs, ws * (long long)c);
-    else if (hs > 1 && (!fits_i32(rs) || !fits_i32((hs - 1) * (rs ? rs : ws * c) + ws * c)))  // a one-row image never steps a row
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hs, rs);
-    else if (const char* axis = aa_bad_axis(filter, hs, ws, g))
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                     (long long)i, filter_max_ratio(filter), axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
-    if (st) {
-      if (bad_index) *bad_index = i;
-      return st;
-    }
-  }
-  return ORE_OK;
-}
-
-ore_status ore_yuv_to_rgb(int32_t matrix, const uint8_t* y, const uint8_t* u, const uint8_t* v, int64_t n, uint8_t* rgb) {
-  YuvMatrix m;
-  if (!yuv_matrix(matrix, &m)) return set_error(nullptr, ORE_ERR_INVALID, "unknown YUV matrix %d", int(matrix));
-  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative count %lld", (long long)n);
-  if (n == 0) return ORE_OK;
-  if (!y || !u || !v || !rgb) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
-  for (int64_t i = 0; i < n; ++i) {
-    int c[3];
-    yuv_rgb(m, y[i], yuv_chroma(m, u[i], v[i]), c);
-    for (int s = 0; s < 3; ++s) rgb[3 * i + s] = uint8_t(c[s]);
-  }
-  return ORE_OK;
-}
-
-ore_status ore_image_check_nv12(const ore_image_nv12* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
-  return ore_image_check_nv12_oriented(imgs, n, h, w, filter, nullptr, bad_index);
-}
-
-ore_status ore_image_check_nv12_oriented(const ore_image_nv12* imgs, int64_t n, int64_t h0, int64_t w0, int32_t filter,
-                                         const uint8_t* orientations, int64_t* bad_index) {
-  int64_t h = h0, w = w0;
-  if (!filter_known(filter))
-    return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
-  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
-  PreprocParams q;  // the output size: the direct conversion's checks, with the three channels a frame converts to
-  if (ore_status st = preproc_params(nullptr, h, w, 3, nullptr, nullptr, 0, &q)) return st;
-  if (n == 0) return ORE_OK;
-  if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
-  for (int64_t i = 0; i < n; ++i) {
-    const ore_image_nv12& d = imgs[i];
-    ore_resize g = d.g;
-    ore_status st = check_orientation(orientations, i);
-    if (!st && orientations) orient_stored(orientations[i], d.g, h0, w0, &g, &h, &w);
-    const long long hs = d.hs, ws = d.ws, ys = d.y_stride, us = d.uv_stride;
-    const long long hc = (hs + 1) / 2, wc2 = 2 * ((ws + 1) / 2);  // UV rows, and the bytes of one
-    if (st) {  // a bad code: the descriptor's geometry is not looked at
-    } else if (!d.y || !d.uv)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null %s pointer", (long long)i, d.y ? "uv" : "y");
-    else if (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
-                     ws, (long long)g.rh, (long long)g.rw, RESIZE_MAX);
-    else if (!resize_axis_ok(hs, g.rh, g.top, h) || !resize_axis_ok(ws, g.rw, g.left, w))
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
-                     (long long)i, (long long)h, (long long)w, (long long)g.top, (long long)g.left, (long long)g.rh, (long long)g.rw);
-    else if (ys != 0 && ys < ws)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: y stride %lld below ws = %lld", (long long)i, ys, ws);
-    else if (us != 0 && us < wc2)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: uv stride %lld below 2*ceil(ws/2) = %lld", (long long)i, us, wc2);
-    else if (hs > 1 && (!fits_i32(ys) || !fits_i32((hs - 1) * (ys ? ys : ws) + ws)))  // a one-row plane never steps a row
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld y rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hs, ys);
-    else if (hc > 1 && (!fits_i32(us) || !fits_i32((hc - 1) * (us ? us : wc2) + wc2)))
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: %lld uv rows at a stride of %lld bytes reach past 2^31 bytes", (long long)i, hc, us);
-    else if (const char* axis = aa_bad_axis(filter, hs, ws, g))
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                     (long long)i, filter_max_ratio(filter), axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
-    if (st) {
-      if (bad_index) *bad_index = i;
-      return st;
-    }
-  }
-  return ORE_OK;
-}
-
-// What an ore_yuv_format is, for ore_image_check_yuv and for ore_image_list_set_yuv's reduction to strided planes
-// (YuvImage): the planes in use, the chroma shifts, and the bytes between the luma and the chroma samples of a row.
-struct YuvLayout {
-  const char* name;
-  int planes;  // plane[0 .. planes) are in use
-  int sx, sy;
-  int ystep, cstep;
-};
-
-static const YuvLayout* yuv_layout(int32_t format) {
-  static const YuvLayout table[] = {
-      {"NV12", 2, 1, 1, 1, 2}, {"YUYV", 1, 1, 0, 2, 4}, {"I444", 3, 0, 0, 1, 1}, {"I440", 3, 0, 1, 1, 1},
-      {"I422", 3, 1, 0, 1, 1}, {"I420", 3, 1, 1, 1, 1}, {"I411", 3, 2, 0, 1, 1}, {"GRAY", 1, 0, 0, 1, 0},
-  };
-  return format >= 0 && format < int32_t(sizeof(table) / sizeof(table[0])) ? &table[format] : nullptr;
-}
-
-// rows of plane k of an hs x ws frame, and the bytes of one
-static long long yuv_plane_rows(const YuvLayout& f, int k, long long hs) { return k == 0 ? hs : (hs + (1 << f.sy) - 1) >> f.sy; }
-static long long yuv_plane_row_bytes(const YuvLayout& f, int k, long long ws) {
-  if (k == 0) return f.ystep == 2 ? 4 * ((ws + 1) / 2) : ws;
-  return ((ws + (1 << f.sx) - 1) >> f.sx) * f.cstep;
-}
-
-ore_status ore_image_check_yuv(const ore_image_yuv* imgs, int64_t n, int64_t h, int64_t w, int32_t filter, int64_t* bad_index) {
-  return ore_image_check_yuv_oriented(imgs, n, h, w, filter, nullptr, bad_index);
-}
-
-ore_status ore_image_check_yuv_oriented(const ore_image_yuv* imgs, int64_t n, int64_t h0, int64_t w0, int32_t filter,
-                                        const uint8_t* orientations, int64_t* bad_index) {
-  int64_t h = h0, w = w0;
-  if (!filter_known(filter))
-    return set_error(nullptr, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
-  if (n < 0) return set_error(nullptr, ORE_ERR_INVALID, "negative image count %lld", (long long)n);
-  PreprocParams q;  // the output size: the direct conversion's checks, with the three channels a frame converts to
-  if (ore_status st = preproc_params(nullptr, h, w, 3, nullptr, nullptr, 0, &q)) return st;
-  if (n == 0) return ORE_OK;
-  if (!imgs) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
-  for (int64_t i = 0; i < n; ++i) {
-    const ore_image_yuv& d = imgs[i];
-    ore_resize g = d.g;
-    ore_status st = check_orientation(orientations, i);
-    if (!st && orientations) orient_stored(orientations[i], d.g, h0, w0, &g, &h, &w);
-    const long long hs = d.hs, ws = d.ws;
-    const YuvLayout* f = yuv_layout(d.format);
-    if (st) {  // a bad code: the descriptor's geometry is not looked at
-    } else if (!f)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: unknown YUV format %d", (long long)i, int(d.format));
-    else if (d.reserved != 0)
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: reserved is %d, it must be 0", (long long)i, int(d.reserved));
-    // from here on a rule is tried while none has failed, and f is then non-null
-    for (int k = 0; !st && k < 3; ++k) {
-      if (k < f->planes && !d.plane[k])
-        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: null plane %d pointer (%s has %d)", (long long)i, k, f->name, f->planes);
-      else if (k >= f->planes && d.plane[k])
-        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: plane %d must be null (%s has %d)", (long long)i, k, f->name, f->planes);
-    }
-    if (!st && (hs < 1 || ws < 1 || hs > RESIZE_MAX || ws > RESIZE_MAX || g.rh < 1 || g.rw < 1 || g.rh > RESIZE_MAX || g.rw > RESIZE_MAX))
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: source %lld x %lld resized to %lld x %lld (each 1..%d)", (long long)i, hs,
-                     ws, (long long)g.rh, (long long)g.rw, RESIZE_MAX);
-    if (!st && (!resize_axis_ok(hs, g.rh, g.top, h) || !resize_axis_ok(ws, g.rw, g.left, w)))
-      st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the %lld x %lld crop at (%lld, %lld) lies outside the %lld x %lld resized image",
-                     (long long)i, (long long)h, (long long)w, (long long)g.top, (long long)g.left, (long long)g.rh, (long long)g.rw);
-    for (int k = 0; !st && k < f->planes; ++k) {
-      const long long rb = yuv_plane_row_bytes(*f, k, ws), ps = d.stride[k];
-      if (ps != 0 && ps < rb)
-        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: plane %d stride %lld below its %lld row bytes", (long long)i, k, ps, rb);
-    }
-    for (int k = 0; !st && k < f->planes; ++k) {
-      const long long rows = yuv_plane_rows(*f, k, hs), rb = yuv_plane_row_bytes(*f, k, ws), ps = d.stride[k];
-      if (rows > 1 && (!fits_i32(ps) || !fits_i32((rows - 1) * (ps ? ps : rb) + rb)))  // a one-row plane never steps a row
-        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: plane %d: %lld rows at a stride of %lld bytes reach past 2^31 bytes",
-                       (long long)i, k, rows, ps);
-    }
-    if (!st)
-      if (const char* axis = aa_bad_axis(filter, hs, ws, g))
-        st = set_error(nullptr, ORE_ERR_INVALID, "image %lld: the antialiasing filter shrinks an axis at most %d times, the %s go %lld -> %lld",
-                       (long long)i, filter_max_ratio(filter), axis, axis[0] == 'r' ? hs : ws, (long long)(axis[0] == 'r' ? g.rh : g.rw));
-    if (st) {
-      if (bad_index) *bad_index = i;
-      return st;
-    }
-  }
-  return ORE_OK;
-}
-
-ore_status ore_image_list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, ore_image_list** out) {
-  return ore_image_list_create_ex(ctx, capacity, c, h, w, ORE_FILTER_BILINEAR, out);
-}
-
-int32_t ore_image_list_filter(ore_image_list* l) { return l ? l->filter : ORE_FILTER_BILINEAR; }
-
-// ore_image_list_create_ex, _create_nv12 and _create_yuv: the list and the table and mirror of its format
-static ore_status list_create(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter, int32_t format,
-                              int32_t matrix, ore_image_list** out) {
-  if (!ctx || !out) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (!filter_known(filter))
-    return set_error(ctx, ORE_ERR_INVALID, "unknown resize filter %d", int(filter));
-  YuvMatrix ym;
-  if (format != ORE_IMAGE_INTERLEAVED && !yuv_matrix(matrix, &ym))
-    return set_error(ctx, ORE_ERR_INVALID, "unknown YUV matrix %d", int(matrix));
-  PreprocParams q;
-  if (ore_status st = preproc_params(ctx, h, w, c, nullptr, nullptr, 0, &q)) return st;
-  if (capacity < 1 || !fits_i32(capacity))
-    return set_error(ctx, ORE_ERR_INVALID, "image list capacity %lld (1..2^31-1)", (long long)capacity);
-  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  ore_image_list* l = new ore_image_list();
-  l->ctx = ctx;
-  l->capacity = capacity;
-  l->c = c; l->h = h; l->w = w;
-  l->filter = filter;
-  l->format = format;
-  l->matrix = format != ORE_IMAGE_INTERLEAVED ? matrix : 0;
-  const bool nv12 = format == ORE_IMAGE_NV12, yuv = format == ORE_IMAGE_YUV;
-  const size_t bytes = size_t(capacity) * (yuv ? sizeof(YuvImage) : nv12 ? sizeof(Nv12Image) : sizeof(ResizeImage));
-  void** table = yuv ? reinterpret_cast<void**>(&l->table_yuv) : nv12 ? reinterpret_cast<void**>(&l->table_nv12) : reinterpret_cast<void**>(&l->table);
-  void** mirror = yuv ? reinterpret_cast<void**>(&l->mirror_yuv) : nv12 ? reinterpret_cast<void**>(&l->mirror_nv12) : reinterpret_cast<void**>(&l->mirror);
-  // the table holds device addresses and geometry: never filled (device_alloc, own = false)
-  if (device_alloc(ctx, table, bytes, false) != hipSuccess || hipHostMalloc(mirror, bytes, hipHostMallocDefault) != hipSuccess ||
-      hipEventCreateWithFlags(&l->uploaded, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)ore_image_list_destroy(l);
-    return set_error(ctx, ORE_ERR_OOM, "image list of %lld descriptors (%zu bytes) allocation failed", (long long)capacity, bytes);
-  }
-  *out = l;
-  return ORE_OK;
-}
-
-ore_status ore_image_list_create_ex(ore_ctx* ctx, int64_t capacity, int64_t c, int64_t h, int64_t w, int32_t filter,
-                                    ore_image_list** out) {
-  return list_create(ctx, capacity, c, h, w, filter, ORE_IMAGE_INTERLEAVED, 0, out);
-}
-
-ore_status ore_image_list_create_nv12(ore_ctx* ctx, int64_t capacity, int64_t h, int64_t w, int32_t filter, int32_t matrix,
-                                      ore_image_list** out) {
-  return list_create(ctx, capacity, 3, h, w, filter, ORE_IMAGE_NV12, matrix, out);
-}
-
-ore_status ore_image_list_create_yuv(ore_ctx* ctx, int64_t capacity, int64_t h, int64_t w, int32_t filter, int32_t matrix,
-                                     ore_image_list** out) {
-  return list_create(ctx, capacity, 3, h, w, filter, ORE_IMAGE_YUV, matrix, out);
-}
-
-int32_t ore_image_list_format(ore_image_list* l) { return l ? l->format : ORE_IMAGE_INTERLEAVED; }
-
-int32_t ore_image_list_matrix(ore_image_list* l) { return l ? l->matrix : ORE_YUV_BT601; }
-
-ore_status ore_image_list_destroy(ore_image_list* l) {
-  if (!l) return ORE_OK;
-  (void)hipSetDevice(l->ctx->device);
-  if (l->uploaded) {  // a pending upload still reads the mirror; launches that read the table are the caller's to finish
-    (void)hipEventSynchronize(l->uploaded);
-    (void)hipEventDestroy(l->uploaded);
-  }
-  if (l->mirror) (void)hipHostFree(l->mirror);
-  if (l->table) (void)hipFree(l->table);
-  if (l->mirror_nv12) (void)hipHostFree(l->mirror_nv12);
-  if (l->table_nv12) (void)hipFree(l->table_nv12);
-  if (l->mirror_yuv) (void)hipHostFree(l->mirror_yuv);
-  if (l->table_yuv) (void)hipFree(l->table_yuv);
-  delete l;
-  return ORE_OK;
-}
-
-int64_t ore_image_list_count(ore_image_list* l) { return l ? l->count : 0; }
-
-int32_t ore_image_list_oriented(ore_image_list* l) { return l && l->oriented ? 1 : 0; }
-
-// The two sets between the descriptors' check and the mirror's rewrite: the capacity, the capture rule, and the
-// wait for the previous upload to have read the mirror.  n == 0 empties the list here.
-static ore_status list_set_begin(ore_image_list* l, int64_t n) {
-  ore_ctx* ctx = l->ctx;
-  if (n > l->capacity)
-    return set_error(ctx, ORE_ERR_INVALID, "%lld images exceed the list's capacity %lld", (long long)n, (long long)l->capacity);
-  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set inside a stream capture: a captured graph reads the table at "
-                                           "replay, set it before or after the capture");
-  if (n == 0) {
-    l->count = 0;
-    return ORE_OK;
-  }
-  ORE_HIP_CHECK(ctx, hipEventSynchronize(l->uploaded));  // the previous upload has read the mirror
-  return ORE_OK;
-}
-
-// the per-descriptor flag words of the _ex sets (null: all zero): ORE_IMAGE_FLIP_H is the only bit
-static ore_status list_check_flags(ore_ctx* ctx, const uint32_t* flags, int64_t n) {
-  for (int64_t i = 0; flags && i < n; ++i)
-    if (flags[i] & ~uint32_t(ORE_IMAGE_FLIP_H))
-      return set_error(ctx, ORE_ERR_INVALID, "image %lld: unknown flag bits 0x%x (ORE_IMAGE_FLIP_H is the only one)", (long long)i,
-                       unsigned(flags[i] & ~uint32_t(ORE_IMAGE_FLIP_H)));
-  return ORE_OK;
-}
-
-ore_status ore_image_list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs, int64_t n) {
-  return ore_image_list_set_nv12_ex(l, imgs, nullptr, n);
-}
-
-static ore_status list_set_nv12(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, const uint8_t* orientations, int64_t n,
-                                bool oriented_entry) {
-  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
-  ore_ctx* ctx = l->ctx;
-  if (l->format == ORE_IMAGE_YUV)
-    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_nv12 on a YUV list: ore_image_list_set_yuv is its entry");
-  if (l->format != ORE_IMAGE_NV12)
-    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_nv12 on a list of interleaved images: ore_image_list_set is its entry");
-  int64_t bad = -1;
-  if (ore_image_check_nv12_oriented(imgs, n, l->h, l->w, l->filter, orientations, &bad)) {
-    ctx->err = ore_last_error(nullptr);
-    return ORE_ERR_INVALID;
-  }
-  if (ore_status st = list_check_flags(ctx, flags, n)) return st;
-  if (ore_status st = list_set_begin(l, n)) return st;
-  if (oriented_entry) l->oriented = true;  // for good: captures of the list record the orientation-reading kernels
-  if (n == 0) return ORE_OK;
-  bool any_flip = false, any_orient = false;
-  int taps = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const ore_image_nv12& d = imgs[i];
-    const int64_t hc = (d.hs + 1) / 2, wc = (d.ws + 1) / 2;
-    Nv12Image& r = l->mirror_nv12[i];
-    r = Nv12Image{};
-    r.y = d.y; r.uv = d.uv;
-    r.Hs = int(d.hs); r.Ws = int(d.ws);
-    r.yrow = int(d.hs > 1 && d.y_stride ? d.y_stride : d.ws);  // dense where 0, and where no row is ever stepped
-    r.uvrow = int(hc > 1 && d.uv_stride ? d.uv_stride : 2 * wc);
-    ore_resize g = d.g;  // an oriented descriptor carries the stored image's geometry and the permutation bits
-    int64_t hz, wz;
-    const int bits = orientations ? orient_stored(orientations[i], d.g, l->h, l->w, &g, &hz, &wz) : 0;
-    r.Rh = int(g.rh); r.Rw = int(g.rw); r.top = int(g.top); r.left = int(g.left);
-    r.flip = (flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0) | bits;
-    any_flip |= r.flip != 0;
-    any_orient |= bits != 0;
-    if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
-  }
-  ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_nv12, l->mirror_nv12, size_t(n) * sizeof(Nv12Image), hipMemcpyHostToDevice, ctx->stream));
-  ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
-  l->count = n;
-  l->any_flip = any_flip;
-  l->any_orient = any_orient;
-  l->taps = taps;
-  return ORE_OK;
-}
-
-ore_status ore_image_list_set_nv12_ex(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags, int64_t n) {
-  return list_set_nv12(l, imgs, flags, nullptr, n, false);
-}
-
-ore_status ore_image_list_set_nv12_oriented(ore_image_list* l, const ore_image_nv12* imgs, const uint32_t* flags,
-                                            const uint8_t* orientations, int64_t n) {
-  return list_set_nv12(l, imgs, flags, orientations, n, true);
-}
-
-static_assert(sizeof(ore_image_yuv) == 104, "ore_image_yuv is part of the ABI");
-static_assert(sizeof(YuvImage) == 80 && sizeof(YuvImage) % 8 == 0, "the pointers of a YuvImage table stay aligned");
-
-ore_status ore_image_list_set_yuv(ore_image_list* l, const ore_image_yuv* imgs, int64_t n) {
-  return ore_image_list_set_yuv_ex(l, imgs, nullptr, n);
-}
-
-static ore_status list_set_yuv(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags, const uint8_t* orientations, int64_t n,
-                               bool oriented_entry) {
-  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
-  ore_ctx* ctx = l->ctx;
-  if (l->format == ORE_IMAGE_NV12)
-    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_yuv on an NV12 list: ore_image_list_set_nv12 is its entry");
-  if (l->format != ORE_IMAGE_YUV)
-    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set_yuv on a list of interleaved images: ore_image_list_set is its entry");
-  int64_t bad = -1;
-  if (ore_image_check_yuv_oriented(imgs, n, l->h, l->w, l->filter, orientations, &bad)) {
-    ctx->err = ore_last_error(nullptr);
-    return ORE_ERR_INVALID;
-  }
-  if (ore_status st = list_check_flags(ctx, flags, n)) return st;
-  if (ore_status st = list_set_begin(l, n)) return st;
-  if (oriented_entry) l->oriented = true;  // for good: captures of the list record the orientation-reading kernels
-  if (n == 0) return ORE_OK;
-  bool any_flip = false, any_orient = false;
-  int taps = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const ore_image_yuv& d = imgs[i];
-    const YuvLayout& f = *yuv_layout(d.format);  // checked
-    int pitch[3] = {0, 0, 0};  // dense where 0, and where no row is ever stepped
-    for (int k = 0; k < f.planes; ++k)
-      pitch[k] = int(yuv_plane_rows(f, k, d.hs) > 1 && d.stride[k] ? d.stride[k] : yuv_plane_row_bytes(f, k, d.ws));
-    // the format ends here: the kernels see three strided planes
-    YuvImage& r = l->mirror_yuv[i];
-    r = YuvImage{};
-    r.y = d.plane[0];
-    r.yrow = pitch[0];
-    if (f.ystep == 2) {  // YUYV: U and V inside the luma plane's groups
-      r.u = d.plane[0] + 1; r.v = d.plane[0] + 3;
-      r.urow = r.vrow = pitch[0];
-    } else if (f.planes == 2) {  // NV12: V one byte after U
-      r.u = d.plane[1]; r.v = d.plane[1] + 1;
-      r.urow = r.vrow = pitch[1];
-    } else if (f.planes == 3) {
-      r.u = d.plane[1]; r.v = d.plane[2];
-      r.urow = pitch[1]; r.vrow = pitch[2];
-    }  // grey: no chroma, u and v stay null
-    r.Hs = int(d.hs); r.Ws = int(d.ws);
-    r.ystep = f.ystep; r.cstep = f.cstep;
-    r.sx = f.sx; r.sy = f.sy;
-    ore_resize g = d.g;  // an oriented descriptor carries the stored image's geometry and the permutation bits
-    int64_t hz, wz;
-    const int bits = orientations ? orient_stored(orientations[i], d.g, l->h, l->w, &g, &hz, &wz) : 0;
-    r.Rh = int(g.rh); r.Rw = int(g.rw); r.top = int(g.top); r.left = int(g.left);
-    r.flip = (flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0) | bits;
-    any_flip |= r.flip != 0;
-    any_orient |= bits != 0;
-    if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
-  }
-  ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table_yuv, l->mirror_yuv, size_t(n) * sizeof(YuvImage), hipMemcpyHostToDevice, ctx->stream));
-  ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
-  l->count = n;
-  l->any_flip = any_flip;
-  l->any_orient = any_orient;
-  l->taps = taps;
-  return ORE_OK;
-}
-
-ore_status ore_image_list_set_yuv_ex(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags, int64_t n) {
-  return list_set_yuv(l, imgs, flags, nullptr, n, false);
-}
-
-ore_status ore_image_list_set_yuv_oriented(ore_image_list* l, const ore_image_yuv* imgs, const uint32_t* flags,
-                                           const uint8_t* orientations, int64_t n) {
-  return list_set_yuv(l, imgs, flags, orientations, n, true);
-}
-
-ore_status ore_image_list_set(ore_image_list* l, const ore_image_u8* imgs, int64_t n) {
-  return ore_image_list_set_ex(l, imgs, nullptr, n);
-}
-
-static ore_status list_set_u8(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, const uint8_t* orientations, int64_t n,
-                              bool oriented_entry) {
-  if (!l) return set_error(nullptr, ORE_ERR_INVALID, "null image list");
-  ore_ctx* ctx = l->ctx;
-  if (l->format == ORE_IMAGE_YUV)
-    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set on a YUV list: ore_image_list_set_yuv is its entry");
-  if (l->format != ORE_IMAGE_INTERLEAVED)
-    return set_error(ctx, ORE_ERR_INVALID, "ore_image_list_set on an NV12 list: ore_image_list_set_nv12 is its entry");
-  int64_t bad = -1;
-  if (ore_image_check_oriented(imgs, n, l->c, l->h, l->w, l->filter, orientations, &bad)) {
-    ctx->err = ore_last_error(nullptr);
-    return ORE_ERR_INVALID;
-  }
-  if (ore_status st = list_check_flags(ctx, flags, n)) return st;
-  if (ore_status st = list_set_begin(l, n)) return st;
-  if (oriented_entry) l->oriented = true;  // for good: captures of the list record the orientation-reading kernels
-  if (n == 0) return ORE_OK;
-  bool any_flip = false, any_orient = false;
-  int taps = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const ore_image_u8& d = imgs[i];
-    ResizeImage& r = l->mirror[i];
-    r = ResizeImage{};
-    r.x = d.data;
-    r.Hs = int(d.hs); r.Ws = int(d.ws);
-    r.row = int(d.hs > 1 && d.row_stride ? d.row_stride : d.ws * l->c);  // dense where 0, and where no row is ever stepped
-    ore_resize g = d.g;  // an oriented descriptor carries the stored image's geometry and the permutation bits
-    int64_t hz, wz;
-    const int bits = orientations ? orient_stored(orientations[i], d.g, l->h, l->w, &g, &hz, &wz) : 0;
-    r.Rh = int(g.rh); r.Rw = int(g.rw); r.top = int(g.top); r.left = int(g.left);
-    r.flip = (flags ? int(flags[i] & ORE_IMAGE_FLIP_H) : 0) | bits;
-    any_flip |= r.flip != 0;
-    any_orient |= bits != 0;
-    if (l->filter == ORE_FILTER_BICUBIC_AA) taps = std::max(taps, resize_cubic_aa_max_taps(r.Ws, r.Rw));
-  }
-  // stream-ordered: launches submitted earlier read the old table, later ones the new
-  ORE_HIP_CHECK(ctx, hipMemcpyAsync(l->table, l->mirror, size_t(n) * sizeof(ResizeImage), hipMemcpyHostToDevice, ctx->stream));
-  ORE_HIP_CHECK(ctx, hipEventRecord(l->uploaded, ctx->stream));
-  l->count = n;
-  l->any_flip = any_flip;
-  l->any_orient = any_orient;
-  l->taps = taps;
-  return ORE_OK;
-}
-
-ore_status ore_image_list_set_ex(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags, int64_t n) {
-  return list_set_u8(l, imgs, flags, nullptr, n, false);
-}
-
-ore_status ore_image_list_set_oriented(ore_image_list* l, const ore_image_u8* imgs, const uint32_t* flags,
-                                       const uint8_t* orientations, int64_t n) {
-  return list_set_u8(l, imgs, flags, orientations, n, true);
-}
-
-ore_status ore_preprocess_list_u8(ore_ctx* ctx, ore_image_list* l, const float* scale, const float* shift, int32_t flags,
-                                  ore_tensor* y) {
-  // the arguments first and the context last, as ore_preprocess_resize_u8
-  if (!l || !y || !y->data) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (y->ndim != 4 || y->dims[0] != l->count || y->dims[1] != l->c || y->dims[2] != l->h || y->dims[3] != l->w)
-    return set_error(ctx, ORE_ERR_INVALID, "list output must be [count,c,H,W] of the image list (%lld x %lld x %lld x %lld)",
-                     (long long)l->count, (long long)l->c, (long long)l->h, (long long)l->w);
-  ResizeListParams p;
-  if (ore_status st = list_params(ctx, l, scale, shift, flags, &p)) return st;
-  if (nstride_of(y) < l->c * l->h * l->w)
-    return set_error(ctx, ORE_ERR_INVALID, "list output: image stride %lld below c*H*W", (long long)nstride_of(y));
-  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null context");
-  if (l->ctx != ctx) return set_error(ctx, ORE_ERR_INVALID, "the image list belongs to another context");
-  if (l->count == 0) return ORE_OK;
-  p.y = y->data;
-  p.y_nstride = nstride_of(y);
-  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  launch_list(ctx, l, p);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

@@ -16,6 +16,7 @@
 // strided planes every YUV format reduces to (both further down).
 #include <hip/hip_runtime.h>
 
+#include "../../include/ore.h"
 #include "ore_kernels.h"
 #include "ore_resize_geom.h"
 
@@ -1171,16 +1172,14 @@ void launch_resize_cubic_u8(const ResizeParams& p, bool aa, hipStream_t s) {
   aa ? cubic_u8<true>(p, s) : cubic_u8<false>(p, s);
 }
 
-// The list launches size the LDS by ResizeListParams::taps: the longest column run of the list's last set, or, where
-// a captured launch may meet the descriptors of a later set, the longest the ratio rule allows.
+// The list launches: the three kernel families (cubic_list, aa_list, plain_list) over the three descriptor formats,
+// then launch_resize_list's choice among them, written once.  The cubic ones size the LDS by p.taps: the longest column
+// run of the list's last set, or, where a captured launch may meet the descriptors of a later set, the longest the
+// ratio rule allows.
 
-void launch_resize_cubic_u8_list(const ResizeListParams& p, bool aa, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  aa ? cubic_u8_list<true>(p, s) : cubic_u8_list<false>(p, s);
-}
+static void cubic_list(const ResizeListParams& p, bool aa, hipStream_t s) { aa ? cubic_u8_list<true>(p, s) : cubic_u8_list<false>(p, s); }
 
-void launch_resize_cubic_nv12_list(const Nv12ListParams& p, bool aa, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void cubic_list(const Nv12ListParams& p, bool aa, hipStream_t s) {
   const Nv12Image* table = p.table + p.first;
   if (aa)
     cubic_launch<true>(ORE_LIST_KERNEL(p.flips, resize_cubic_nv12_list_kernel, true,), p.H, p.W, p.N, p.taps, p.flips, s, table, p);
@@ -1188,8 +1187,7 @@ void launch_resize_cubic_nv12_list(const Nv12ListParams& p, bool aa, hipStream_t
     cubic_launch<false>(ORE_LIST_KERNEL(p.flips, resize_cubic_nv12_list_kernel, false,), p.H, p.W, p.N, 0, p.flips, s, table, p);
 }
 
-void launch_resize_cubic_yuv_list(const YuvListParams& p, bool aa, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void cubic_list(const YuvListParams& p, bool aa, hipStream_t s) {
   const YuvImage* table = p.table + p.first;
   if (aa)
     cubic_launch<true>(ORE_LIST_KERNEL(p.flips, resize_cubic_yuv_list_kernel, true,), p.H, p.W, p.N, p.taps, p.flips, s, table, p);
@@ -1209,8 +1207,7 @@ void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s) {
   }
 }
 
-void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void aa_list(const ResizeListParams& p, hipStream_t s) {
   const ResizeImage* table = p.table + p.first;
   const dim3 grid = list_grid(p.H, p.W, p.N, RS_THREADS, p.flips);
   switch (p.C) {
@@ -1221,30 +1218,40 @@ void launch_resize_aa_u8_list(const ResizeListParams& p, hipStream_t s) {
   }
 }
 
-void launch_resize_nv12_list(const Nv12ListParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void plain_list(const Nv12ListParams& p, hipStream_t s) {
   aa_launch(ORE_LIST_KERNEL(p.flips, resize_nv12_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
-void launch_resize_aa_nv12_list(const Nv12ListParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void aa_list(const Nv12ListParams& p, hipStream_t s) {
   aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_nv12_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
-void launch_resize_yuv_list(const YuvListParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void plain_list(const YuvListParams& p, hipStream_t s) {
   aa_launch(ORE_LIST_KERNEL(p.flips, resize_yuv_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
-void launch_resize_aa_yuv_list(const YuvListParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void aa_list(const YuvListParams& p, hipStream_t s) {
   aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_yuv_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
 
-void launch_resize_u8_list(const ResizeListParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+static void plain_list(const ResizeListParams& p, hipStream_t s) {
   aa_launch(ORE_LIST_KERNEL(p.flips, resize_u8_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
 }
+
+template <class P>
+static void resize_list(const P& p, int32_t filter, hipStream_t s) {
+  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
+  if (filter & ORE_FILTER_CUBIC_BIT)
+    cubic_list(p, filter == ORE_FILTER_BICUBIC_AA, s);
+  else if (filter == ORE_FILTER_BILINEAR_AA)
+    aa_list(p, s);
+  else
+    plain_list(p, s);
+}
+
+void launch_resize_list(const ResizeListParams& p, int32_t filter, hipStream_t s) { resize_list(p, filter, s); }
+void launch_resize_list(const Nv12ListParams& p, int32_t filter, hipStream_t s) { resize_list(p, filter, s); }
+void launch_resize_list(const YuvListParams& p, int32_t filter, hipStream_t s) { resize_list(p, filter, s); }
 
 void launch_resize_u8(const ResizeParams& p, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;

@@ -512,7 +512,20 @@ class ImageList:
     makes it a list of the antialiased filter, cubic=True of the bicubic ones (see preprocess_resize_u8): properties
     of the list."""
 
+    antialias = False
+    cubic = False
+    # what a descriptor format has of its own: its set entries, its ctypes descriptor, what messages call its items,
+    # and _describe below
+    _SET, _SET_EX, _SET_ORIENTED = "ore_image_list_set", "ore_image_list_set_ex", "ore_image_list_set_oriented"
+    _DESC = _lib.ImageU8
+    _NOUN = "images"
+
     def __init__(self, ctx: Context, capacity: int, out_hw, channels: int = 3, antialias: bool = False, cubic: bool = False):
+        self._create(ctx, capacity, out_hw, channels, antialias, cubic, "ore_image_list_create_ex", lead=(int(channels),))
+
+    def _create(self, ctx, capacity, out_hw, channels, antialias, cubic, entry, lead=(), tail=()):
+        """The attributes every list has, and its handle from the format's create entry: entry(ctx, capacity, *lead,
+        h, w, filter, *tail, &handle)."""
         h, w = (int(v) for v in out_hw)
         self.ctx = ctx
         self.capacity = int(capacity)
@@ -523,59 +536,61 @@ class ImageList:
         self._images = ()
         self.h = None
         hnd = ctypes.c_void_p()
-        check(load().ore_image_list_create_ex(ctx.h, self.capacity, self.channels, h, w, _filter(antialias, cubic),
-                                              ctypes.byref(hnd)), ctx.h)
+        check(getattr(load(), entry)(ctx.h, self.capacity, *lead, h, w, _filter(antialias, cubic), *tail, ctypes.byref(hnd)), ctx.h)
         self.h = hnd
 
-    def _descriptors(self, images, geometries, short):
-        """The host checks of set(): the ore_image_u8 array of `images`, before any library call."""
+    def _describe(self, d, x, name):
+        """The format's own fields of descriptor d from item x of a set, after the item's host checks -> (hs, ws)."""
+        _check_image_u8(x, self.ctx.device, self.channels, name)
+        d.data = x.data_ptr()
+        d.row_stride = int(x.stride(0))
+        return int(x.shape[0]), int(x.shape[1])
+
+    def _descriptors(self, items, geometries, short, codes=None):
+        """The host checks of set() and set_oriented() (codes: its EXIF codes, one per item): the descriptor array of
+        `items`, before any library call."""
         if geometries is not None and short is not None:
             raise OreError(1, "set: pass geometries or short, not both")
-        images = list(images)
-        if len(images) > self.capacity:
-            raise OreError(1, f"set: {len(images)} images exceed the list's capacity {self.capacity}")
-        if geometries is not None and len(geometries) != len(images):
-            raise OreError(1, f"set: {len(geometries)} geometries for {len(images)} images")
-        arr = (_lib.ImageU8 * max(len(images), 1))()
-        for i, x in enumerate(images):
-            _check_image_u8(x, self.ctx.device, self.channels, f"images[{i}]")
-            hs, ws = int(x.shape[0]), int(x.shape[1])
-            arr[i].data = x.data_ptr()
+        items = list(items)
+        if len(items) > self.capacity:
+            raise OreError(1, f"set: {len(items)} {self._NOUN} exceed the list's capacity {self.capacity}")
+        if geometries is not None and len(geometries) != len(items):
+            raise OreError(1, f"set: {len(geometries)} geometries for {len(items)} {self._NOUN}")
+        arr = (self._DESC * max(len(items), 1))()
+        for i, x in enumerate(items):
+            name = f"{self._NOUN}[{i}]"
+            hs, ws = self._describe(arr[i], x, name)
             arr[i].hs, arr[i].ws = hs, ws
-            arr[i].row_stride = int(x.stride(0))
-            arr[i].g = self._geometry(i, hs, ws, geometries, short, f"images[{i}]")
-        return images, arr
+            arr[i].g = self._geometry(i, hs, ws, geometries, short, name, None if codes is None else codes[i])
+        return items, arr
 
-    def set(self, images, geometries=None, short=None, flips=None):
-        """ore_image_list_set: images is a sequence of uint8 CUDA tensors [Hs, Ws, C] (sliced views included:
-        that is where row strides come from).  Geometry per image: geometries[i] = (resized_hw, origin); or
-        short=S for center_crop_geometry(src_hw, S, out_hw); or neither, a plain resize to out_hw.  The upload
-        is ordered on the context's stream; a rejected set leaves the list as it was.  The list keeps
-        references to the tensors.  flips (ore_image_list_set_ex): one bool per image; a flipped image is its
-        unflipped output with the columns reversed, bit for bit -- the mirror of the window, not a resize of
-        the mirrored source."""
-        images, arr = self._descriptors(images, geometries, short)
-        if flips is None:
-            check(load().ore_image_list_set(self.h, arr, len(images)), self.ctx.h)
-        else:
-            words = _flip_words(flips, len(images))
-            check(load().ore_image_list_set_ex(self.h, arr, words, len(images)), self.ctx.h)
-        self._images = tuple(images)
-        return self
-
-    _SET_ORIENTED = "ore_image_list_set_oriented"
-    _codes = None  # the EXIF codes of the set_oriented call in progress: _descriptors sizes its geometries by them
-
-    def _geometry(self, i, hs, ws, geometries, short, name):
-        """The ore_resize of image i of a set: in displayed space, which under set_oriented is the oriented size."""
-        shown = (hs, ws) if self._codes is None else oriented_hw((hs, ws), self._codes[i])
+    def _geometry(self, i, hs, ws, geometries, short, name, code=None):
+        """The ore_resize of item i of a set: in displayed space, which under an orientation code is the oriented size."""
+        shown = (hs, ws) if code is None else oriented_hw((hs, ws), code)
         if geometries is not None:
             resized, origin = geometries[i]
         elif short is not None:
             resized, origin = center_crop_geometry(shown, short, self.out_hw)
         else:
             resized, origin = None, (0, 0)
-        return _resize_arg(shown, self.out_hw, resized, origin, getattr(self, "antialias", False), name, getattr(self, "cubic", False))
+        return _resize_arg(shown, self.out_hw, resized, origin, self.antialias, name, self.cubic)
+
+    def set(self, images, geometries=None, short=None, flips=None):
+        """ore_image_list_set: images is a sequence of uint8 CUDA tensors [Hs, Ws, C] (sliced views included:
+        that is where row strides come from); the frame lists take frames as their classes say.  Geometry per image:
+        geometries[i] = (resized_hw, origin); or short=S for center_crop_geometry(src_hw, S, out_hw); or neither, a
+        plain resize to out_hw.  The upload is ordered on the context's stream; a rejected set leaves the list as it
+        was.  The list keeps references to the tensors.  flips (ore_image_list_set_ex, _set_nv12_ex, _set_yuv_ex):
+        one bool per image; a flipped image is its unflipped output with the columns reversed, bit for bit -- the
+        mirror of the window, not a resize of the mirrored source."""
+        images, arr = self._descriptors(images, geometries, short)
+        if flips is None:
+            check(getattr(load(), self._SET)(self.h, arr, len(images)), self.ctx.h)
+        else:
+            words = _flip_words(flips, len(images))
+            check(getattr(load(), self._SET_EX)(self.h, arr, words, len(images)), self.ctx.h)
+        self._images = tuple(images)
+        return self
 
     def set_oriented(self, images, orientations, geometries=None, short=None, flips=None):
         """set() with one EXIF orientation code 1..8 per image (the _set_oriented entries; rotation_orientation maps a
@@ -586,11 +601,7 @@ class ImageList:
         The first call marks the list (include/ore.h: captures of a marked list serve later orientations)."""
         images = list(images)
         codes = _orient_bytes(orientations, len(images))
-        self._codes = list(codes)[:len(images)]
-        try:
-            images, arr = self._descriptors(images, geometries, short)
-        finally:
-            self._codes = None
+        images, arr = self._descriptors(images, geometries, short, list(codes)[:len(images)])
         words = None if flips is None else _flip_words(flips, len(images))
         check(getattr(load(), self._SET_ORIENTED)(self.h, arr, words, codes, len(images)), self.ctx.h)
         self._images = tuple(images)
@@ -695,57 +706,26 @@ class Nv12ImageList(ImageList):
     half-resolution plane of (U, V) pairs, each with its own pitch -- resized, cropped and normalised in ONE launch
     with the colour conversion inside it.  Image i is bit for bit image i of an ImageList fed nv12_to_rgb of the
     frame.  Three channels (R, G, B); the matrix ("bt601", "bt709", "bt601_full") and the filter are properties of
-    the list.  Model.run_u8_list, classify_u8_list and the captures take it as they take an ImageList."""
+    the list.  Model.run_u8_list, classify_u8_list and the captures take it as they take an ImageList.
+
+    set() (ore_image_list_set_nv12) takes a sequence of (y, uv) pairs of uint8 CUDA tensors, y [Hs, Ws] and uv
+    [ceil(Hs/2), ceil(Ws/2), 2], views included: the pitches are the tensors' row strides.  A window of a
+    larger frame must start at an even row and column (y[y0:, x0:] with uv[y0 // 2:, x0 // 2:]).  Geometry,
+    flips (ore_image_list_set_nv12_ex), ordering and what a rejected set leaves behind are ImageList.set's."""
+
+    _SET, _SET_EX, _SET_ORIENTED = "ore_image_list_set_nv12", "ore_image_list_set_nv12_ex", "ore_image_list_set_nv12_oriented"
+    _DESC = _lib.ImageNv12
+    _NOUN = "frames"
 
     def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601", antialias: bool = False, cubic: bool = False):
-        h, w = (int(v) for v in out_hw)
-        self.ctx = ctx
-        self.capacity = int(capacity)
-        self.out_hw = (h, w)
-        self.channels = 3
-        self.antialias = bool(antialias)
-        self.cubic = bool(cubic)
         self.matrix = _yuv_matrix(matrix)
-        self._images = ()
-        self.h = None
-        hnd = ctypes.c_void_p()
-        check(load().ore_image_list_create_nv12(ctx.h, self.capacity, h, w, _filter(antialias, cubic), self.matrix,
-                                                ctypes.byref(hnd)), ctx.h)
-        self.h = hnd
+        self._create(ctx, capacity, out_hw, 3, antialias, cubic, "ore_image_list_create_nv12", tail=(self.matrix,))
 
-    _SET_ORIENTED = "ore_image_list_set_nv12_oriented"
-
-    def _descriptors(self, frames, geometries, short):
-        """The host checks of set(): the ore_image_nv12 array of `frames`, before any library call."""
-        if geometries is not None and short is not None:
-            raise OreError(1, "set: pass geometries or short, not both")
-        frames = list(frames)
-        if len(frames) > self.capacity:
-            raise OreError(1, f"set: {len(frames)} frames exceed the list's capacity {self.capacity}")
-        if geometries is not None and len(geometries) != len(frames):
-            raise OreError(1, f"set: {len(geometries)} geometries for {len(frames)} frames")
-        arr = (_lib.ImageNv12 * max(len(frames), 1))()
-        for i, f in enumerate(frames):
-            y, uv, hs, ws = _check_frame_nv12(f, self.ctx.device, f"frames[{i}]")
-            arr[i].y, arr[i].uv = y.data_ptr(), uv.data_ptr()
-            arr[i].hs, arr[i].ws = hs, ws
-            arr[i].y_stride, arr[i].uv_stride = int(y.stride(0)), int(uv.stride(0))
-            arr[i].g = self._geometry(i, hs, ws, geometries, short, f"frames[{i}]")
-        return frames, arr
-
-    def set(self, frames, geometries=None, short=None, flips=None):
-        """ore_image_list_set_nv12: frames is a sequence of (y, uv) pairs of uint8 CUDA tensors, y [Hs, Ws] and uv
-        [ceil(Hs/2), ceil(Ws/2), 2], views included: the pitches are the tensors' row strides.  A window of a
-        larger frame must start at an even row and column (y[y0:, x0:] with uv[y0 // 2:, x0 // 2:]).  Geometry,
-        flips (ore_image_list_set_nv12_ex), ordering and what a rejected set leaves behind are ImageList.set's."""
-        frames, arr = self._descriptors(frames, geometries, short)
-        if flips is None:
-            check(load().ore_image_list_set_nv12(self.h, arr, len(frames)), self.ctx.h)
-        else:
-            words = _flip_words(flips, len(frames))
-            check(load().ore_image_list_set_nv12_ex(self.h, arr, words, len(frames)), self.ctx.h)
-        self._images = tuple(frames)
-        return self
+    def _describe(self, d, frame, name):
+        y, uv, hs, ws = _check_frame_nv12(frame, self.ctx.device, name)
+        d.y, d.uv = y.data_ptr(), uv.data_ptr()
+        d.y_stride, d.uv_stride = int(y.stride(0)), int(uv.stride(0))
+        return hs, ws
 
 
 # ore_yuv_format name -> (planes in use, sx, sy): the chroma shifts of include/ore.h
@@ -855,65 +835,34 @@ class YuvImageList(ImageList):
     resized, cropped and normalised in ONE launch with the colour conversion inside it.  Image i is bit for bit
     image i of an ImageList fed yuv_planes_to_rgb of the frame.  Three channels (R, G, B); the matrix (a JPEG's is
     "bt601_full") and the filter are properties of the list, the layout is each frame's own.  Model.run_u8_list,
-    classify_u8_list, the captures and set_views take it as they take an ImageList."""
+    classify_u8_list, the captures and set_views take it as they take an ImageList.
+
+    set() (ore_image_list_set_yuv) takes a sequence of (fmt, plane, ...) with fmt one of "nv12" "yuyv" "i444"
+    "i440" "i422" "i420" "i411" "gray" and the planes uint8 CUDA tensors, views included (the pitches are the
+    tensors' row strides):
+        i4xx   y [Hs, Ws], u and v [ceil(Hs / 2^sy), ceil(Ws / 2^sx)]
+        nv12   y [Hs, Ws], uv [ceil(Hs/2), ceil(Ws/2), 2]
+        yuyv   one plane [Hs, ceil(Ws/2), 4] of Y0 U Y1 V groups; the width is twice the groups, or one less
+               when given: ("yuyv", plane, ws)
+        gray   y [Hs, Ws]
+    A window of a larger frame must start at a row and column that are multiples of (2^sy, 2^sx).  Geometry,
+    flips (ore_image_list_set_yuv_ex), ordering and what a rejected set leaves behind are ImageList.set's."""
+
+    _SET, _SET_EX, _SET_ORIENTED = "ore_image_list_set_yuv", "ore_image_list_set_yuv_ex", "ore_image_list_set_yuv_oriented"
+    _DESC = _lib.ImageYuv
+    _NOUN = "frames"
 
     def __init__(self, ctx: Context, capacity: int, out_hw, matrix="bt601_full", antialias: bool = False, cubic: bool = False):
-        h, w = (int(v) for v in out_hw)
-        self.ctx = ctx
-        self.capacity = int(capacity)
-        self.out_hw = (h, w)
-        self.channels = 3
-        self.antialias = bool(antialias)
-        self.cubic = bool(cubic)
         self.matrix = _yuv_matrix(matrix)
-        self._images = ()
-        self.h = None
-        hnd = ctypes.c_void_p()
-        check(load().ore_image_list_create_yuv(ctx.h, self.capacity, h, w, _filter(antialias, cubic), self.matrix,
-                                               ctypes.byref(hnd)), ctx.h)
-        self.h = hnd
+        self._create(ctx, capacity, out_hw, 3, antialias, cubic, "ore_image_list_create_yuv", tail=(self.matrix,))
 
-    _SET_ORIENTED = "ore_image_list_set_yuv_oriented"
-
-    def _descriptors(self, frames, geometries, short):
-        """The host checks of set(): the ore_image_yuv array of `frames`, before any library call."""
-        if geometries is not None and short is not None:
-            raise OreError(1, "set: pass geometries or short, not both")
-        frames = list(frames)
-        if len(frames) > self.capacity:
-            raise OreError(1, f"set: {len(frames)} frames exceed the list's capacity {self.capacity}")
-        if geometries is not None and len(geometries) != len(frames):
-            raise OreError(1, f"set: {len(geometries)} geometries for {len(frames)} frames")
-        arr = (_lib.ImageYuv * max(len(frames), 1))()
-        for i, f in enumerate(frames):
-            fmt, planes, hs, ws = _check_frame_yuv(f, self.ctx.device, f"frames[{i}]")
-            for k, p in enumerate(planes):
-                arr[i].plane[k] = p.data_ptr()
-                arr[i].stride[k] = int(p.stride(0))
-            arr[i].hs, arr[i].ws = hs, ws
-            arr[i].format = fmt
-            arr[i].g = self._geometry(i, hs, ws, geometries, short, f"frames[{i}]")
-        return frames, arr
-
-    def set(self, frames, geometries=None, short=None, flips=None):
-        """ore_image_list_set_yuv: frames is a sequence of (fmt, plane, ...) with fmt one of "nv12" "yuyv" "i444"
-        "i440" "i422" "i420" "i411" "gray" and the planes uint8 CUDA tensors, views included (the pitches are the
-        tensors' row strides):
-            i4xx   y [Hs, Ws], u and v [ceil(Hs / 2^sy), ceil(Ws / 2^sx)]
-            nv12   y [Hs, Ws], uv [ceil(Hs/2), ceil(Ws/2), 2]
-            yuyv   one plane [Hs, ceil(Ws/2), 4] of Y0 U Y1 V groups; the width is twice the groups, or one less
-                   when given: ("yuyv", plane, ws)
-            gray   y [Hs, Ws]
-        A window of a larger frame must start at a row and column that are multiples of (2^sy, 2^sx).  Geometry,
-        flips (ore_image_list_set_yuv_ex), ordering and what a rejected set leaves behind are ImageList.set's."""
-        frames, arr = self._descriptors(frames, geometries, short)
-        if flips is None:
-            check(load().ore_image_list_set_yuv(self.h, arr, len(frames)), self.ctx.h)
-        else:
-            words = _flip_words(flips, len(frames))
-            check(load().ore_image_list_set_yuv_ex(self.h, arr, words, len(frames)), self.ctx.h)
-        self._images = tuple(frames)
-        return self
+    def _describe(self, d, frame, name):
+        fmt, planes, hs, ws = _check_frame_yuv(frame, self.ctx.device, name)
+        for k, p in enumerate(planes):
+            d.plane[k] = p.data_ptr()
+            d.stride[k] = int(p.stride(0))
+        d.format = fmt
+        return hs, ws
 
 
 def preprocess_list_u8(ctx: Context, lst: ImageList, scale=None, shift=None, reverse_channels: bool = False):

@@ -171,7 +171,8 @@ def test_set_oriented_argument_errors_come_before_the_library():
         names = list(inspect.signature(cls.set_oriented).parameters)
         assert names[1:] == [names[1], "orientations", "geometries", "short", "flips"]
         assert all(inspect.signature(cls.set_oriented).parameters[k].default is None for k in names[3:])
-        assert list(inspect.signature(cls._descriptors).parameters)[2:] == ["geometries", "short"]  # unchanged
+        assert list(inspect.signature(cls._descriptors).parameters)[2:] == ["geometries", "short", "codes"]
+        assert inspect.signature(cls._descriptors).parameters["codes"].default is None  # positional callers unchanged
         lst = _host_list(cls)
         with pytest.raises(ore.OreError, match="2 orientations for 0 images"):
             lst.set_oriented([], [6, 6])
@@ -186,8 +187,8 @@ def test_set_oriented_argument_errors_come_before_the_library():
             lst.set_oriented([], [], flips=[True])
         with pytest.raises(ore.OreError, match="exceed the list's capacity"):
             lst.set_oriented([None] * 5, [1] * 5)
-        assert lst._images == () and lst._codes is None  # nothing was kept
+        assert lst._images == () and not hasattr(lst, "_codes")  # nothing was kept: the codes travel as an argument
     lst = _host_list()
     with pytest.raises(ore.OreError, match="uint8 CUDA"):  # the images' own checks still run
         lst.set_oriented([torch.zeros((4, 4, 3), dtype=torch.uint8)], [6])
-    assert lst._codes is None
+    assert not hasattr(lst, "_codes") and set(vars(lst)) == {"ctx", "capacity", "channels", "out_hw", "h", "_images"}

@@ -103,7 +103,8 @@ def test_image_list_python_layer_host():
     import inspect
     for cls in (ore.ImageList, ore.Nv12ImageList):
         names = list(inspect.signature(cls._descriptors).parameters)
-        assert len(names) == 4 and names[2:] == ["geometries", "short"]
+        assert len(names) == 5 and names[2:] == ["geometries", "short", "codes"]  # codes: set_oriented's, optional
+        assert inspect.signature(cls._descriptors).parameters["codes"].default is None
         assert list(inspect.signature(cls.set).parameters)[2:] == ["geometries", "short", "flips"]
         assert inspect.signature(cls.set).parameters["flips"].default is None
         lst = _host_list(cls)
