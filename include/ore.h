@@ -840,6 +840,39 @@ ore_status ore_model_graph_capture_classify_u8_list(ore_model* m, ore_image_list
  * / V there are ceil(G / gb) chunks of ceil(G / nchunks) groups each, chunk c writing rows [g0, g0 + gc) -- at
  * V == 1 the arithmetic of ore_model_run.  Buffers, timing events and the step list are unchanged. */
 ore_status ore_model_set_views(ore_model* m, int32_t views);
+/* Class activation maps of the selected classes (extension; ore_cam.hip).  A model "has a map
+ * conv" when, walking back from graph.output[0] through an optional Softmax and any Dropout / Reshape, it meets a
+ * GlobalAveragePool fed by an optional Relu and then a Conv with a 1x1 kernel, stride 1, zero pads and M = the
+ * model's output elems.  The pool's input T [n, M, Hm, Wm] is, class by class, the class activation map (Zhou et
+ * al. 2016).  With classes c[g, j] as the classify entries return them (group g = image i / views):
+ *     maps[i, j, r, q] = T[i, c[i / views, j], r, q]      float32, contiguous [n, k, Hm, Wm]
+ * with the bits of T as the model's unfused plan stores it: f32 models the conv kernels' k-ordered f32 fma
+ * chain, + bias, Relu; f16 models RNE_f16(relu?(sum_k f16(x_k) f16(w_k) [f32 accumulate] + b)) widened exactly.
+ * Non-finite values follow the Conv and Relu rules above.  The maps do not depend on the fusion flags, the streams
+ * setting or the tiles: one launch per chunk gathers the k weight rows and recomputes them from the conv's input.
+ *  ore_class_maps_f32: the kernel alone, on f32 NCHW x [n, C, H, W] (x->nstride honoured, any 4-byte aligned
+ *    base), DEVICE weights w [M, C] row-major, DEVICE bias [M] or NULL, DEVICE classes [n / views, k] int32, into
+ *    DEVICE maps [n, k, H, W].  Checked from the arguments alone, before the context and any device call
+ *    (ORE_ERR_INVALID): null pointers, x not 4-D, k outside 1..min(M, 64), views outside 1..ORE_MAX_VIEWS, n not a
+ *    multiple of views, the nstride rule at the top of this file.  n == 0 is ORE_OK and launches nothing.  A class
+ *    id outside 0..M-1 cannot be checked on the host: the kernel clamps the row index, so it never reads outside w,
+ *    and that slot's content is unspecified.  Nothing outside [n, k, H, W] is written.
+ *  ore_model_cam_dims: Hm, Wm; ORE_ERR_UNSUPPORTED with a message naming what was found when the model has no
+ *    map conv (MNIST-8).
+ *  ore_model_set_cam: while d_maps (DEVICE, cap_elems floats) is set, every classify entry -- ore_model_classify,
+ *    _classify_u8, _classify_u8_list and the three _graph_capture_classify* -- launches the map kernel behind each
+ *    chunk's top-k launch, images [i0, i0 + nc) with the class rows from i0 / views, after the pass's last timing
+ *    event (it is not an exec step); ore_model_run* ignore the setting.  A call with n * topk * Hm * Wm > cap_elems
+ *    is ORE_ERR_INVALID before any device call.  NULL turns it off (the default).  Turning it on or off replans
+ *    (the conv's input stays live to the end of the pass, as the output value does): ORE_ERR_INVALID while the
+ *    stream is capturing; re-capture afterwards, as after ore_model_set_fusion; autotuned tiles survive.  Changing
+ *    only the pointer or the capacity does not replan.  Off, the plan, the arena and the launches are those of a
+ *    model that never had it on.  A captured graph keeps the buffer and setting it was captured with.
+ *    ore_model_read_value of the conv's input works after a run with the maps on. */
+ore_status ore_class_maps_f32(ore_ctx* ctx, const ore_tensor* x, const float* w, const float* bias, int64_t M, int32_t relu,
+                              const int32_t* classes, int32_t k, int32_t views, float* maps);
+ore_status ore_model_cam_dims(ore_model* m, int64_t hw[2]);
+ore_status ore_model_set_cam(ore_model* m, float* d_maps, int64_t cap_elems);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);
 int32_t ore_model_step_count(ore_model* m);
 ore_status ore_model_step_info(ore_model* m, int32_t i, const char** op, const char** name, double* flops,

@@ -570,5 +570,23 @@ void launch_topk(const float* x, long long stride, long long rows, int D, int k,
 // ascending row order, one IEEE division by V); values / indices are contiguous [groups][k].  V == 1 is launch_topk.
 void launch_topk_mean(const float* x, long long stride, long long groups, int V, int D, int k, float* values,
                       int* indices, hipStream_t s);
+// class activation maps of the selected classes (ore_cam.hip): the rows classes[i / views][0 .. k) of a 1x1 conv
+// (row-major f32 weights [M][C], + bias, + Relu) over image i's C x P activations, as float32 [N][k][P] with the
+// bits the model's conv kernels store -- class_maps_f32_kernel over f32 NCHW planes (x_ps: plane stride),
+// class_maps_f16_kernel over f16 NHWC pixels (x_ps: pixel stride in halves; the result rounded to f16 and widened).
+// A class id outside 0 .. M - 1 is clamped into w.
+struct ClassMaps {
+  const void* x;        // image i at x + i * x_nstride elements (floats / halves)
+  const float* w;       // [M][C]
+  const float* bias;    // [M] or null
+  const int* classes;   // [N / views][k]
+  float* maps;          // [N][k][P], contiguous
+  long long x_nstride;
+  int N, C, P, M, k, views, relu;
+  int x_ps;
+};
+bool class_maps_eligible(const ClassMaps& p);
+void launch_class_maps_f32(const ClassMaps& p, hipStream_t s);
+void launch_class_maps_f16(const ClassMaps& p, hipStream_t s);
 
 }  // namespace ore

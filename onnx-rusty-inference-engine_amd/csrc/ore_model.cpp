@@ -588,6 +588,57 @@ void set_tile(ore_model* m, int k, int t) {
   else b.plan.cfg = t;
 }
 
+// The map conv of ore_model_set_cam (include/ore.h), over the unfused node steps: back from the graph output
+// through an optional Softmax and any Dropout / Reshape to a GlobalAveragePool, whose input T comes through an
+// optional Relu from a 1x1 / stride-1 / unpadded Conv of M = the output's elems.  Sets cam_conv, cam_in, cam_map and
+// cam_relu, or leaves cam_conv < 0 and says in cam_why what it met instead.
+void find_map_conv(ore_model* m) {
+  std::vector<int> producer(m->values.size(), -1);
+  for (size_t i = 0; i < m->base_steps.size(); ++i)
+    if (m->base_steps[i].out >= 0) producer[m->base_steps[i].out] = int(i);
+  auto found = [&](int v, const char* want) {
+    const int p = v >= 0 ? producer[v] : -1;
+    m->cam_why = std::string("no map conv: expected ") + want + ", found " +
+                 (p < 0 ? "the value '" + m->values[v].name + "' that no node produces"
+                        : m->base_steps[p].op + " '" + m->base_steps[p].name + "'");
+  };
+  int v = m->output_value, p = producer[v];
+  bool softmax = false;
+  while (p >= 0 && (m->base_steps[p].kind == S_COPY || (m->base_steps[p].kind == S_SOFTMAX && !softmax))) {
+    softmax = softmax || m->base_steps[p].kind == S_SOFTMAX;
+    v = m->base_steps[p].in0;
+    p = producer[v];
+  }
+  if (p < 0 || m->base_steps[p].kind != S_GAP) return found(v, "GlobalAveragePool");
+  const int T = m->base_steps[p].in0;
+  v = T;
+  p = producer[v];
+  bool relu = false;
+  if (p >= 0 && m->base_steps[p].kind == S_RELU) {
+    relu = true;
+    v = m->base_steps[p].in0;
+    p = producer[v];
+  }
+  if (p < 0 || m->base_steps[p].kind != S_CONV) return found(v, "a 1x1 Conv feeding the GlobalAveragePool");
+  const Step& s = m->base_steps[p];
+  const int64_t out_elems = m->values[m->output_value].per_image();
+  if (s.kh != 1 || s.kw != 1 || s.sh != 1 || s.sw != 1 || s.win.pt || s.win.pl || s.win.pb || s.win.pr || s.M != out_elems) {
+    m->cam_why = "no map conv: Conv '" + s.name + "' feeding the GlobalAveragePool has a " + std::to_string(s.kh) + "x" +
+                 std::to_string(s.kw) + " kernel, stride " + std::to_string(s.sh) + "x" + std::to_string(s.sw) + ", pads " +
+                 std::to_string(s.win.pt + s.win.pl + s.win.pb + s.win.pr) + " and " + std::to_string(s.M) +
+                 " channels (expected 1x1, stride 1, zero pads, " + std::to_string(out_elems) + " channels)";
+    return;
+  }
+  if (m->values[s.in0].es != (m->f16 ? 2 : 4) || m->values[s.in0].ndim != 4) {
+    m->cam_why = "no map conv: the input of Conv '" + s.name + "' is not stored in the model's precision";
+    return;
+  }
+  m->cam_conv = p;
+  m->cam_in = s.in0;
+  m->cam_map = T;
+  m->cam_relu = relu;
+}
+
 }  // namespace
 
 // the band walkers' geometry for a fused first conv + pool + squeeze step (their layout checks are the
@@ -757,6 +808,7 @@ ore_status ore_model_load_ex(ore_ctx* ctx, const void* bytes, size_t len, int64_
   if (m->values[m->output_value].es != 4)
     return fail(set_error(ctx, ORE_ERR_UNSUPPORTED, "f16 model: graph output '%s' must be f32 (end with GlobalAveragePool / Softmax)",
                           g.outputs[0].name.c_str()));
+  find_map_conv(m);
   if (ore_status st = plan(m)) { std::string e = ctx->err; ore_model_destroy(m); return set_error(ctx, st, "%s", e.c_str()); }
   *out = m;
   return ORE_OK;
@@ -950,11 +1002,44 @@ static ore_status check_views(ore_model* m, int64_t n) {
   return ORE_OK;
 }
 
-// the classify entries' checks: check_run_args with two outputs, and whole groups of views
+// the classify entries' rule under ore_model_set_cam: the maps of n images fit the caller's buffer
+static ore_status check_cam(ore_model* m, int64_t n) {
+  if (!m->cam_buf) return ORE_OK;
+  const Value& T = m->values[m->cam_map];
+  const int64_t need = n * m->topk * T.dims[2] * T.dims[3];
+  if (need > m->cam_cap)
+    return set_error(m->ctx, ORE_ERR_INVALID, "the class maps of %lld images at k = %d (%lld x %lld) need %lld floats, the buffer of "
+                     "ore_model_set_cam holds %lld", (long long)n, int(m->topk), (long long)T.dims[2], (long long)T.dims[3],
+                     (long long)need, (long long)m->cam_cap);
+  return ORE_OK;
+}
+
+// the classify entries' checks: check_run_args with two outputs, whole groups of views, and room for the class maps
 static ore_status check_classify_args(ore_model* m, const void* d_input, int64_t n, float* d_scores, int32_t* d_classes) {
   if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
   if (ore_status st = check_run_args(m, d_input, n, d_scores)) return st;
-  return check_views(m, n);
+  if (ore_status st = check_views(m, n)) return st;
+  return check_cam(m, n);
+}
+
+// The class maps of a chunk (ore_model_set_cam): images [i0, i0 + nc) of the run, whose map conv input the pass
+// just left in place (pinned by the plan), under the classes the chunk's top-k launch wrote for groups i0 / views ...
+static ore_status launch_cam(ore_model* m, int64_t i0, int64_t nc, int64_t views, const int32_t* d_classes) {
+  ore_ctx* ctx = m->ctx;
+  const Step& cv = m->base_steps[m->cam_conv];
+  const Value& T = m->values[m->cam_map];
+  const Ref x = ref_of(m, m->cam_in);
+  const int64_t P = T.dims[2] * T.dims[3];
+  if (!x.p || x.es != (m->f16 ? 2 : 4)) return err(m, ORE_ERR_INVALID, "internal: the map conv's input is not materialised");
+  const ClassMaps p{x.p, m->values[cv.in1].cptr, cv.in2 >= 0 ? m->values[cv.in2].cptr : nullptr,
+                    d_classes + (i0 / views) * m->topk, m->cam_buf + i0 * m->topk * P, x.nstride, int(nc), int(cv.C), int(P),
+                    int(cv.M), int(m->topk), int(views), m->cam_relu ? 1 : 0,
+                    int(m->f16 ? pixel_stride(x, cv.C) : plane_stride(x, P))};
+  if (!class_maps_eligible(p)) return err(m, ORE_ERR_INVALID, "internal: class maps on an unsupported layout");
+  if (m->f16) launch_class_maps_f16(p, ctx->stream);
+  else launch_class_maps_f32(p, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
 }
 
 // ore_model_run, ore_model_run_u8 and the classify entries: the graph over n images, in chunks of at most
@@ -1047,6 +1132,8 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
       launch_topk_mean(r.p, r.nstride, nc / views, int(views), int(out_img), m->topk, d_output + g0 * m->topk,
                        d_classes + g0 * m->topk, ctx->stream);
       ORE_HIP_CHECK(ctx, hipGetLastError());
+      if (m->cam_buf)  // the maps of the classes just selected, from the map conv's input the pass left in place
+        if (ore_status st = launch_cam(m, i0, nc, views, d_classes)) return st;
     }
   }
   return ORE_OK;
@@ -1123,6 +1210,44 @@ ore_status ore_model_set_views(ore_model* m, int32_t views) {
   return ORE_OK;
 }
 
+ore_status ore_model_cam_dims(ore_model* m, int64_t hw[2]) {
+  if (!m || !hw) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+  if (m->cam_conv < 0) return set_error(m->ctx, ORE_ERR_UNSUPPORTED, "%s", m->cam_why.c_str());
+  hw[0] = m->values[m->cam_map].dims[2];
+  hw[1] = m->values[m->cam_map].dims[3];
+  return ORE_OK;
+}
+
+ore_status ore_model_set_cam(ore_model* m, float* d_maps, int64_t cap_elems) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  ore_ctx* ctx = m->ctx;
+  if (d_maps && m->cam_conv < 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "%s", m->cam_why.c_str());
+  if (d_maps && cap_elems < 0) return set_error(ctx, ORE_ERR_INVALID, "class map buffer of %lld floats", (long long)cap_elems);
+  if ((d_maps != nullptr) != (m->cam_buf != nullptr)) {  // on <-> off: the plan pins (or releases) the conv's input
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return set_error(ctx, ORE_ERR_INVALID, "ore_model_set_cam inside a stream capture (it replans the model)");
+    // the arena is sized anew, so that turning the maps off gives back exactly the arena of a model without them
+    // (plan() alone only ever grows it)
+    ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ORE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (m->arena_alloc) (void)hipFree(m->arena_alloc);
+    m->arena = m->arena_alloc = nullptr;
+    m->arena_bytes = 0;
+    float* const old_buf = m->cam_buf;
+    m->cam_buf = d_maps;
+    if (ore_status st = plan(m)) {  // back to the plan that stood
+      const std::string e = ctx->err;
+      m->cam_buf = old_buf;
+      (void)plan(m);
+      return set_error(ctx, st, "%s", e.c_str());
+    }
+  }
+  m->cam_buf = d_maps;
+  m->cam_cap = d_maps ? cap_elems : 0;
+  return ORE_OK;
+}
+
 ore_status ore_model_classify(ore_model* m, const float* d_input, int64_t n, float* d_scores, int32_t* d_classes) {
   if (ore_status st = check_classify_args(m, d_input, n, d_scores, d_classes)) return st;
   if (n == 0) return ORE_OK;
@@ -1160,6 +1285,7 @@ ore_status ore_model_classify_u8_list(ore_model* m, ore_image_list* l, float* d_
   if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
   if (ore_status st = check_list_args(m, l, d_scores)) return st;
   if (ore_status st = check_views(m, l->count)) return st;
+  if (ore_status st = check_cam(m, l->count)) return st;
   if (l->count == 0) return ORE_OK;
   if (ore_status st = ensure_stage(m)) return st;
   if (ore_status st = ensure_rows(m)) return st;
@@ -1404,6 +1530,7 @@ ore_status ore_model_graph_capture_classify_u8_list(ore_model* m, ore_image_list
   if (!d_classes) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
   if (ore_status st = check_list_args(m, l, d_scores)) return st;
   if (ore_status st = check_views(m, l->count)) return st;
+  if (ore_status st = check_cam(m, l->count)) return st;
   return capture_run(m, nullptr, nullptr, l->count, d_scores, d_classes, l);
 }
 

@@ -197,6 +197,15 @@ struct ore_model {
   size_t rows_bytes = 0;
   int32_t topk = 1;
   int32_t views = 1;  // ore_model_set_views: the classify entries select over the mean of this many consecutive rows
+  // class activation maps (ore_model_set_cam): the map conv found at load (find_map_conv; cam_conv < 0: none, cam_why
+  // says what was found instead), and the caller's buffer the classify entries fill behind each chunk's top-k launch
+  int cam_conv = -1;             // base step index of the 1x1 conv in front of [Relu ->] GlobalAveragePool
+  int cam_in = -1;               // its input value: with the maps on, never elided and live to the end of the pass
+  int cam_map = -1;              // the pool's input value T (its dims are the map's)
+  bool cam_relu = false;         // a Relu between the conv and the pool
+  std::string cam_why;
+  float* cam_buf = nullptr;      // DEVICE [n, topk, Hm, Wm]; null: off
+  int64_t cam_cap = 0;           // its capacity in floats
 };
 
 namespace ore {

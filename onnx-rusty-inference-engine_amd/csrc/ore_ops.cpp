@@ -884,6 +884,35 @@ ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, i
   return ORE_OK;
 }
 
+ore_status ore_class_maps_f32(ore_ctx* ctx, const ore_tensor* x, const float* w, const float* bias, int64_t M, int32_t relu,
+                              const int32_t* classes, int32_t k, int32_t views, float* maps) {
+  // the context last, as ore_topk_mean_f32: what can be judged without one is
+  if (!x || !x->data || !w || !classes || !maps) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (x->ndim != 4) return set_error(ctx, ORE_ERR_INVALID, "class maps: x of %d dims, expected [n, C, H, W]", int(x->ndim));
+  const int64_t n = x->dims[0], C = x->dims[1], P = x->dims[2] * x->dims[3];
+  if (n < 0 || C <= 0 || x->dims[2] <= 0 || x->dims[3] <= 0 || M <= 0 || !fits_i32(C) || !fits_i32(P) || !fits_i32(M))
+    return set_error(ctx, ORE_ERR_INVALID, "class maps: x [%lld, %lld, %lld, %lld] and M = %lld", (long long)n, (long long)C,
+                     (long long)x->dims[2], (long long)x->dims[3], (long long)M);
+  if (k < 1 || k > std::min<int64_t>(M, 64))
+    return set_error(ctx, ORE_ERR_INVALID, "class maps: k = %d outside 1..%lld (min(M, 64))", int(k),
+                     (long long)std::min<int64_t>(M, 64));
+  if (views < 1 || views > ORE_MAX_VIEWS)
+    return set_error(ctx, ORE_ERR_INVALID, "class maps: views = %d outside 1..%d (ORE_MAX_VIEWS)", int(views), ORE_MAX_VIEWS);
+  if (n % views != 0)
+    return set_error(ctx, ORE_ERR_INVALID, "class maps of %lld images: not a multiple of views = %d", (long long)n, int(views));
+  if (ore_status st = check_image_stride(ctx, "class maps", "x", x)) return st;
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  const ClassMaps p{x->data, w, bias, classes, maps, nstride_of(x), int(n), int(C), int(P), int(M), int(k), int(views),
+                    relu ? 1 : 0, int(P)};
+  if (!class_maps_eligible(p)) return set_error(ctx, ORE_ERR_INVALID, "class maps: %lld images of %lld pixels exceed one launch",
+                                                (long long)n, (long long)P);
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_class_maps_f32(p, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
 ore_status ore_matmul_f32(ore_ctx* ctx, const ore_tensor* a, const ore_tensor* b, ore_tensor* y) {
   if (!ctx || !a || !b || !y) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (a->ndim != 2 || b->ndim != 2 || y->ndim != 2 || a->dims[1] != b->dims[0] || y->dims[0] != a->dims[0] ||

@@ -21,6 +21,8 @@ void count_uses(ore_model* m, const std::vector<Step>& steps) {
   for (auto& s : steps)
     for (int id : {s.in0, s.in1, s.in2, s.in3})
       if (id >= 0) m->values[id].uses++;
+  // the class-map kernel reads the map conv's input after the pass (ore_model_set_cam): no pass may elide it
+  if (m->cam_buf && m->cam_in >= 0) m->values[m->cam_in].uses++;
 }
 
 // plane stride of a padded activation: 128-B aligned planes when that costs <= 5 %, else 16-B
@@ -711,6 +713,8 @@ struct Planner {
     }
     // the model output stays live to the end (it may be copied out after the last step)
     if (m->output_value >= 0) val(root(m->output_value)).last = nsteps;
+    // so does the map conv's input while the class maps are on: the kernel behind the top-k launch reads it
+    if (m->cam_buf && m->cam_in >= 0) val(root(m->cam_in)).last = nsteps;
 
     struct Slot { int64_t off, size; int first, last; };
     std::vector<int> roots;

@@ -68,6 +68,7 @@ EXPORTED = [
     "ore_model_graph_capture", "ore_model_graph_launch", "ore_model_enable_timing",
     "ore_model_step_count", "ore_model_step_info", "ore_model_step_times", "ore_model_run_batch",
     "ore_ctx_set_alloc_fill", "ore_model_fill_scratch", "ore_model_scratch_info",
+    "ore_class_maps_f32", "ore_model_cam_dims", "ore_model_set_cam",
 ]
 
 
@@ -219,6 +220,9 @@ def load():
         "ore_image_list_oriented": (i32, [vp]),
         "ore_topk_mean_f32": (i32, [vp, T, i32, i32, vp, vp]),
         "ore_model_set_views": (i32, [vp, i32]),
+        "ore_class_maps_f32": (i32, [vp, T, vp, vp, i64, i32, vp, i32, i32, vp]),
+        "ore_model_cam_dims": (i32, [vp, I64P]),
+        "ore_model_set_cam": (i32, [vp, vp, i64]),
         "ore_model_parse": (i32, [ctypes.c_char_p, ctypes.c_size_t]),
         "ore_model_load": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, ctypes.POINTER(vp)]),
         "ore_model_load_ex": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, i32, ctypes.POINTER(vp)]),

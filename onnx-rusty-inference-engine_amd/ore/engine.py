@@ -926,6 +926,52 @@ def topk_mean(ctx: Context, x, views: int, k: int):
     return values, indices
 
 
+def class_maps(ctx: Context, x, w, bias, classes, relu: bool = True, views: int = 1):
+    """ore_class_maps_f32 (extension): the class activation maps of the selected classes, a gathered 1x1 conv.
+    x float32 [n, C, H, W] (images may be strided: x.stride(0) >= C*H*W with dense images), w float32 [M, C]
+    (or [M, C, 1, 1]), bias float32 [M] or None, classes int32 [n // views, k]; returns float32 [n, k, H, W] with
+    maps[i, j] = relu?(conv1x1(x[i], w[classes[i // views, j]]) + bias[...]), the conv kernels' bits."""
+    torch = _torch()
+    for name, t, dt in (("x", x, torch.float32), ("w", w, torch.float32), ("classes", classes, torch.int32)) + \
+            ((("bias", bias, torch.float32),) if bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise OreError(1, f"{name}: expected a {str(dt).split('.')[-1]} CUDA tensor")
+        if t.device.index != ctx.device:
+            raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
+    if x.dim() != 4:
+        raise OreError(1, f"x: expected [n, C, H, W], got {tuple(x.shape)}")
+    n, C, H, W = (int(s) for s in x.shape)
+    if n and (not x[0].is_contiguous() or (n > 1 and x.stride(0) < C * H * W)):
+        raise OreError(1, "x: expected dense images at an image stride of at least C*H*W")
+    if not w.is_contiguous() or w.dim() not in (2, 4) or int(w.shape[1]) != C or w.numel() != int(w.shape[0]) * C:
+        raise OreError(1, f"w: expected a contiguous [M, {C}] tensor, got {tuple(w.shape)}")
+    M = int(w.shape[0])
+    if bias is not None and (not bias.is_contiguous() or tuple(bias.shape) != (M,)):
+        raise OreError(1, f"bias: expected a contiguous [{M}] tensor, got {tuple(bias.shape)}")
+    views = int(views)
+    if not 1 <= views <= _lib.MAX_VIEWS:
+        raise OreError(1, f"views = {views} outside 1..{_lib.MAX_VIEWS}")
+    if n % views:
+        raise OreError(1, f"{n} images are not a multiple of views = {views}")
+    if classes.dim() != 2 or not classes.is_contiguous() or int(classes.shape[0]) != n // views:
+        raise OreError(1, f"classes: expected a contiguous [{n // views}, k] tensor, got {tuple(classes.shape)}")
+    k = int(classes.shape[1])
+    if not 1 <= k <= min(M, 64):
+        raise OreError(1, f"k = {k} outside 1..{min(M, 64)} (min(M, 64))")
+    d = Tensor()
+    d.data = x.data_ptr()
+    d.ndim = 4
+    d.dims[0], d.dims[1], d.dims[2], d.dims[3] = n, C, H, W
+    d.nstride = int(x.stride(0)) if n > 1 else 0
+    maps = torch.empty((n, k, H, W), dtype=torch.float32, device=x.device)
+    if n == 0:
+        return maps
+    check(load().ore_class_maps_f32(ctx.h, ctypes.byref(d), ctypes.c_void_p(w.data_ptr()),
+                                    ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, M, 1 if relu else 0,
+                                    ctypes.c_void_p(classes.data_ptr()), k, views, ctypes.c_void_p(maps.data_ptr())), ctx.h)
+    return maps
+
+
 # ------------------------------------------------------------------------------ graph walker
 class Model:
     """ore_model: the device-resident walker over one ONNX graph."""
@@ -1102,6 +1148,64 @@ class Model:
         [n // views, topk], n a multiple of views.  1 <= views <= min(64, run_batch); default 1.  run* ignore it."""
         check(load().ore_model_set_views(self.h, int(views)), self.ctx.h)
         self.views = int(views)
+
+    # ---- class activation maps (ore_model_set_cam): the map-conv planes of the selected classes
+    _cam_out = None  # the tensor of set_cam_output (kept alive: the library holds its pointer)
+
+    @property
+    def cam_hw(self):
+        """ore_model_cam_dims: (Hm, Wm) of the model's class activation maps; raises ORE_ERR_UNSUPPORTED for a
+        model without a map conv (a 1x1 Conv [-> Relu] -> GlobalAveragePool head)."""
+        hw = (ctypes.c_int64 * 2)()
+        check(load().ore_model_cam_dims(self.h, hw), self.ctx.h)
+        return int(hw[0]), int(hw[1])
+
+    def set_cam_output(self, maps):
+        """ore_model_set_cam: while a float32 CUDA tensor is set, classify* / capture_classify* also write the
+        class activation maps of the classes they select into it, as [n, topk, Hm, Wm] (maps[i, j] belongs to
+        classes[i // views, j]); it must hold n * topk * Hm * Wm floats for every call.  None turns the maps
+        off.  Turning them on or off replans the model (re-capture graphs afterwards); another tensor does not."""
+        torch = _torch()
+        if maps is None:
+            check(load().ore_model_set_cam(self.h, None, 0), self.ctx.h)
+            self._cam_out = None
+        else:
+            if not isinstance(maps, torch.Tensor) or not maps.is_cuda or maps.dtype != torch.float32:
+                raise OreError(1, "maps: expected a float32 CUDA tensor")
+            if maps.device.index != self.ctx.device:
+                raise OreError(1, f"maps: on cuda:{maps.device.index}, the context is on cuda:{self.ctx.device}")
+            if not maps.is_contiguous():
+                raise OreError(1, "maps: expected a contiguous tensor")
+            check(load().ore_model_set_cam(self.h, ctypes.c_void_p(maps.data_ptr()), int(maps.numel())), self.ctx.h)
+            self._cam_out = maps
+        self.run_batch = int(load().ore_model_run_batch(self.h))
+
+    def _with_cam(self, n: int, call):
+        """call() with a fresh [n, topk, Hm, Wm] tensor set as the map output; the previous setting is restored."""
+        torch = _torch()
+        maps = torch.empty((n, self.topk) + self.cam_hw, dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        if n == 0:
+            return call() + (maps,)
+        prev = self._cam_out
+        self.set_cam_output(maps)
+        try:
+            return call() + (maps,)
+        finally:
+            self.set_cam_output(prev)
+
+    def classify_cam(self, x):
+        """classify(x) with the class activation maps: (scores, classes, maps [n, topk, Hm, Wm]).  A convenience: it
+        sets a fresh buffer and restores the previous setting, two replans per call from off; for repeated calls
+        set_cam_output once and use classify_into."""
+        return self._with_cam(self._check_classify_in(x, False), lambda: self.classify(x))
+
+    def classify_cam_u8(self, x):
+        """classify_u8(x) with the class activation maps."""
+        return self._with_cam(self._check_classify_in(x, True), lambda: self.classify_u8(x))
+
+    def classify_cam_u8_list(self, lst):
+        """classify_u8_list(lst) with the class activation maps."""
+        return self._with_cam(self._check_list(lst), lambda: self.classify_u8_list(lst))
 
     def _subjects(self, n: int) -> int:
         """The output rows of a classification of n images: n // views, n a multiple of views."""
