@@ -873,6 +873,51 @@ ore_status ore_class_maps_f32(ore_ctx* ctx, const ore_tensor* x, const float* w,
                               const int32_t* classes, int32_t k, int32_t views, float* maps);
 ore_status ore_model_cam_dims(ore_model* m, int64_t hw[2]);
 ore_status ore_model_set_cam(ore_model* m, float* d_maps, int64_t cap_elems);
+/* Localisation from class activation maps (extension; ore_cam_box.hip): the maps at image
+ * resolution, and one box per map (Zhou et al. 2016: resize the map to the image, keep what is above a fraction
+ * of its range, box the largest connected component).  Given the bits of a map, both answers are exact.
+ *  Upsampled value.  A plane m [Hm, Wm] resized to H x W, H >= Hm and W >= Wm: with (y0, y1, ty) row r's entry of
+ *    ore_resize_taps(Hm, H, 0, H), (x0, x1, tx) column q's of ore_resize_taps(Wm, W, 0, W), and a, b, c, d =
+ *    m[y0, x0], m[y0, x1], m[y1, x0], m[y1, x1]:
+ *        top = a + (b - a) tx;  bot = c + (d - c) tx;  u[r, q] = top + (bot - top) ty
+ *    where every -, * and + rounds on its own (never an FMA), as in the resize above.  With H = Hm and W = Wm it is
+ *    m exactly.  NaN and +-inf follow the arithmetic as written.
+ *  Box.  For one plane, u its upsampled values and a fraction 0 <= frac <= 1: lo, hi = the minimum and maximum of
+ *    the non-NaN elements of u (np.fmin / np.fmax reductions; NaN when there is none);
+ *        thr = fadd_rn(lo, fmul_rn(frac, fsub_rn(hi, lo)));   mask = u >= thr
+ *    (a NaN u or a NaN thr is false).  Components of the mask are 8-connected; the chosen one has the most pixels,
+ *    and among equal counts the one whose first pixel in raster order comes first.  box = (top, left, bottom, right),
+ *    half-open, in the H x W grid, and area = the component's pixel count; an empty mask gives (0, 0, 0, 0) and 0.
+ *  Caps of the box: Hm Wm <= ORE_CAM_BOX_MAX_MAP, Hm <= H <= ORE_CAM_BOX_MAX_SIDE, Wm <= W <= ORE_CAM_BOX_MAX_SIDE.
+ *  ore_upsample_maps_f32: DEVICE contiguous maps [planes, hm, wm] -> DEVICE out [planes, h, w]; nothing else is written.
+ *    Checked in this order, the context last, all before any device call (ORE_ERR_INVALID, the message names the
+ *    quantity): null pointers; planes < 0; hm, wm, h, w outside 1..16384; h < hm or w < wm; planes h w >= 2^31.
+ *  ore_cam_boxes_f32: DEVICE contiguous maps [planes, hm, wm] -> DEVICE boxes [planes, 4] and areas [planes] (or
+ *    NULL), one workgroup per plane, no global scratch; the H x W planes are never stored.  Checked in this order,
+ *    the context last (ORE_ERR_INVALID): null maps or boxes; planes < 0 (or >= 2^31); the caps (hm wm, then h, then
+ *    w); h < hm or w < wm; frac outside [0, 1] or NaN.
+ *  Both: planes == 0 is ORE_OK and launches nothing.
+ *  ore_cam_box_host: host only, one plane in HOST memory, as ore_resize_taps is: the plain C++ restatement (the
+ *    shared tap header, a queue flood fill) for integrators to test against.  The checks of ore_cam_boxes_f32;
+ *    area may be NULL.
+ *  ore_model_set_cam_boxes: while d_boxes (DEVICE, cap_planes x 4 int32; d_areas cap_planes int32 or NULL) is set,
+ *    every classify entry that ore_model_set_cam governs launches the box kernel behind each chunk's map launch
+ *    (after the pass's last timing event; not an exec step) over planes [i0 topk, (i0 + nc) topk) of the maps buffer,
+ *    H x W the model's input size: boxes[i, j] belongs to maps[i, j] (per image under views, as the maps are).
+ *    ORE_ERR_INVALID when the maps are off, when frac is outside [0, 1], when cap_planes < 0, and inside a stream
+ *    capture; ORE_ERR_UNSUPPORTED naming it when the model's map or input size is outside the caps.  A classify
+ *    call with n topk > cap_planes is ORE_ERR_INVALID before any device call.  d_boxes == NULL turns the boxes off
+ *    (the default), and so does ore_model_set_cam(m, NULL, 0).  It never replans and allocates nothing; a captured
+ *    graph keeps the setting it was captured with.  Off, every entry launches what it launched without it. */
+#define ORE_CAM_BOX_MAX_MAP 4096
+#define ORE_CAM_BOX_MAX_SIDE 512
+ore_status ore_upsample_maps_f32(ore_ctx* ctx, const float* maps, int64_t planes, int64_t hm, int64_t wm, int64_t h, int64_t w,
+                                 float* out);
+ore_status ore_cam_boxes_f32(ore_ctx* ctx, const float* maps, int64_t planes, int64_t hm, int64_t wm, int64_t h, int64_t w,
+                             float frac, int32_t* boxes, int32_t* areas);
+ore_status ore_cam_box_host(const float* map, int64_t hm, int64_t wm, int64_t h, int64_t w, float frac, int32_t box[4],
+                            int32_t* area);
+ore_status ore_model_set_cam_boxes(ore_model* m, int32_t* d_boxes, int32_t* d_areas, int64_t cap_planes, float frac);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);
 int32_t ore_model_step_count(ore_model* m);
 ore_status ore_model_step_info(ore_model* m, int32_t i, const char** op, const char** name, double* flops,

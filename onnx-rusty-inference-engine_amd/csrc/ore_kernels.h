@@ -588,5 +588,17 @@ struct ClassMaps {
 bool class_maps_eligible(const ClassMaps& p);
 void launch_class_maps_f32(const ClassMaps& p, hipStream_t s);
 void launch_class_maps_f16(const ClassMaps& p, hipStream_t s);
+// localisation from class activation maps (ore_cam_box.hip; include/ore.h states the arithmetic): contiguous f32
+// planes [planes][hm][wm] resized to [planes][h][w] with the float bilinear filter (hm <= h, wm <= w, each at most
+// RESIZE_MAX, planes h w < 2^31), and per plane the box (top, left, bottom, right), half-open, and the pixel count
+// of the largest 8-connected component of the resized plane at or above lo + frac (hi - lo).  The box kernel is
+// one workgroup per plane in LDS: cam_boxes_unsupported names the quantity outside its caps ("map", "h", "w"), or
+// returns null.  areas may be null.  planes >= 1.
+constexpr int CAM_BOX_MAX_MAP = 4096;  // ORE_CAM_BOX_MAX_MAP: hm wm
+constexpr int CAM_BOX_MAX_SIDE = 512;  // ORE_CAM_BOX_MAX_SIDE: h, w
+const char* cam_boxes_unsupported(long long hm, long long wm, long long h, long long w);
+void launch_upsample_maps_f32(const float* maps, long long planes, int hm, int wm, int h, int w, float* out, hipStream_t s);
+void launch_cam_boxes_f32(const float* maps, long long planes, int hm, int wm, int h, int w, float frac, int* boxes, int* areas,
+                          hipStream_t s);
 
 }  // namespace ore

@@ -1011,6 +1011,9 @@ static ore_status check_cam(ore_model* m, int64_t n) {
     return set_error(m->ctx, ORE_ERR_INVALID, "the class maps of %lld images at k = %d (%lld x %lld) need %lld floats, the buffer of "
                      "ore_model_set_cam holds %lld", (long long)n, int(m->topk), (long long)T.dims[2], (long long)T.dims[3],
                      (long long)need, (long long)m->cam_cap);
+  if (m->box_buf && n * m->topk > m->box_cap)
+    return set_error(m->ctx, ORE_ERR_INVALID, "the boxes of %lld images at k = %d need %lld planes, the buffers of "
+                     "ore_model_set_cam_boxes hold %lld", (long long)n, int(m->topk), (long long)(n * m->topk), (long long)m->box_cap);
   return ORE_OK;
 }
 
@@ -1038,6 +1041,19 @@ static ore_status launch_cam(ore_model* m, int64_t i0, int64_t nc, int64_t views
   if (!class_maps_eligible(p)) return err(m, ORE_ERR_INVALID, "internal: class maps on an unsupported layout");
   if (m->f16) launch_class_maps_f16(p, ctx->stream);
   else launch_class_maps_f32(p, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+// The boxes of a chunk's maps (ore_model_set_cam_boxes): planes [i0 topk, (i0 + nc) topk) of the maps buffer that
+// launch_cam just filled, resized to the model's input size
+static ore_status launch_cam_boxes(ore_model* m, int64_t i0, int64_t nc) {
+  ore_ctx* ctx = m->ctx;
+  const Value& T = m->values[m->cam_map];
+  const Value& iv = m->values[m->input_value];
+  const int64_t P = T.dims[2] * T.dims[3], p0 = i0 * m->topk;
+  launch_cam_boxes_f32(m->cam_buf + p0 * P, nc * m->topk, int(T.dims[2]), int(T.dims[3]), int(iv.dims[2]), int(iv.dims[3]),
+                       m->box_frac, m->box_buf + p0 * 4, m->box_areas ? m->box_areas + p0 : nullptr, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }
@@ -1133,7 +1149,11 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
                        d_classes + g0 * m->topk, ctx->stream);
       ORE_HIP_CHECK(ctx, hipGetLastError());
       if (m->cam_buf)  // the maps of the classes just selected, from the map conv's input the pass left in place
+      {
         if (ore_status st = launch_cam(m, i0, nc, views, d_classes)) return st;
+        if (m->box_buf)
+          if (ore_status st = launch_cam_boxes(m, i0, nc)) return st;
+      }
     }
   }
   return ORE_OK;
@@ -1245,6 +1265,38 @@ ore_status ore_model_set_cam(ore_model* m, float* d_maps, int64_t cap_elems) {
   }
   m->cam_buf = d_maps;
   m->cam_cap = d_maps ? cap_elems : 0;
+  if (!d_maps) {  // the boxes are those of the maps
+    m->box_buf = m->box_areas = nullptr;
+    m->box_cap = 0;
+  }
+  return ORE_OK;
+}
+
+ore_status ore_model_set_cam_boxes(ore_model* m, int32_t* d_boxes, int32_t* d_areas, int64_t cap_planes, float frac) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  ore_ctx* ctx = m->ctx;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return set_error(ctx, ORE_ERR_INVALID, "ore_model_set_cam_boxes inside a stream capture");
+  if (d_boxes) {
+    if (m->cam_conv < 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "%s", m->cam_why.c_str());
+    if (!m->cam_buf)
+      return set_error(ctx, ORE_ERR_INVALID, "ore_model_set_cam_boxes: the class maps are off (ore_model_set_cam first: the boxes "
+                       "are computed from its buffer)");
+    if (cap_planes < 0) return set_error(ctx, ORE_ERR_INVALID, "box buffers of %lld planes", (long long)cap_planes);
+    if (!(frac >= 0.0f && frac <= 1.0f)) return set_error(ctx, ORE_ERR_INVALID, "cam boxes: frac = %g outside [0, 1]", double(frac));
+    const Value& T = m->values[m->cam_map];
+    const Value& iv = m->values[m->input_value];
+    const int64_t hm = T.dims[2], wm = T.dims[3], h = iv.ndim == 4 ? iv.dims[2] : 0, w = iv.ndim == 4 ? iv.dims[3] : 0;
+    if (cam_boxes_unsupported(hm, wm, h, w) || h < hm || w < wm)
+      return set_error(ctx, ORE_ERR_UNSUPPORTED, "cam boxes: a %lld x %lld map under a %lld x %lld input is outside the box kernel's "
+                       "caps (hm * wm <= %d, hm <= h <= %d, wm <= w <= %d)", (long long)hm, (long long)wm, (long long)h, (long long)w,
+                       ORE_CAM_BOX_MAX_MAP, ORE_CAM_BOX_MAX_SIDE, ORE_CAM_BOX_MAX_SIDE);
+  }
+  m->box_buf = d_boxes;
+  m->box_areas = d_boxes ? d_areas : nullptr;
+  m->box_cap = d_boxes ? cap_planes : 0;
+  m->box_frac = d_boxes ? frac : 0.0f;
   return ORE_OK;
 }
 

@@ -206,6 +206,11 @@ struct ore_model {
   std::string cam_why;
   float* cam_buf = nullptr;      // DEVICE [n, topk, Hm, Wm]; null: off
   int64_t cam_cap = 0;           // its capacity in floats
+  // boxes of the class activation maps (ore_model_set_cam_boxes): one launch behind each chunk's map launch
+  int32_t* box_buf = nullptr;    // DEVICE [n, topk, 4]; null: off
+  int32_t* box_areas = nullptr;  // DEVICE [n, topk] or null
+  int64_t box_cap = 0;           // planes both hold
+  float box_frac = 0.0f;         // the threshold's share of the map's range
 };
 
 namespace ore {

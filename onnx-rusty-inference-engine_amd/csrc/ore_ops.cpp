@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "ore_chunk.h"
 #include "ore_internal.h"
@@ -910,6 +911,111 @@ ore_status ore_class_maps_f32(ore_ctx* ctx, const ore_tensor* x, const float* w,
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   launch_class_maps_f32(p, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+static_assert(CAM_BOX_MAX_MAP == ORE_CAM_BOX_MAX_MAP && CAM_BOX_MAX_SIDE == ORE_CAM_BOX_MAX_SIDE, "ore.h and ore_kernels.h");
+
+// the rules that ore_cam_boxes_f32 and ore_cam_box_host share, behind their pointer checks, in the header's order
+static ore_status check_cam_box_shape(ore_ctx* ctx, int64_t hm, int64_t wm, int64_t h, int64_t w, float frac) {
+  if (const char* what = cam_boxes_unsupported(hm, wm, h, w)) {
+    if (what[0] == 'm')
+      return set_error(ctx, ORE_ERR_INVALID, "cam boxes: a map of hm x wm = %lld x %lld, expected hm, wm >= 1 and hm * wm <= %d "
+                       "(ORE_CAM_BOX_MAX_MAP)", (long long)hm, (long long)wm, ORE_CAM_BOX_MAX_MAP);
+    return set_error(ctx, ORE_ERR_INVALID, "cam boxes: %s = %lld outside 1..%d (ORE_CAM_BOX_MAX_SIDE)", what,
+                     (long long)(what[0] == 'h' ? h : w), ORE_CAM_BOX_MAX_SIDE);
+  }
+  if (h < hm) return set_error(ctx, ORE_ERR_INVALID, "cam boxes: h = %lld below hm = %lld (the map is only enlarged)", (long long)h, (long long)hm);
+  if (w < wm) return set_error(ctx, ORE_ERR_INVALID, "cam boxes: w = %lld below wm = %lld (the map is only enlarged)", (long long)w, (long long)wm);
+  if (!(frac >= 0.0f && frac <= 1.0f)) return set_error(ctx, ORE_ERR_INVALID, "cam boxes: frac = %g outside [0, 1]", double(frac));
+  return ORE_OK;
+}
+
+ore_status ore_upsample_maps_f32(ore_ctx* ctx, const float* maps, int64_t planes, int64_t hm, int64_t wm, int64_t h, int64_t w,
+                                 float* out) {
+  if (!maps || !out) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (planes < 0) return set_error(ctx, ORE_ERR_INVALID, "upsample maps: planes = %lld", (long long)planes);
+  const int64_t sides[4] = {hm, wm, h, w};
+  const char* const names[4] = {"hm", "wm", "h", "w"};
+  for (int i = 0; i < 4; ++i)
+    if (sides[i] < 1 || sides[i] > RESIZE_MAX)
+      return set_error(ctx, ORE_ERR_INVALID, "upsample maps: %s = %lld outside 1..%d", names[i], (long long)sides[i], RESIZE_MAX);
+  if (h < hm) return set_error(ctx, ORE_ERR_INVALID, "upsample maps: h = %lld below hm = %lld (the map is only enlarged)", (long long)h, (long long)hm);
+  if (w < wm) return set_error(ctx, ORE_ERR_INVALID, "upsample maps: w = %lld below wm = %lld (the map is only enlarged)", (long long)w, (long long)wm);
+  if (planes > ((int64_t(1) << 31) - 1) / (h * w))
+    return set_error(ctx, ORE_ERR_INVALID, "upsample maps: planes * h * w = %lld * %lld * %lld is not below 2^31", (long long)planes,
+                     (long long)h, (long long)w);
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (planes == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_upsample_maps_f32(maps, planes, int(hm), int(wm), int(h), int(w), out, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_cam_boxes_f32(ore_ctx* ctx, const float* maps, int64_t planes, int64_t hm, int64_t wm, int64_t h, int64_t w,
+                             float frac, int32_t* boxes, int32_t* areas) {
+  if (!maps || !boxes) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (planes < 0 || !fits_i32(planes)) return set_error(ctx, ORE_ERR_INVALID, "cam boxes: planes = %lld", (long long)planes);
+  if (ore_status st = check_cam_box_shape(ctx, hm, wm, h, w, frac)) return st;
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (planes == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_cam_boxes_f32(maps, planes, int(hm), int(wm), int(h), int(w), frac, boxes, areas, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+// The arithmetic of include/ore.h in plain C++: the resized plane from resize_tap and resize_lerp_rn, lo / hi by
+// comparisons (a NaN never enters), the mask, and a queue flood fill over the pixels in raster order, so that the
+// components come in the order of their first pixels and a later one must be strictly larger to win.
+ore_status ore_cam_box_host(const float* map, int64_t hm, int64_t wm, int64_t h, int64_t w, float frac, int32_t box[4],
+                            int32_t* area) {
+  if (!map || !box) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  if (ore_status st = check_cam_box_shape(nullptr, hm, wm, h, w, frac)) return st;
+  const int H = int(h), W = int(w), Wm = int(wm);
+  std::vector<ResizeTap> ty(H), tx(W);
+  for (int r = 0; r < H; ++r) ty[r] = resize_tap(int(hm), H, r);
+  for (int q = 0; q < W; ++q) tx[q] = resize_tap(Wm, W, q);
+  std::vector<float> u(size_t(H) * W);
+  float lo = INFINITY, hi = -INFINITY;
+  for (int r = 0; r < H; ++r)
+    for (int q = 0; q < W; ++q) {
+      const float* r0 = map + ty[r].i0 * Wm;
+      const float* r1 = map + ty[r].i1 * Wm;
+      const float top = resize_lerp_rn(r0[tx[q].i0], r0[tx[q].i1], tx[q].t);
+      const float bot = resize_lerp_rn(r1[tx[q].i0], r1[tx[q].i1], tx[q].t);
+      const float v = resize_lerp_rn(top, bot, ty[r].t);
+      u[size_t(r) * W + q] = v;
+      if (v < lo) lo = v;
+      if (v > hi) hi = v;
+    }
+  // no non-NaN value leaves lo = +inf, hi = -inf: the threshold is then NaN, as that of the NaN reductions is
+  const float thr = resize_lerp_rn(lo, hi, frac);
+  std::vector<uint8_t> todo(size_t(H) * W);
+  for (size_t i = 0; i < todo.size(); ++i) todo[i] = u[i] >= thr;
+  std::vector<int> queue;
+  int best = 0, bt = 0, bl = 0, bb = 0, br = 0;
+  for (int s = 0; s < H * W; ++s) {
+    if (!todo[s]) continue;
+    queue.assign(1, s);
+    todo[s] = 0;
+    int t = H, l = W, b = -1, rr = -1;
+    for (size_t k = 0; k < queue.size(); ++k) {
+      const int r = queue[k] / W, q = queue[k] - r * W;
+      t = std::min(t, r), b = std::max(b, r), l = std::min(l, q), rr = std::max(rr, q);
+      for (int dr = -1; dr <= 1; ++dr)
+        for (int dq = -1; dq <= 1; ++dq) {
+          const int r2 = r + dr, q2 = q + dq;
+          if (r2 < 0 || r2 >= H || q2 < 0 || q2 >= W || !todo[r2 * W + q2]) continue;
+          todo[r2 * W + q2] = 0;
+          queue.push_back(r2 * W + q2);
+        }
+    }
+    if (int(queue.size()) > best) best = int(queue.size()), bt = t, bl = l, bb = b + 1, br = rr + 1;
+  }
+  box[0] = bt, box[1] = bl, box[2] = bb, box[3] = br;
+  if (area) *area = best;
   return ORE_OK;
 }
 

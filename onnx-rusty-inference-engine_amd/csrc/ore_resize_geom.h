@@ -41,6 +41,16 @@ ORE_RS_HD inline ResizeTap resize_tap(int S, int D, int o) {
   return r;
 }
 
+// The blend of two samples under a tap's weight, every operation rounded on its own (never an FMA): a + (b - a) t.
+// The float resizes (the class activation maps of ore_cam_box.hip and their host restatement ore_cam_box_host) take
+// it from here; ore_resize.hip keeps its own lerp_rn, the same three operations.
+ORE_RS_HD inline float resize_lerp_rn(float a, float b, float t) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  const float p = d * t;
+  return a + p;
+}
+
 // one axis of a geometry: S source samples resized to D, of which [origin, origin + count) are produced
 ORE_RS_HD inline bool resize_axis_ok(long long S, long long D, long long origin, long long count) {
   return S >= 1 && S <= RESIZE_MAX && D >= 1 && D <= RESIZE_MAX && origin >= 0 && count >= 1 && count <= D &&

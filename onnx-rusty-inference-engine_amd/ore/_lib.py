@@ -39,6 +39,8 @@ IMAGE_INTERLEAVED, IMAGE_NV12, IMAGE_YUV = 0, 1, 2  # ore_image_format (ore_imag
 YUV_FORMATS = {"nv12": 0, "yuyv": 1, "i444": 2, "i440": 3, "i422": 4, "i420": 5, "i411": 6, "gray": 7}
 IMAGE_FLIP_H = 1  # ORE_IMAGE_FLIP_H: the per-descriptor flag of ore_image_list_set_ex / _set_nv12_ex
 MAX_VIEWS = 64  # ORE_MAX_VIEWS (ore_topk_mean_f32, ore_model_set_views)
+CAM_BOX_MAX_MAP = 4096  # ORE_CAM_BOX_MAX_MAP (ore_cam_boxes_f32: Hm * Wm)
+CAM_BOX_MAX_SIDE = 512  # ORE_CAM_BOX_MAX_SIDE (ore_cam_boxes_f32: H, W)
 PAD = {"NOTSET": 0, "NOT_SET": 0, "SAME_UPPER": 1, "SAME_LOWER": 2, "VALID": 3}
 
 # every symbol include/ore.h declares (checked by tests/test_abi.py on CPU)
@@ -69,6 +71,7 @@ EXPORTED = [
     "ore_model_step_count", "ore_model_step_info", "ore_model_step_times", "ore_model_run_batch",
     "ore_ctx_set_alloc_fill", "ore_model_fill_scratch", "ore_model_scratch_info",
     "ore_class_maps_f32", "ore_model_cam_dims", "ore_model_set_cam",
+    "ore_upsample_maps_f32", "ore_cam_boxes_f32", "ore_cam_box_host", "ore_model_set_cam_boxes",
 ]
 
 
@@ -223,6 +226,10 @@ def load():
         "ore_class_maps_f32": (i32, [vp, T, vp, vp, i64, i32, vp, i32, i32, vp]),
         "ore_model_cam_dims": (i32, [vp, I64P]),
         "ore_model_set_cam": (i32, [vp, vp, i64]),
+        "ore_upsample_maps_f32": (i32, [vp, vp, i64, i64, i64, i64, i64, vp]),
+        "ore_cam_boxes_f32": (i32, [vp, vp, i64, i64, i64, i64, i64, ctypes.c_float, vp, vp]),
+        "ore_cam_box_host": (i32, [vp, i64, i64, i64, i64, ctypes.c_float, vp, vp]),
+        "ore_model_set_cam_boxes": (i32, [vp, vp, vp, i64, ctypes.c_float]),
         "ore_model_parse": (i32, [ctypes.c_char_p, ctypes.c_size_t]),
         "ore_model_load": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, ctypes.POINTER(vp)]),
         "ore_model_load_ex": (i32, [vp, ctypes.c_char_p, ctypes.c_size_t, i64, i32, ctypes.POINTER(vp)]),

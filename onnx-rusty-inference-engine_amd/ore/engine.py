@@ -972,6 +972,88 @@ def class_maps(ctx: Context, x, w, bias, classes, relu: bool = True, views: int 
     return maps
 
 
+def _check_maps(ctx: Context, maps, out_hw, name: str):
+    """(planes, Hm, Wm, H, W) of contiguous float32 CUDA maps [..., Hm, Wm] on the context's device."""
+    torch = _torch()
+    if not isinstance(maps, torch.Tensor) or not maps.is_cuda or maps.dtype != torch.float32:
+        raise OreError(1, f"{name}: maps: expected a float32 CUDA tensor")
+    if maps.device.index != ctx.device:
+        raise OreError(1, f"{name}: maps: on cuda:{maps.device.index}, the context is on cuda:{ctx.device}")
+    if maps.dim() < 2 or not maps.is_contiguous():
+        raise OreError(1, f"{name}: maps: expected a contiguous [..., Hm, Wm] tensor, got {tuple(maps.shape)}")
+    hm, wm = (int(s) for s in maps.shape[-2:])
+    h, w = (int(v) for v in out_hw)
+    if min(hm, wm, h, w) < 1:
+        raise OreError(1, f"{name}: a {hm} x {wm} map resized to {h} x {w}: sizes must be positive")
+    planes = 1
+    for s in maps.shape[:-2]:
+        planes *= int(s)
+    return planes, hm, wm, h, w
+
+
+def upsample_maps(ctx: Context, maps, out_hw):
+    """ore_upsample_maps_f32 (extension): float32 maps [..., Hm, Wm] resized to [..., H, W] with the bilinear filter
+    of resize_taps on floats (H >= Hm, W >= Wm), every operation rounded on its own: numpy reproduces the bits."""
+    torch = _torch()
+    planes, hm, wm, h, w = _check_maps(ctx, maps, out_hw, "upsample_maps")
+    out = torch.empty(tuple(maps.shape[:-2]) + (h, w), dtype=torch.float32, device=maps.device)
+    if planes == 0:
+        return out
+    check(load().ore_upsample_maps_f32(ctx.h, ctypes.c_void_p(maps.data_ptr()), planes, hm, wm, h, w,
+                                       ctypes.c_void_p(out.data_ptr())), ctx.h)
+    return out
+
+
+def cam_boxes(ctx: Context, maps, out_hw, frac: float = 0.2):
+    """ore_cam_boxes_f32 (extension): for every plane of float32 maps [..., Hm, Wm], the bounding box (top, left,
+    bottom, right), half-open, in the H x W grid, of the largest 8-connected component of the upsampled plane at or
+    above lo + frac * (hi - lo), and that component's pixel count: (boxes int32 [..., 4], areas int32 [...]).  An
+    empty mask gives (0, 0, 0, 0) and 0; among equal counts the component met first in raster order wins."""
+    torch = _torch()
+    planes, hm, wm, h, w = _check_maps(ctx, maps, out_hw, "cam_boxes")
+    lead = tuple(maps.shape[:-2])
+    boxes = torch.empty(lead + (4,), dtype=torch.int32, device=maps.device)
+    areas = torch.empty(lead, dtype=torch.int32, device=maps.device)
+    if planes == 0:
+        return boxes, areas
+    check(load().ore_cam_boxes_f32(ctx.h, ctypes.c_void_p(maps.data_ptr()), planes, hm, wm, h, w, float(frac),
+                                   ctypes.c_void_p(boxes.data_ptr()), ctypes.c_void_p(areas.data_ptr())), ctx.h)
+    return boxes, areas
+
+
+def cam_box_reference(map_np, out_hw, frac: float = 0.2):
+    """ore_cam_box_host (host only): the box and the area of one float32 plane [Hm, Wm] by the library's plain C++
+    restatement of cam_boxes' arithmetic: ((top, left, bottom, right), area)."""
+    m = np.ascontiguousarray(map_np, dtype=np.float32)
+    if m.ndim != 2:
+        raise OreError(1, f"cam_box_reference: expected one [Hm, Wm] plane, got {m.shape}")
+    h, w = (int(v) for v in out_hw)
+    box = (ctypes.c_int32 * 4)()
+    area = ctypes.c_int32()
+    check(load().ore_cam_box_host(m.ctypes.data_as(ctypes.c_void_p), m.shape[0], m.shape[1], h, w, float(frac), box,
+                                  ctypes.byref(area)))
+    return tuple(int(v) for v in box), int(area.value)
+
+
+def box_to_source(box, src_hw, resized_hw, origin, out_hw, flip: bool = False):
+    """Host arithmetic only: a box (top, left, bottom, right) of the model's H x W window (out_hw) as float
+    (y0, x0, y1, x1) in the displayed source image of src_hw = (Hs, Ws), for the window that starts at `origin` of
+    the image resized to resized_hw = (rh, rw) -- the geometry an image list or set_input_resize was given.  Columns
+    are mirrored within W first when the descriptor was flipped; then the origin is added and rows scale by Hs / rh,
+    columns by Ws / rw.  List geometries describe the displayed (oriented) image, so orientations need nothing."""
+    t, l, b, r = (float(v) for v in box)
+    hs, ws = (int(v) for v in src_hw)
+    rh, rw = (int(v) for v in resized_hw)
+    top, left = (int(v) for v in origin)
+    h, w = (int(v) for v in out_hw)
+    if min(hs, ws, rh, rw, h, w) < 1 or top < 0 or left < 0 or top + h > rh or left + w > rw:
+        raise OreError(1, f"box_to_source: a {h} x {w} window at {(top, left)} of a {rh} x {rw} resized image of {hs} x {ws}")
+    if flip:
+        l, r = w - r, w - l
+    sy, sx = hs / rh, ws / rw
+    return (t + top) * sy, (l + left) * sx, (b + top) * sy, (r + left) * sx
+
+
 # ------------------------------------------------------------------------------ graph walker
 class Model:
     """ore_model: the device-resident walker over one ONNX graph."""
@@ -1169,6 +1251,7 @@ class Model:
         if maps is None:
             check(load().ore_model_set_cam(self.h, None, 0), self.ctx.h)
             self._cam_out = None
+            self._cam_boxes = None  # the boxes go with the maps
         else:
             if not isinstance(maps, torch.Tensor) or not maps.is_cuda or maps.dtype != torch.float32:
                 raise OreError(1, "maps: expected a float32 CUDA tensor")
@@ -1206,6 +1289,73 @@ class Model:
     def classify_cam_u8_list(self, lst):
         """classify_u8_list(lst) with the class activation maps."""
         return self._with_cam(self._check_list(lst), lambda: self.classify_u8_list(lst))
+
+    # ---- boxes of the class activation maps (ore_model_set_cam_boxes)
+    _cam_boxes = None  # (boxes, areas, frac) of set_cam_boxes (kept alive: the library holds their pointers)
+
+    def set_cam_boxes(self, boxes, areas=None, frac: float = 0.2):
+        """ore_model_set_cam_boxes: while an int32 CUDA tensor is set, classify* / capture_classify* also write, for
+        every map of set_cam_output, the box (top, left, bottom, right) in the model's H x W input of the largest
+        component of the upsampled map at or above lo + frac * (hi - lo): boxes as [n, topk, 4], areas (optional) as
+        [n, topk].  Both must hold n * topk planes for every call.  The maps must be on; None turns the boxes off, and
+        so does set_cam_output(None).  It never replans."""
+        torch = _torch()
+        if boxes is None:
+            check(load().ore_model_set_cam_boxes(self.h, None, None, 0, 0.0), self.ctx.h)
+            self._cam_boxes = None
+            return
+        for name, t in (("boxes", boxes),) + ((("areas", areas),) if areas is not None else ()):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32:
+                raise OreError(1, f"{name}: expected an int32 CUDA tensor")
+            if t.device.index != self.ctx.device:
+                raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{self.ctx.device}")
+            if not t.is_contiguous():
+                raise OreError(1, f"{name}: expected a contiguous tensor")
+        cap = int(boxes.numel()) // 4
+        if areas is not None:
+            cap = min(cap, int(areas.numel()))
+        check(load().ore_model_set_cam_boxes(self.h, ctypes.c_void_p(boxes.data_ptr()),
+                                             ctypes.c_void_p(areas.data_ptr()) if areas is not None else None, cap, float(frac)),
+              self.ctx.h)
+        self._cam_boxes = (boxes, areas, float(frac))
+
+    def _with_boxes(self, n: int, call, frac: float):
+        """_with_cam(n, call) with fresh [n, topk, 4] / [n, topk] tensors set as the box output; the previous
+        settings are restored (set_cam_output(None) inside _with_cam drops the boxes with the maps)."""
+        torch = _torch()
+        dev = f"cuda:{self.ctx.device}"
+        boxes = torch.empty((n, self.topk, 4), dtype=torch.int32, device=dev)
+        areas = torch.empty((n, self.topk), dtype=torch.int32, device=dev)
+        prev = self._cam_boxes
+
+        def inner():
+            if n:
+                self.set_cam_boxes(boxes, areas, frac)
+            return call()
+
+        try:
+            return self._with_cam(n, inner) + (boxes, areas)
+        finally:
+            if self._cam_out is None:  # the library dropped the boxes with the maps
+                self._cam_boxes = None
+            elif prev is not None:
+                self.set_cam_boxes(*prev)
+            else:
+                self.set_cam_boxes(None)
+
+    def classify_boxes(self, x, frac: float = 0.2):
+        """classify_cam(x) with the boxes: (scores, classes, maps, boxes [n, topk, 4], areas [n, topk]).  A convenience
+        built on classify_cam, with its two replans per call from off; for repeated calls set_cam_output and
+        set_cam_boxes once and use classify_into."""
+        return self._with_boxes(self._check_classify_in(x, False), lambda: self.classify(x), frac)
+
+    def classify_boxes_u8(self, x, frac: float = 0.2):
+        """classify_u8(x) with the class activation maps and their boxes."""
+        return self._with_boxes(self._check_classify_in(x, True), lambda: self.classify_u8(x), frac)
+
+    def classify_boxes_u8_list(self, lst, frac: float = 0.2):
+        """classify_u8_list(lst) with the class activation maps and their boxes."""
+        return self._with_boxes(self._check_list(lst), lambda: self.classify_u8_list(lst), frac)
 
     def _subjects(self, n: int) -> int:
         """The output rows of a classification of n images: n // views, n a multiple of views."""
