@@ -464,8 +464,13 @@ struct ResizeParams {
   int plane[4];
   float scale[4], shift[4];
 };
-void launch_resize_u8(const ResizeParams& p, hipStream_t s);
-// the same conversion over an image list (ore_image_list, resize_u8_list_kernel): every image has its own
+// The dense conversion under `filter` (an ore_resize_filter, known to the caller's checks), one thread per output
+// pixel.  Under ORE_FILTER_BILINEAR_AA the axes that shrink take the area-weighted filter of ore_resize_geom.h (every
+// such axis within RESIZE_AA_MAX_RATIO, checked by the caller) and the others resize_tap; a launch in which nothing
+// shrinks is the plain filter bit for bit and runs its kernel.  ORE_FILTER_BICUBIC and ORE_FILTER_BICUBIC_AA (every
+// axis within RESIZE_CUBIC_AA_MAX_RATIO, checked by the caller) take their taps and weights from there as well.
+void launch_resize_dense(const ResizeParams& p, int32_t filter, hipStream_t s);
+// the same conversion over an image list (ore_image_list, resize_list_kernel): every image has its own
 // base, size, row stride and geometry, packed by ore_image_list_set into a device table of these
 struct ResizeImage {
   const unsigned char* x;  // row 0, column 0, channel 0; any alignment
@@ -492,11 +497,6 @@ struct ResizeListParams {
                              // 1: the flag-reading instance; 2: the one that reads the orientation bits as well
   int taps;                  // ORE_FILTER_BICUBIC_AA: no column run of a descriptor is longer (1..RESIZE_AA_MAX_TAPS)
 };
-// the same two conversions under ORE_FILTER_BILINEAR_AA: axes that shrink take the area-weighted filter of
-// ore_resize_geom.h (every such axis within RESIZE_AA_MAX_RATIO, checked by the caller), the others resize_tap.
-// One thread per output pixel (resize_aa_pixel_kernel and its list form); a dense launch in which nothing
-// shrinks goes to launch_resize_u8.
-void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s);
 // the list conversions over NV12 frames (ore_image_list_create_nv12): a full-resolution Y plane and a
 // half-resolution interleaved UV plane, each with its own pitch; source pixel (r, j) is Y at (r, j) and the UV
 // pair at (r >> 1, j >> 1), converted to R, G, B bytes by ore_yuv.h under the list's matrix.  The result is
@@ -554,9 +554,6 @@ struct YuvListParams {
   int flips;               // as ResizeListParams::flips
   int taps;                // as ResizeListParams::taps
 };
-// the dense conversion under the cubic filters (ORE_FILTER_BICUBIC; aa: ORE_FILTER_BICUBIC_AA, every axis within
-// RESIZE_CUBIC_AA_MAX_RATIO, checked by the caller): resize_cubic_kernel, one thread per pixel
-void launch_resize_cubic_u8(const ResizeParams& p, bool aa, hipStream_t s);
 // The list conversions, one overload per descriptor format: the kernel of `filter` (an ore_resize_filter, known to
 // the caller's checks: bilinear, its antialiased form, or the cubic pair in their list forms) and of p.flips.
 void launch_resize_list(const ResizeListParams& p, int32_t filter, hipStream_t s);

@@ -1126,12 +1126,7 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
       if (m->in_resized) {  // the source images have their own size
         rsz.x = d_u8 + i0 * m->in_hs * m->in_ws * iv.dims[1];
         rsz.N = nc;
-        if (m->in_filter & ORE_FILTER_CUBIC_BIT)
-          launch_resize_cubic_u8(rsz, m->in_filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
-        else if (m->in_filter == ORE_FILTER_BILINEAR_AA)
-          launch_resize_aa_u8(rsz, ctx->stream);
-        else
-          launch_resize_u8(rsz, ctx->stream);
+        launch_resize_dense(rsz, m->in_filter, ctx->stream);
       } else {
         pre.x = d_u8 + i0 * in_img;
         pre.N = nc;

@@ -1200,12 +1200,7 @@ ore_status ore_preprocess_resize_u8_ex(ore_ctx* ctx, const uint8_t* x, int64_t n
   p.N = n;
   p.y_nstride = nstride_of(y);
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (filter & ORE_FILTER_CUBIC_BIT)
-    launch_resize_cubic_u8(p, filter == ORE_FILTER_BICUBIC_AA, ctx->stream);
-  else if (filter == ORE_FILTER_BILINEAR_AA)
-    launch_resize_aa_u8(p, ctx->stream);
-  else
-    launch_resize_u8(p, ctx->stream);
+  launch_resize_dense(p, filter, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

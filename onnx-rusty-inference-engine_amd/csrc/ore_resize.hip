@@ -7,14 +7,24 @@
 //
 // resize_u8_generic_kernel: one thread per output pixel, byte loads of the 2 x 2 x C taps from global memory,
 // C float stores (a wave writes 256 contiguous bytes per plane).  Any size, alignment and y stride.  It is the
-// only dense kernel (resize_u8_list_kernel below is the same arithmetic over an image list): an LDS-staged one (a workgroup staging a band's source rows with 16-byte loads, 4 pixels x C
-// channels per thread, float4 stores) ran 2.0x faster at 375 x 500 -> 224 but lost at 1080 x 1920 -> 224,
-// where this kernel already moves its bytes at the device-to-device copy rate, and was removed
-// (DESIGN.md 3.8b has the numbers).
+// only dense bilinear kernel: an LDS-staged one (a workgroup staging a band's source rows with 16-byte loads,
+// 4 pixels x C channels per thread, float4 stores) ran 2.0x faster at 375 x 500 -> 224 but lost at
+// 1080 x 1920 -> 224, where this kernel already moves its bytes at the device-to-device copy rate, and was
+// removed (DESIGN.md 3.8b has the numbers).
 // Image bases are 64-bit; offsets inside one image stay below 2^31 (sizes <= RESIZE_MAX, C <= 4).
-// The list kernels exist three times: over interleaved bytes, over NV12 planes converted on the fly, and over the
-// strided planes every YUV format reduces to (both further down).
+//
+// Everything else in this file is three parts that meet in two kernel templates:
+//  - the list skeleton (list_pixels): which output pixel a thread computes for which descriptor, line by line or, for
+//    a transposing descriptor, tile by tile through LDS;
+//  - the sources (SrcU8<C>, SrcNv12, SrcYuv<F>): where a row of an image starts and the C ints of its pixels, whether
+//    they are interleaved bytes, NV12 planes converted on the fly or the strided planes every YUV format reduces to;
+//  - the four filter bodies (bilinear_pixel, aa_pixel, cubic_pixel, cubic_aa_pixel) over a source and a ResizeGeom.
+// resize_list_kernel<FILTER, C, MODE> is the skeleton around a body over the descriptor's source, and
+// resize_dense_kernel<FILTER, C> the body over image i of a batch.  One body reads no source: the plain filter over
+// interleaved descriptors keeps its channel count at run time (bilinear_u8_pixel), one instance per mode.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/ore.h"
 #include "ore_kernels.h"
@@ -60,17 +70,18 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_generic_kernel(ResizePar
   }
 }
 
-// resize_u8_list_kernel: the same thread-per-pixel arithmetic over an image list (ore_image_list): image i of
-// the launch takes its base, size, row stride and geometry from table[i].  The table is a const __restrict__
-// kernel argument indexed by the block index alone, so the descriptor is one scalar load per workgroup and
-// lives in SGPRs; the taps, which the dense kernel computes once per thread, are computed per image (one
-// image per thread unless the list passes the grid's 65,535).  Every output pixel costs the same work
-// whatever its source size, so mixed sizes bring no load imbalance.
+// ---------------------------------------------------------------------------------------------------------
+// The list skeleton.  An image list (ore_image_list) is a device table of descriptors: image i of the launch takes
+// its base, size, row stride and geometry from table[i].  The table is a const __restrict__ kernel argument indexed
+// by the block index alone, so the descriptor is one scalar load per workgroup and lives in SGPRs; the taps, which
+// the dense bilinear kernel computes once per thread, are computed per image (one image per thread unless the list
+// passes the grid's 65,535).  Every output pixel costs the same work whatever its source size, so mixed sizes bring
+// no load imbalance.
 //
 // A descriptor's flip (ORE_IMAGE_FLIP_H, ore_image_list_set_ex) mirrors its window: output column q takes resized
 // column left + W - 1 - q, the store position stays q, so the image is the unflipped one with its columns
-// reversed, bit for bit.  The flag comes with the descriptor: wave-uniform, one scalar select per image.  Each
-// list kernel exists per ListMode: LIST_FLIP reads the flag; LIST_PLAIN does not, and is the one launched when no
+// reversed, bit for bit.  The flag comes with the descriptor: wave-uniform, one scalar select per image.  The list
+// kernel exists per ListMode: LIST_FLIP reads the flag; LIST_PLAIN does not, and is the one launched when no
 // descriptor of the list is flipped (ResizeListParams::flips), so that such a launch pays nothing for the feature.
 //
 // A descriptor's orientation (ore_image_list_set_oriented, EXIF codes 1..8) is three more bits of the same word
@@ -79,8 +90,8 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_generic_kernel(ResizePar
 // window of Hz x Wz = (H, W), or (W, H) under the transpose: (u, v) = (r, q) or (q, r), each reversed in its extent
 // where its bit is set.  The taps and every float operation stay those of the stored window, so the image is the
 // unoriented one of shape (Hz, Wz) permuted, bit for bit.  The bits are wave-uniform like the flag; a third instance
-// of each kernel (LIST_ORIENT) reads them, launched only for a list that holds a code other than 1 (or, inside a
-// capture, a list marked by a first oriented set), so the two instances above run what they ran.
+// (LIST_ORIENT) reads them, launched only for a list that holds a code other than 1 (or, inside a capture, a list
+// marked by a first oriented set), so that the two instances above pay nothing for them either.
 enum ListMode { LIST_PLAIN = 0, LIST_FLIP = 1, LIST_ORIENT = 2 };
 
 struct ListRQ {
@@ -144,22 +155,263 @@ __device__ __forceinline__ void list_image(int word, const P& p, int C, float* _
   __syncthreads();  // the tile is free for the next image of this block
 }
 
-// a list kernel's LIST_ORIENT form: every image of the block through list_image.  body(d, pp, yo, hw, px, r, q) is the
-// kernel's pixel: row r and column q of descriptor d's window, stored at yo[pp.plane[s] * hw + px]
-template <int T, class D, class P, class F>
-__device__ __forceinline__ void list_tiled(const D* __restrict__ table, const P& p, int C, F&& body) {
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const D d = table[i];
-    list_image<T>(d.flip, p, C, p.y + size_t(i) * size_t(p.y_nstride), [&](const P& pp, float* yo, int hw, int px, int r, int q) {
-      const ListRQ m = list_rq<LIST_ORIENT>(d.flip, p.H, p.W, r, q);
-      body(d, pp, yo, hw, px, m.r, m.q);
-    });
+// The skeleton of every list kernel, for workgroups of T threads: the images blockIdx.y walks, and for each the
+// output pixel of this thread.  body(d, pp, yo, hw, px, r, q) is the kernel's pixel: row r and column q of descriptor
+// d's window, stored at yo[pp.plane[s] * hw + px].  LIST_PLAIN and LIST_FLIP: thread t of block b has pixel b T + t of
+// every image; LIST_ORIENT: every image through list_image.
+template <int T, int MODE, class D, class P, class F>
+__device__ __forceinline__ void list_pixels(const D* __restrict__ table, const P& p, int C, F&& body) {
+  if constexpr (MODE == LIST_ORIENT) {
+    for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+      const D d = table[i];
+      list_image<T>(d.flip, p, C, p.y + size_t(i) * size_t(p.y_nstride), [&](const P& pp, float* yo, int hw, int px, int r, int q) {
+        const ListRQ m = list_rq<LIST_ORIENT>(d.flip, p.H, p.W, r, q);
+        body(d, pp, yo, hw, px, m.r, m.q);
+      });
+    }
+  } else {
+    const int px = blockIdx.x * T + threadIdx.x;
+    const int HW = p.H * p.W;
+    if (px >= HW) return;
+    const int r = px / p.W, q = px - r * p.W;
+    for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
+      const D d = table[i];
+      const ListRQ m = list_rq<MODE>(d.flip, p.H, p.W, r, q);
+      body(d, p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q);
+    }
   }
 }
 
-// one output pixel of descriptor d: row r and column q of its window, stored at yi[plane * HW] (yi: the pixel in plane 0)
-__device__ __forceinline__ void u8_list_pixel(const ResizeImage& d, const ResizeListParams& p, float* yi, int HW,
-                                              int r, int q) {
+// ---------------------------------------------------------------------------------------------------------
+// The sources.  A filter body reads an image through a source: where a row starts (at), the C ints of one of its
+// pixels (px) and of four neighbours at once (px4: interleaved bytes as C dwords), and through the image's geometry
+// (ResizeGeom), which a dense batch, the three descriptors and nothing else supply.  The three kinds of source differ
+// in nothing else; the antialiased bilinear filter, whose column runs are integer sums over grouped loads, has one
+// aa_row per kind beside them (further down).
+
+struct ResizeGeom {
+  int Hs, Ws, Rh, Rw, top, left;
+};
+
+template <class T>
+__device__ __forceinline__ ResizeGeom resize_geom(const T& t) {
+  ResizeGeom g;
+  g.Hs = t.Hs; g.Ws = t.Ws; g.Rh = t.Rh; g.Rw = t.Rw; g.top = t.top; g.left = t.left;
+  return g;
+}
+
+template <int C>
+struct SrcU8 {
+  const unsigned char* x;
+  int row;  // bytes between rows
+  using Row = const unsigned char*;
+  __device__ __forceinline__ Row at(int r) const { return x + size_t(r) * size_t(row); }
+  __device__ __forceinline__ void px(Row w, int j, int (&v)[C]) const {
+#pragma unroll
+    for (int s = 0; s < C; ++s) v[s] = int(w[j * C + s]);
+  }
+  // pixels j .. j + 3, all inside the row: their 4 C bytes as C dword loads at the pixels' own (any) alignment
+  __device__ __forceinline__ void px4(Row w, int j, int (&v)[4][C]) const {
+    unsigned d[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) __builtin_memcpy(&d[i], w + j * C + 4 * i, 4);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int s = 0; s < C; ++s) {
+        const int k = t * C + s;
+        v[t][s] = int((d[k >> 2] >> (8 * (k & 3))) & 0xffu);
+      }
+  }
+};
+
+// NV12 sources (ore_image_list_create_nv12): the pixel fetch replaced by fetch and convert.  Source pixel (r, j) is
+// the Y byte at (r, j) and the UV pair at (r >> 1, j >> 1), converted by ore_yuv.h to the R, G, B bytes an
+// interleaved source would hold with C = 3; everything after the fetch is the same code.  The six matrix integers
+// are kernel arguments (SGPRs).  The clamp makes the conversion non-linear, so it is done per tap and cannot leave
+// the sums; what depends on the chroma pair alone (yuv_chroma) is computed once per pair.
+
+// the chroma terms of pair c of UV row ur: two bytes at any alignment
+__device__ __forceinline__ YuvChroma nv12_chroma(const YuvMatrix& m, const unsigned char* __restrict__ ur, int c) {
+  unsigned short uv;
+  __builtin_memcpy(&uv, ur + 2 * c, 2);
+  return yuv_chroma(m, int(uv & 0xffu), int(uv >> 8));
+}
+
+// R, G, B of source pixel j of a row (yr: its Y bytes, ur: its UV pairs)
+__device__ __forceinline__ void nv12_pixel(const YuvMatrix& m, const unsigned char* __restrict__ yr,
+                                           const unsigned char* __restrict__ ur, int j, int (&rgb)[3]) {
+  yuv_rgb(m, int(yr[j]), nv12_chroma(m, ur, j >> 1), rgb);
+}
+
+struct SrcNv12 {
+  const unsigned char* y;
+  const unsigned char* uv;
+  int yrow, uvrow;
+  YuvMatrix m;
+  struct Row {
+    const unsigned char* yr;
+    const unsigned char* ur;
+  };
+  __device__ __forceinline__ Row at(int r) const {
+    return Row{y + size_t(r) * size_t(yrow), uv + size_t(r >> 1) * size_t(uvrow)};
+  }
+  __device__ __forceinline__ void px(const Row& w, int j, int (&v)[3]) const { nv12_pixel(m, w.yr, w.ur, j, v); }
+  __device__ __forceinline__ void px4(const Row& w, int j, int (&v)[4][3]) const {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) px(w, j + t, v[t]);
+  }
+};
+
+// YUV sources of any ore_yuv_format (ore_image_list_create_yuv): the NV12 fetch generalised to strided planes
+// (YuvImage, ore_kernels.h).  ore_image_list_set_yuv reduced the format to three bases, three pitches, a luma and
+// a chroma byte step and the two subsampling shifts, so nothing here reads the format.  Those fields leave four ways
+// to fetch a pixel (YuvFetch), and the source is templated on them: the way is chosen from the descriptor -- one
+// scalar load per workgroup, so the branch is wave-uniform -- in one place, yuv_fetch_as, and the body it selects is
+// branch-free, so that its loads issue together.  Where a filter makes the choice was measured per filter (DESIGN.md
+// 3.8f) and is kept: once per image around the whole pixel for the bilinear and cubic bodies, once per tap row for
+// the antialiased bilinear one.  (Choosing per pixel fetched instead, inside the fetch, put each of the four taps'
+// loads behind a wait of its own: 162 us against 109 us for 256 NV12 frames of 1080 x 1920 under the plain filter.)
+enum YuvFetch {
+  YUV_GREY = 0,    // u == null: Y alone, every chroma term zero
+  YUV_PLANES = 1,  // cstep == 1: Y, U and V by a byte load each
+  YUV_PAIRS = 2,   // cstep == 2: NV12's interleaved pairs, v == u + 1: Y by a byte, (U, V) by one two-byte load
+  YUV_PACKED = 3,  // ystep == 2: YUYV, a pixel's group Y0 U Y1 V is one dword
+};
+
+// the three rows source row r reads; u and v are null in a grey frame
+struct YuvRow {
+  const unsigned char* y;
+  const unsigned char* u;
+  const unsigned char* v;
+};
+
+__device__ __forceinline__ YuvRow yuv_row(const YuvImage& d, int r) {
+  YuvRow w;
+  w.y = d.y + size_t(r) * size_t(d.yrow);
+  w.u = nullptr; w.v = nullptr;
+  if (d.u) {
+    const size_t cr = size_t(r >> d.sy);
+    w.u = d.u + cr * size_t(d.urow);
+    w.v = d.v + cr * size_t(d.vrow);
+  }
+  return w;
+}
+
+// the chroma terms of sample c of a row of planes or pairs; the pair is two bytes at any alignment, as nv12_chroma
+template <int F>
+__device__ __forceinline__ YuvChroma yuv_sample(const YuvMatrix& m, const YuvRow& w, int c) {
+  static_assert(F == YUV_PLANES || F == YUV_PAIRS, "grey rows have no chroma, packed rows carry it beside the luma");
+  if (F == YUV_PAIRS) {
+    unsigned short uv;
+    __builtin_memcpy(&uv, w.u + 2 * c, 2);
+    return yuv_chroma(m, int(uv & 0xffu), int(uv >> 8));
+  }
+  return yuv_chroma(m, int(w.u[c]), int(w.v[c]));
+}
+
+template <int F>
+struct SrcYuv {
+  YuvImage d;
+  YuvMatrix m;
+  using Row = YuvRow;
+  __device__ __forceinline__ Row at(int r) const { return yuv_row(d, r); }
+  __device__ __forceinline__ void px(const Row& w, int j, int (&rgb)[3]) const {
+    if constexpr (F == YUV_PACKED) {
+      unsigned g;
+      __builtin_memcpy(&g, w.y + 4 * (j >> 1), 4);
+      yuv_rgb(m, int((g >> (16 * (j & 1))) & 0xffu), yuv_chroma(m, int((g >> 8) & 0xffu), int(g >> 24)), rgb);
+    } else if constexpr (F == YUV_GREY) {
+      yuv_rgb(m, int(w.y[j]), YuvChroma{0, 0, 0}, rgb);  // U = V = 128
+    } else {
+      yuv_rgb(m, int(w.y[j]), yuv_sample<F>(m, w, j >> d.sx), rgb);
+    }
+  }
+  __device__ __forceinline__ void px4(const Row& w, int j, int (&v)[4][3]) const {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) px(w, j + t, v[t]);
+  }
+};
+
+// a YUV descriptor whose way to fetch is not chosen yet: its rows start where every SrcYuv<F>'s do
+struct SrcYuvAny {
+  YuvImage d;
+  YuvMatrix m;
+  using Row = YuvRow;
+  __device__ __forceinline__ Row at(int r) const { return yuv_row(d, r); }
+};
+
+// f(the source to read through): the descriptor's SrcYuv<F>, or a source of the other kinds as it is
+template <class Fn>
+__device__ __forceinline__ void yuv_fetch_as(const SrcYuvAny& src, Fn&& f) {
+  const YuvImage& d = src.d;
+  switch (d.ystep != 1 ? YUV_PACKED : !d.u ? YUV_GREY : d.cstep == 2 ? YUV_PAIRS : YUV_PLANES) {
+    case YUV_PACKED: return f(SrcYuv<YUV_PACKED>{d, src.m});
+    case YUV_PAIRS: return f(SrcYuv<YUV_PAIRS>{d, src.m});
+    case YUV_PLANES: return f(SrcYuv<YUV_PLANES>{d, src.m});
+    default: return f(SrcYuv<YUV_GREY>{d, src.m});
+  }
+}
+
+template <class Src, class Fn>
+__device__ __forceinline__ void yuv_fetch_as(const Src& src, Fn&& f) {
+  f(src);
+}
+
+// the source of image i of a dense batch, and of a list descriptor under its list's parameters
+template <int C>
+__device__ __forceinline__ SrcU8<C> src_of(const ResizeParams& p, long long i) {
+  const int row = p.Ws * p.C;
+  return SrcU8<C>{p.x + size_t(i) * size_t(p.Hs) * size_t(row), row};
+}
+
+template <int C>
+__device__ __forceinline__ SrcU8<C> src_of(const ResizeImage& d, const ResizeListParams&) {
+  return SrcU8<C>{d.x, d.row};
+}
+
+template <int C>
+__device__ __forceinline__ SrcNv12 src_of(const Nv12Image& d, const Nv12ListParams& p) {
+  static_assert(C == 3, "an NV12 frame converts to three channels");
+  return SrcNv12{d.y, d.uv, d.yrow, d.uvrow, p.m};
+}
+
+template <int C>
+__device__ __forceinline__ SrcYuvAny src_of(const YuvImage& d, const YuvListParams& p) {
+  static_assert(C == 3, "a YUV frame converts to three channels");
+  return SrcYuvAny{d, p.m};
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// ORE_FILTER_BILINEAR over a source: the arithmetic at the top of the file.  One output pixel: row r and column q of
+// the window, stored at yi[plane * HW] (yi: the pixel in plane 0).  A YUV descriptor's way to fetch is chosen once per
+// image around the four fetches alone; the taps before them and the lerps and stores after them exist once.
+template <int C, class Src, class P>
+__device__ __forceinline__ void bilinear_pixel(const Src& src, const ResizeGeom& g, const P& p, float* yi, int HW, int r, int q) {
+  const ResizeTap ty = resize_tap(g.Hs, g.Rh, g.top + r);
+  const ResizeTap tx = resize_tap(g.Ws, g.Rw, g.left + q);
+  const typename Src::Row w0 = src.at(ty.i0), w1 = src.at(ty.i1);
+  int a[C], b[C], c[C], e[C];
+  yuv_fetch_as(src, [&](const auto& s) {
+    s.px(w0, tx.i0, a);
+    s.px(w0, tx.i1, b);
+    s.px(w1, tx.i0, c);
+    s.px(w1, tx.i1, e);
+  });
+#pragma unroll
+  for (int s = 0; s < C; ++s) {
+    const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
+    const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
+    yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
+  }
+}
+
+// The same pixel of an interleaved descriptor with the channel count at run time (p.C), each channel loaded and
+// stored in turn: the list kernel's one bilinear instance per mode for C = 1..4 (C = 0 in its template arguments).
+// A body over SrcU8<C> loads all 4 C bytes before the first store, which is another schedule -- as declaring yi
+// __restrict__ is -- and wants a measurement of its own.
+__device__ __forceinline__ void bilinear_u8_pixel(const ResizeImage& d, const ResizeListParams& p, float* yi, int HW,
+                                                  int r, int q) {
   const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
   const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
   const size_t r0 = size_t(ty.i0) * size_t(d.row), r1 = size_t(ty.i1) * size_t(d.row);
@@ -172,35 +424,6 @@ __device__ __forceinline__ void u8_list_pixel(const ResizeImage& d, const Resize
   }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(RS_THREADS) void resize_u8_list_kernel(const ResizeImage* __restrict__ table,
-                                                                    ResizeListParams p) {
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<RS_THREADS>(table, p, p.C, [](const ResizeImage& d, const ResizeListParams& pp, float* yo, int hw, int px, int r, int q) {
-      u8_list_pixel(d, pp, yo + px, hw, r, q);
-    });
-    return;
-  }
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {  // u8_list_pixel, kept inline: these two instances' code is the parent's
-    const ResizeImage d = table[i];
-    const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_rq<MODE>(d.flip, p.H, p.W, r, q).q);
-    const size_t r0 = size_t(ty.i0) * size_t(d.row), r1 = size_t(ty.i1) * size_t(d.row);
-    const size_t c0 = size_t(tx.i0) * p.C, c1 = size_t(tx.i1) * p.C;
-    const unsigned char* xi = d.x;
-    float* yi = p.y + size_t(i) * size_t(p.y_nstride) + px;
-    for (int s = 0; s < p.C; ++s) {
-      const float up = lerp_rn(float(xi[r0 + c0 + s]), float(xi[r0 + c1 + s]), tx.t);
-      const float lo = lerp_rn(float(xi[r1 + c0 + s]), float(xi[r1 + c1 + s]), tx.t);
-      yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // ORE_FILTER_BILINEAR_AA (include/ore.h has the arithmetic): an axis that shrinks sums every source sample of
 // the stretched triangle (resize_aa_span / resize_aa_weight), the other axis keeps resize_tap.  Per output
@@ -210,17 +433,12 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_list_kernel(const Resize
 // correctly rounded fdiv); they are the only place the ISA holds v_fma.  A run of column taps is read four
 // taps (4 C bytes) at a time as C dwords at the run's own alignment, the rest by bytes.
 //
-// One device body (aa_pixel), dense and list kernels over it, templated on the channel count so that the
-// per-channel sums live in registers: one thread per output pixel walks its taps_y x taps_x window in global
-// memory, any size, alignment, row stride and y stride, 64-bit image bases only.  A band kernel (a workgroup
-// computing the horizontal sums of a band's source rows once into LDS, then the vertical chains from LDS) gave
-// the same bits but was slower at both bench geometries and was removed (DESIGN.md 3.8d has the numbers).
-
-struct AaImage {
-  const unsigned char* x;
-  int Hs, Ws, row;  // row: bytes between rows
-  int Rh, Rw, top, left;
-};
+// One device body (aa_pixel), templated on the channel count so that the per-channel sums live in registers: one
+// thread per output pixel walks its taps_y x taps_x window in global memory, any size, alignment, row stride and y
+// stride, 64-bit image bases only.  What it asks of a source is one tap row's column sums: aa_row, one overload per
+// kind of source, each with the grouped loads its layout allows.  A band kernel (a workgroup computing the horizontal
+// sums of a band's source rows once into LDS, then the vertical chains from LDS) gave the same bits but was slower at
+// both bench geometries and was removed (DESIGN.md 3.8d has the numbers).
 
 __device__ __forceinline__ float macc_rn(float acc, float v, float g) {
 #pragma clang fp contract(off)
@@ -249,10 +467,11 @@ __device__ __forceinline__ AaAxis aa_axis(bool shrinks, int S, int D, int o) {
   return a;
 }
 
-// g of one source row (xr: its first byte) for resized column ox
+// g of source row r of interleaved bytes for resized column ox
 template <int C>
-__device__ __forceinline__ void aa_row(const unsigned char* __restrict__ xr, bool sx, const AaAxis& ax, int Ws, int Rw,
-                                       int ox, float (&g)[C]) {
+__device__ __forceinline__ void aa_row(const SrcU8<C>& src, const ResizeGeom& d, int r, bool sx, const AaAxis& ax, int ox,
+                                       float (&g)[C]) {
+  const unsigned char* __restrict__ xr = src.at(r);
   if (sx) {
     int acc[C];
 #pragma unroll
@@ -261,21 +480,21 @@ __device__ __forceinline__ void aa_row(const unsigned char* __restrict__ xr, boo
     int j = 0;
     // four taps at a time: their 4 C bytes as C dword loads at the window's own (any) alignment, all inside it
     for (; j + 4 <= ax.n; j += 4) {
-      unsigned d[C];
+      unsigned dw[C];
 #pragma unroll
-      for (int i = 0; i < C; ++i) __builtin_memcpy(&d[i], pp + j * C + 4 * i, 4);
+      for (int i = 0; i < C; ++i) __builtin_memcpy(&dw[i], pp + j * C + 4 * i, 4);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const int u = resize_aa_weight(Ws, Rw, ox, ax.first + j + t);
+        const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j + t);
 #pragma unroll
         for (int s = 0; s < C; ++s) {
           const int k = t * C + s;
-          acc[s] += __mul24(u, int((d[k >> 2] >> (8 * (k & 3))) & 0xffu));
+          acc[s] += __mul24(u, int((dw[k >> 2] >> (8 * (k & 3))) & 0xffu));
         }
       }
     }
     for (; j < ax.n; ++j) {
-      const int u = resize_aa_weight(Ws, Rw, ox, ax.first + j);
+      const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j);
 #pragma unroll
       for (int s = 0; s < C; ++s) acc[s] += __mul24(u, int(pp[j * C + s]));
     }
@@ -298,49 +517,13 @@ __device__ __forceinline__ void aa_store(const P& p, float* __restrict__ yi, int
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// NV12 sources (ore_image_list_create_nv12): the pixel fetch of the kernels above replaced by fetch and convert.
-// Source pixel (r, j) is the Y byte at (r, j) and the UV pair at (r >> 1, j >> 1), converted by ore_yuv.h to the
-// R, G, B bytes the interleaved kernels would read with C = 3; everything after the fetch is their code.  The
-// six matrix integers are kernel arguments (SGPRs).  The clamp makes the conversion non-linear, so it is done
-// per tap and cannot leave the sums; what depends on the chroma pair alone (yuv_chroma) is computed once per pair.
-
-struct AaNv12 {
-  const unsigned char* y;
-  const unsigned char* uv;
-  int Hs, Ws, yrow, uvrow;
-  int Rh, Rw, top, left;
-  YuvMatrix m;
-};
-
-__device__ __forceinline__ AaNv12 aa_image(const Nv12Image& t, const YuvMatrix& m) {
-  AaNv12 d;
-  d.y = t.y; d.uv = t.uv;
-  d.Hs = t.Hs; d.Ws = t.Ws; d.yrow = t.yrow; d.uvrow = t.uvrow;
-  d.Rh = t.Rh; d.Rw = t.Rw; d.top = t.top; d.left = t.left;
-  d.m = m;
-  return d;
-}
-
-// the chroma terms of pair c of UV row ur: two bytes at any alignment
-__device__ __forceinline__ YuvChroma nv12_chroma(const YuvMatrix& m, const unsigned char* __restrict__ ur, int c) {
-  unsigned short uv;
-  __builtin_memcpy(&uv, ur + 2 * c, 2);
-  return yuv_chroma(m, int(uv & 0xffu), int(uv >> 8));
-}
-
-// R, G, B of source pixel j of a row (yr: its Y bytes, ur: its UV pairs)
-__device__ __forceinline__ void nv12_pixel(const YuvMatrix& m, const unsigned char* __restrict__ yr,
-                                           const unsigned char* __restrict__ ur, int j, int (&rgb)[3]) {
-  yuv_rgb(m, int(yr[j]), nv12_chroma(m, ur, j >> 1), rgb);
-}
-
-// g of source row r for resized column ox: aa_row over converted pixels.  A run of column taps reads its Y
-// bytes four taps at a time as one dword at the run's own alignment, and the two chroma pairs those four taps
+// g of NV12 source row r for resized column ox: the row above over converted pixels.  A run of column taps reads its
+// Y bytes four taps at a time as one dword at the run's own alignment, and the two chroma pairs those four taps
 // share -- three where the run starts on an odd column, the first and the last then serving one tap each.
-__device__ __forceinline__ void aa_row_nv12(const AaNv12& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[3]) {
-  const unsigned char* yr = d.y + size_t(r) * size_t(d.yrow);
-  const unsigned char* ur = d.uv + size_t(r >> 1) * size_t(d.uvrow);
+__device__ __forceinline__ void aa_row(const SrcNv12& src, const ResizeGeom& d, int r, bool sx, const AaAxis& ax, int ox,
+                                       float (&g)[3]) {
+  const unsigned char* yr = src.y + size_t(r) * size_t(src.yrow);
+  const unsigned char* ur = src.uv + size_t(r >> 1) * size_t(src.uvrow);
   if (sx) {
     int acc[3] = {0, 0, 0};
     const unsigned char* pp = yr + ax.first;
@@ -350,15 +533,15 @@ __device__ __forceinline__ void aa_row_nv12(const AaNv12& d, int r, bool sx, con
       unsigned yy;
       __builtin_memcpy(&yy, pp + j, 4);
       const int c0 = (ax.first + j) >> 1;
-      const YuvChroma k0 = nv12_chroma(d.m, ur, c0), k1 = nv12_chroma(d.m, ur, c0 + 1);
+      const YuvChroma k0 = nv12_chroma(src.m, ur, c0), k1 = nv12_chroma(src.m, ur, c0 + 1);
       // tap t takes pair (odd + t) >> 1; the third pair exists where it is needed: tap 3 of an odd start is inside the row
-      const YuvChroma k2 = odd ? nv12_chroma(d.m, ur, c0 + 2) : k1;
+      const YuvChroma k2 = odd ? nv12_chroma(src.m, ur, c0 + 2) : k1;
       const YuvChroma kt[4] = {k0, odd ? k1 : k0, k1, k2};
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j + t);
         int rgb[3];
-        yuv_rgb(d.m, int((yy >> (8 * t)) & 0xffu), kt[t], rgb);
+        yuv_rgb(src.m, int((yy >> (8 * t)) & 0xffu), kt[t], rgb);
 #pragma unroll
         for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
       }
@@ -366,7 +549,7 @@ __device__ __forceinline__ void aa_row_nv12(const AaNv12& d, int r, bool sx, con
     for (; j < ax.n; ++j) {
       const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j);
       int rgb[3];
-      nv12_pixel(d.m, yr, ur, ax.first + j, rgb);
+      nv12_pixel(src.m, yr, ur, ax.first + j, rgb);
 #pragma unroll
       for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
     }
@@ -374,115 +557,30 @@ __device__ __forceinline__ void aa_row_nv12(const AaNv12& d, int r, bool sx, con
     for (int s = 0; s < 3; ++s) g[s] = float(acc[s]);
   } else {
     int a[3], b[3];
-    nv12_pixel(d.m, yr, ur, ax.first, a);
-    nv12_pixel(d.m, yr, ur, ax.i1, b);
+    nv12_pixel(src.m, yr, ur, ax.first, a);
+    nv12_pixel(src.m, yr, ur, ax.i1, b);
 #pragma unroll
     for (int s = 0; s < 3; ++s) g[s] = lerp_rn(float(a[s]), float(b[s]), ax.t);
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// YUV sources of any ore_yuv_format (ore_image_list_create_yuv): the NV12 fetch above generalised to strided planes
-// (YuvImage, ore_kernels.h).  ore_image_list_set_yuv reduced the format to three bases, three pitches, a luma and
-// a chroma byte step and the two subsampling shifts, so nothing here reads the format.  Those fields leave four ways
-// to fetch a pixel (YuvFetch), and the code is templated on them: the way is chosen ONCE per image (bilinear) or per
-// tap row (antialiased) from the descriptor -- one scalar load per workgroup, so the branch is wave-uniform -- and
-// the body it selects is branch-free, so that its loads issue together.  (Choosing per pixel instead, inside the
-// fetch, put each of the four taps' loads behind a wait of its own: 162 us against 109 us for 256 NV12 frames of
-// 1080 x 1920 under the plain filter)
-enum YuvFetch {
-  YUV_GREY = 0,    // u == null: Y alone, every chroma term zero
-  YUV_PLANES = 1,  // cstep == 1: Y, U and V by a byte load each
-  YUV_PAIRS = 2,   // cstep == 2: NV12's interleaved pairs, v == u + 1: Y by a byte, (U, V) by one two-byte load
-  YUV_PACKED = 3,  // ystep == 2: YUYV, a pixel's group Y0 U Y1 V is one dword
-};
-
-template <class D>
-__device__ __forceinline__ int yuv_fetch(const D& d) {
-  return d.ystep != 1 ? YUV_PACKED : !d.u ? YUV_GREY : d.cstep == 2 ? YUV_PAIRS : YUV_PLANES;
-}
-
-struct AaYuv {
-  const unsigned char* y;
-  const unsigned char* u;
-  const unsigned char* v;
-  int Hs, Ws, yrow, urow, vrow;
-  int ystep, cstep, sx, sy;
-  int Rh, Rw, top, left;
-  YuvMatrix m;
-};
-
-__device__ __forceinline__ AaYuv aa_image(const YuvImage& t, const YuvMatrix& m) {
-  AaYuv d;
-  d.y = t.y; d.u = t.u; d.v = t.v;
-  d.Hs = t.Hs; d.Ws = t.Ws; d.yrow = t.yrow; d.urow = t.urow; d.vrow = t.vrow;
-  d.ystep = t.ystep; d.cstep = t.cstep; d.sx = t.sx; d.sy = t.sy;
-  d.Rh = t.Rh; d.Rw = t.Rw; d.top = t.top; d.left = t.left;
-  d.m = m;
-  return d;
-}
-
-// the three rows source row r reads; u and v are null in a grey frame
-struct YuvRow {
-  const unsigned char* y;
-  const unsigned char* u;
-  const unsigned char* v;
-};
-
-template <class D>
-__device__ __forceinline__ YuvRow yuv_row(const D& d, int r) {
-  YuvRow w;
-  w.y = d.y + size_t(r) * size_t(d.yrow);
-  w.u = nullptr; w.v = nullptr;
-  if (d.u) {
-    const size_t cr = size_t(r >> d.sy);
-    w.u = d.u + cr * size_t(d.urow);
-    w.v = d.v + cr * size_t(d.vrow);
-  }
-  return w;
-}
-
-// the chroma terms of sample c of a row of planes or pairs; the pair is two bytes at any alignment, as nv12_chroma
-template <int F>
-__device__ __forceinline__ YuvChroma yuv_sample(const YuvMatrix& m, const YuvRow& w, int c) {
-  static_assert(F == YUV_PLANES || F == YUV_PAIRS, "grey rows have no chroma, packed rows carry it beside the luma");
-  if (F == YUV_PAIRS) {
-    unsigned short uv;
-    __builtin_memcpy(&uv, w.u + 2 * c, 2);
-    return yuv_chroma(m, int(uv & 0xffu), int(uv >> 8));
-  }
-  return yuv_chroma(m, int(w.u[c]), int(w.v[c]));
-}
-
-// R, G, B of source pixel j of a row
-template <int F, class D>
-__device__ __forceinline__ void yuv_pixel(const D& d, const YuvMatrix& m, const YuvRow& w, int j, int (&rgb)[3]) {
-  if constexpr (F == YUV_PACKED) {
-    unsigned g;
-    __builtin_memcpy(&g, w.y + 4 * (j >> 1), 4);
-    yuv_rgb(m, int((g >> (16 * (j & 1))) & 0xffu), yuv_chroma(m, int((g >> 8) & 0xffu), int(g >> 24)), rgb);
-  } else if constexpr (F == YUV_GREY) {
-    yuv_rgb(m, int(w.y[j]), YuvChroma{0, 0, 0}, rgb);  // U = V = 128
-  } else {
-    yuv_rgb(m, int(w.y[j]), yuv_sample<F>(m, w, j >> d.sx), rgb);
-  }
-}
-
-__device__ __forceinline__ void yuv_tap(const AaYuv& d, int ox, int col, int Y, const YuvChroma& k, int (&acc)[3]) {
+__device__ __forceinline__ void yuv_tap(const YuvMatrix& m, const ResizeGeom& d, int ox, int col, int Y, const YuvChroma& k,
+                                        int (&acc)[3]) {
   const int u = resize_aa_weight(d.Ws, d.Rw, ox, col);
   int rgb[3];
-  yuv_rgb(d.m, Y, k, rgb);
+  yuv_rgb(m, Y, k, rgb);
 #pragma unroll
   for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
 }
 
-// The groups of four taps of a run over planes whose luma step is 1 (every format but YUYV), as aa_row_nv12 does
+// The groups of four taps of a run over planes whose luma step is 1 (every format but YUYV), as the NV12 row does
 // them: the four Y bytes as one dword at the run's own alignment, and each chroma sample those taps touch fetched
 // and multiplied out once -- four samples under SX = 0; two under SX = 1, three where the run starts on an odd
 // column; one under SX = 2, two where it does not start on a multiple of four; none for grey (SX = -1).  j steps
 // by four, so every group of the run starts on the same phase.  Returns the taps done; the rest go one by one.
 template <int F, int SX>
-__device__ __forceinline__ int aa_run_planar(const AaYuv& d, const YuvRow& w, const AaAxis& ax, int ox, int (&acc)[3]) {
+__device__ __forceinline__ int aa_run_planar(const YuvMatrix& m, const ResizeGeom& d, const YuvRow& w, const AaAxis& ax, int ox,
+                                             int (&acc)[3]) {
   static_assert((F == YUV_GREY) == (SX < 0), "SX = -1 stands for no chroma");
   constexpr int S = SX < 0 ? 0 : SX;
   constexpr int NK = SX < 0 ? 1 : ((2 + (1 << S)) >> S) + 1;
@@ -497,17 +595,17 @@ __device__ __forceinline__ int aa_run_planar(const AaYuv& d, const YuvRow& w, co
       k[0] = YuvChroma{0, 0, 0};
     } else {
       const int c0 = col >> S;
-      k[0] = yuv_sample<F>(d.m, w, c0);
+      k[0] = yuv_sample<F>(m, w, c0);
       // sample c0 + s exists where a tap of the group needs it: the last tap takes sample c0 + ((ph + 3) >> S)
 #pragma unroll
-      for (int s = 1; s < NK; ++s) k[s] = ((ph + 3) >> S) >= s ? yuv_sample<F>(d.m, w, c0 + s) : k[s - 1];
+      for (int s = 1; s < NK; ++s) k[s] = ((ph + 3) >> S) >= s ? yuv_sample<F>(m, w, c0 + s) : k[s - 1];
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       constexpr int last = NK - 1;
       const int lo = t >> S, hi = lo + 1 < last ? lo + 1 : last;  // tap t takes sample (ph + t) >> S: lo or the next
       const YuvChroma kt = ((ph + t) >> S) != lo ? k[hi] : k[lo < last ? lo : last];
-      yuv_tap(d, ox, col + t, int((yy >> (8 * t)) & 0xffu), kt, acc);
+      yuv_tap(m, d, ox, col + t, int((yy >> (8 * t)) & 0xffu), kt, acc);
     }
   }
   return j;
@@ -516,7 +614,8 @@ __device__ __forceinline__ int aa_run_planar(const AaYuv& d, const YuvRow& w, co
 // The same groups of a YUYV row (luma step 2): row bytes are groups Y0 U Y1 V of two columns.  The two groups of
 // four taps from an even column carry their four lumas and both chroma pairs: two dword loads and nothing else; from
 // an odd column the taps reach into a third group, which is inside the row because its first column is a tap.
-__device__ __forceinline__ int aa_run_yuyv(const AaYuv& d, const YuvRow& w, const AaAxis& ax, int ox, int (&acc)[3]) {
+__device__ __forceinline__ int aa_run_yuyv(const YuvMatrix& m, const ResizeGeom& d, const YuvRow& w, const AaAxis& ax, int ox,
+                                           int (&acc)[3]) {
   const bool odd = (ax.first & 1) != 0;
   int j = 0;
   for (; j + 4 <= ax.n; j += 4) {
@@ -527,32 +626,33 @@ __device__ __forceinline__ int aa_run_yuyv(const AaYuv& d, const YuvRow& w, cons
     __builtin_memcpy(&g1, gp + 4, 4);
     g2 = g1;
     if (odd) __builtin_memcpy(&g2, gp + 8, 4);
-    const YuvChroma k0 = yuv_chroma(d.m, int((g0 >> 8) & 0xffu), int(g0 >> 24));
-    const YuvChroma k1 = yuv_chroma(d.m, int((g1 >> 8) & 0xffu), int(g1 >> 24));
-    const YuvChroma k2 = odd ? yuv_chroma(d.m, int((g2 >> 8) & 0xffu), int(g2 >> 24)) : k1;
+    const YuvChroma k0 = yuv_chroma(m, int((g0 >> 8) & 0xffu), int(g0 >> 24));
+    const YuvChroma k1 = yuv_chroma(m, int((g1 >> 8) & 0xffu), int(g1 >> 24));
+    const YuvChroma k2 = odd ? yuv_chroma(m, int((g2 >> 8) & 0xffu), int(g2 >> 24)) : k1;
     const YuvChroma kt[4] = {k0, odd ? k1 : k0, k1, k2};
     const unsigned yt[4] = {odd ? g0 >> 16 : g0, odd ? g1 : g0 >> 16, odd ? g1 >> 16 : g1, odd ? g2 : g1 >> 16};
 #pragma unroll
-    for (int t = 0; t < 4; ++t) yuv_tap(d, ox, col + t, int(yt[t] & 0xffu), kt[t], acc);
+    for (int t = 0; t < 4; ++t) yuv_tap(m, d, ox, col + t, int(yt[t] & 0xffu), kt[t], acc);
   }
   return j;
 }
 
 // g of source row r for resized column ox under one way to fetch and, for planes, one horizontal chroma shift
-template <int F, int SX>
-__device__ __forceinline__ void aa_row_yuv_as(const AaYuv& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[3]) {
-  const YuvRow w = yuv_row(d, r);
+template <int SX, int F>
+__device__ __forceinline__ void aa_row_yuv_as(const SrcYuv<F>& src, const ResizeGeom& d, int r, bool sx, const AaAxis& ax, int ox,
+                                              float (&g)[3]) {
+  const YuvRow w = src.at(r);
   if (sx) {
     int acc[3] = {0, 0, 0};
     int j;
     if constexpr (F == YUV_PACKED)
-      j = aa_run_yuyv(d, w, ax, ox, acc);
+      j = aa_run_yuyv(src.m, d, w, ax, ox, acc);
     else
-      j = aa_run_planar<F, SX>(d, w, ax, ox, acc);
+      j = aa_run_planar<F, SX>(src.m, d, w, ax, ox, acc);
     for (; j < ax.n; ++j) {
       const int u = resize_aa_weight(d.Ws, d.Rw, ox, ax.first + j);
       int rgb[3];
-      yuv_pixel<F>(d, d.m, w, ax.first + j, rgb);
+      src.px(w, ax.first + j, rgb);
 #pragma unroll
       for (int s = 0; s < 3; ++s) acc[s] += __mul24(u, rgb[s]);
     }
@@ -560,59 +660,48 @@ __device__ __forceinline__ void aa_row_yuv_as(const AaYuv& d, int r, bool sx, co
     for (int s = 0; s < 3; ++s) g[s] = float(acc[s]);
   } else {
     int a[3], b[3];
-    yuv_pixel<F>(d, d.m, w, ax.first, a);
-    yuv_pixel<F>(d, d.m, w, ax.i1, b);
+    src.px(w, ax.first, a);
+    src.px(w, ax.i1, b);
 #pragma unroll
     for (int s = 0; s < 3; ++s) g[s] = lerp_rn(float(a[s]), float(b[s]), ax.t);
   }
 }
 
-// g of source row r for resized column ox: aa_row over converted pixels, by the descriptor's way to fetch
-__device__ __forceinline__ void aa_row_yuv(const AaYuv& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[3]) {
-  switch (yuv_fetch(d)) {
-    case YUV_PACKED: return aa_row_yuv_as<YUV_PACKED, 1>(d, r, sx, ax, ox, g);
-    case YUV_GREY: return aa_row_yuv_as<YUV_GREY, -1>(d, r, sx, ax, ox, g);
-    case YUV_PAIRS: return aa_row_yuv_as<YUV_PAIRS, 1>(d, r, sx, ax, ox, g);  // pairs are NV12: sx = 1
-    default: break;
-  }
-  if (d.sx == 0) return aa_row_yuv_as<YUV_PLANES, 0>(d, r, sx, ax, ox, g);
-  if (d.sx == 1) return aa_row_yuv_as<YUV_PLANES, 1>(d, r, sx, ax, ox, g);
-  aa_row_yuv_as<YUV_PLANES, 2>(d, r, sx, ax, ox, g);
+// g of YUV source row r: the row above over converted pixels, by the chroma shift of the source's way to fetch
+template <int F>
+__device__ __forceinline__ void aa_row(const SrcYuv<F>& src, const ResizeGeom& d, int r, bool sx, const AaAxis& ax, int ox,
+                                       float (&g)[3]) {
+  if constexpr (F == YUV_GREY)
+    aa_row_yuv_as<-1>(src, d, r, sx, ax, ox, g);
+  else if constexpr (F != YUV_PLANES)
+    aa_row_yuv_as<1>(src, d, r, sx, ax, ox, g);  // YUYV, and pairs are NV12: sx = 1
+  else if (src.d.sx == 0)
+    aa_row_yuv_as<0>(src, d, r, sx, ax, ox, g);
+  else if (src.d.sx == 1)
+    aa_row_yuv_as<1>(src, d, r, sx, ax, ox, g);
+  else
+    aa_row_yuv_as<2>(src, d, r, sx, ax, ox, g);
 }
 
-// g of source row r of an image, by the kind of its source
-template <int C>
-__device__ __forceinline__ void aa_src_row(const AaImage& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[C]) {
-  aa_row<C>(d.x + size_t(r) * size_t(d.row), sx, ax, d.Ws, d.Rw, ox, g);
-}
-
-template <int C>
-__device__ __forceinline__ void aa_src_row(const AaYuv& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[C]) {
-  static_assert(C == 3, "a YUV frame converts to three channels");
-  aa_row_yuv(d, r, sx, ax, ox, g);
-}
-
-template <int C>
-__device__ __forceinline__ void aa_src_row(const AaNv12& d, int r, bool sx, const AaAxis& ax, int ox, float (&g)[C]) {
-  static_assert(C == 3, "an NV12 frame converts to three channels");
-  aa_row_nv12(d, r, sx, ax, ox, g);
-}
-
-// output pixel px of image d (AaImage: interleaved bytes; AaNv12) from global memory: row r and column q of the
-// window (not px's row and column where a list descriptor is flipped or oriented)
-template <int C, class D, class P>
-__device__ __forceinline__ void aa_pixel(const D& d, const P& p, float* __restrict__ yi, int HW, int px, int r, int q) {
+// output pixel px of an image from global memory: row r and column q of the window (not px's row and column where a
+// list descriptor is flipped or oriented)
+template <int C, class Src, class P>
+__device__ __forceinline__ void aa_pixel(const Src& src, const ResizeGeom& d, const P& p, float* __restrict__ yi, int HW, int px,
+                                         int r, int q) {
   const bool sx = d.Ws > d.Rw, sy = d.Hs > d.Rh;
   const int oy = d.top + r, ox = d.left + q;
   const AaAxis ax = aa_axis(sx, d.Ws, d.Rw, ox);
   const AaAxis ay = aa_axis(sy, d.Hs, d.Rh, oy);
+  const auto row = [&](int sr, float (&g)[C]) {  // a YUV descriptor's way to fetch is chosen here, per tap row
+    yuv_fetch_as(src, [&](const auto& s) { aa_row(s, d, sr, sx, ax, ox, g); });
+  };
   float w[C];
   if (sy) {
 #pragma unroll
     for (int s = 0; s < C; ++s) w[s] = 0.f;
     for (int i = 0; i < ay.n; ++i) {
       float g[C];
-      aa_src_row<C>(d, ay.first + i, sx, ax, ox, g);
+      row(ay.first + i, g);
       const float v = float(resize_aa_weight(d.Hs, d.Rh, oy, ay.first + i));
 #pragma unroll
       for (int s = 0; s < C; ++s) w[s] = macc_rn(w[s], v, g[s]);
@@ -622,233 +711,18 @@ __device__ __forceinline__ void aa_pixel(const D& d, const P& p, float* __restri
     for (int s = 0; s < C; ++s) w[s] = w[s] / vf;
   } else {
     float g0[C], g1[C];
-    aa_src_row<C>(d, ay.first, sx, ax, ox, g0);
-    aa_src_row<C>(d, ay.i1, sx, ax, ox, g1);
+    row(ay.first, g0);
+    row(ay.i1, g1);
 #pragma unroll
     for (int s = 0; s < C; ++s) w[s] = lerp_rn(g0[s], g1[s], ay.t);
   }
   aa_store<C>(p, yi, HW, px, sx, ax.sum, w);
 }
 
-__device__ __forceinline__ AaImage aa_image(const ResizeParams& p, long long i) {
-  AaImage d;
-  d.row = p.Ws * p.C;
-  d.x = p.x + size_t(i) * size_t(p.Hs) * size_t(d.row);
-  d.Hs = p.Hs; d.Ws = p.Ws;
-  d.Rh = p.Rh; d.Rw = p.Rw; d.top = p.top; d.left = p.left;
-  return d;
-}
-
-__device__ __forceinline__ AaImage aa_image(const ResizeImage& t) {
-  AaImage d;
-  d.x = t.x;
-  d.Hs = t.Hs; d.Ws = t.Ws; d.row = t.row;
-  d.Rh = t.Rh; d.Rw = t.Rw; d.top = t.top; d.left = t.left;
-  return d;
-}
-
-template <int C>
-__global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_kernel(ResizeParams p) {
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
-    aa_pixel<C>(aa_image(p, i), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, q);
-}
-
-// the list descriptor is one scalar load per workgroup, as in resize_u8_list_kernel
-template <int C, int MODE>
-__global__ __launch_bounds__(RS_THREADS) void resize_aa_pixel_list_kernel(const ResizeImage* __restrict__ table,
-                                                                          ResizeListParams p) {
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<RS_THREADS>(table, p, C, [&](const ResizeImage& d, const ResizeListParams& pp, float* yo, int hw, int px, int r, int q) {
-      aa_pixel<C>(aa_image(d), pp, yo, hw, px, r, q);
-    });
-    return;
-  }
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const ListRQ m = list_rq<MODE>(table[i].flip, p.H, p.W, r, q);
-    aa_pixel<C>(aa_image(table[i]), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q);
-  }
-}
-
-// the NV12 list kernels: resize_u8_list_kernel and resize_aa_pixel_list_kernel<3> over converted pixels; the
-// descriptor is one scalar load per workgroup as there
-// one output pixel of descriptor d, as u8_list_pixel
-__device__ __forceinline__ void nv12_list_pixel(const Nv12Image& d, const Nv12ListParams& p, float* yi, int HW,
-                                                int r, int q) {
-  const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-  const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
-  const unsigned char* y0 = d.y + size_t(ty.i0) * size_t(d.yrow);
-  const unsigned char* y1 = d.y + size_t(ty.i1) * size_t(d.yrow);
-  const unsigned char* u0 = d.uv + size_t(ty.i0 >> 1) * size_t(d.uvrow);
-  const unsigned char* u1 = d.uv + size_t(ty.i1 >> 1) * size_t(d.uvrow);
-  int a[3], b[3], c[3], e[3];
-  nv12_pixel(p.m, y0, u0, tx.i0, a);
-  nv12_pixel(p.m, y0, u0, tx.i1, b);
-  nv12_pixel(p.m, y1, u1, tx.i0, c);
-  nv12_pixel(p.m, y1, u1, tx.i1, e);
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
-    const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
-    yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
-  }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(RS_THREADS) void resize_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<RS_THREADS>(table, p, 3, [](const Nv12Image& d, const Nv12ListParams& pp, float* yo, int hw, int px, int r, int q) {
-      nv12_list_pixel(d, pp, yo + px, hw, r, q);
-    });
-    return;
-  }
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {  // nv12_list_pixel, kept inline as in resize_u8_list_kernel
-    const Nv12Image d = table[i];
-    const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_rq<MODE>(d.flip, p.H, p.W, r, q).q);
-    const unsigned char* y0 = d.y + size_t(ty.i0) * size_t(d.yrow);
-    const unsigned char* y1 = d.y + size_t(ty.i1) * size_t(d.yrow);
-    const unsigned char* u0 = d.uv + size_t(ty.i0 >> 1) * size_t(d.uvrow);
-    const unsigned char* u1 = d.uv + size_t(ty.i1 >> 1) * size_t(d.uvrow);
-    int a[3], b[3], c[3], e[3];
-    nv12_pixel(p.m, y0, u0, tx.i0, a);
-    nv12_pixel(p.m, y0, u0, tx.i1, b);
-    nv12_pixel(p.m, y1, u1, tx.i0, c);
-    nv12_pixel(p.m, y1, u1, tx.i1, e);
-    float* yi = p.y + size_t(i) * size_t(p.y_nstride) + px;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
-      const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
-      yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
-    }
-  }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(RS_THREADS) void resize_aa_nv12_list_kernel(const Nv12Image* __restrict__ table, Nv12ListParams p) {
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<RS_THREADS>(table, p, 3, [&](const Nv12Image& d, const Nv12ListParams& pp, float* yo, int hw, int px, int r, int q) {
-      aa_pixel<3>(aa_image(d, p.m), pp, yo, hw, px, r, q);
-    });
-    return;
-  }
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const ListRQ m = list_rq<MODE>(table[i].flip, p.H, p.W, r, q);
-    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q);
-  }
-}
-
-// the four pixels of a bilinear tap, fetched one way
-template <int F>
-__device__ __forceinline__ void yuv_quad(const YuvImage& d, const YuvMatrix& m, const YuvRow& w0, const YuvRow& w1,
-                                         const ResizeTap& tx, int (&a)[3], int (&b)[3], int (&c)[3], int (&e)[3]) {
-  yuv_pixel<F>(d, m, w0, tx.i0, a);
-  yuv_pixel<F>(d, m, w0, tx.i1, b);
-  yuv_pixel<F>(d, m, w1, tx.i0, c);
-  yuv_pixel<F>(d, m, w1, tx.i1, e);
-}
-
-// the YUV list kernels: the NV12 pair over the strided-plane descriptor, which is one scalar load per workgroup as there
-// one output pixel of descriptor d, as u8_list_pixel
-__device__ __forceinline__ void yuv_list_pixel(const YuvImage& d, const YuvListParams& p, float* yi, int HW,
-                                               int r, int q) {
-  const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-  const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + q);
-  const YuvRow w0 = yuv_row(d, ty.i0), w1 = yuv_row(d, ty.i1);
-  int a[3], b[3], c[3], e[3];
-  switch (yuv_fetch(d)) {
-    case YUV_PACKED: yuv_quad<YUV_PACKED>(d, p.m, w0, w1, tx, a, b, c, e); break;
-    case YUV_PAIRS: yuv_quad<YUV_PAIRS>(d, p.m, w0, w1, tx, a, b, c, e); break;
-    case YUV_PLANES: yuv_quad<YUV_PLANES>(d, p.m, w0, w1, tx, a, b, c, e); break;
-    default: yuv_quad<YUV_GREY>(d, p.m, w0, w1, tx, a, b, c, e); break;
-  }
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
-    const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
-    yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
-  }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(RS_THREADS) void resize_yuv_list_kernel(const YuvImage* __restrict__ table, YuvListParams p) {
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<RS_THREADS>(table, p, 3, [](const YuvImage& d, const YuvListParams& pp, float* yo, int hw, int px, int r, int q) {
-      yuv_list_pixel(d, pp, yo + px, hw, r, q);
-    });
-    return;
-  }
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {  // yuv_list_pixel, kept inline as in resize_u8_list_kernel
-    const YuvImage d = table[i];
-    const ResizeTap ty = resize_tap(d.Hs, d.Rh, d.top + r);
-    const ResizeTap tx = resize_tap(d.Ws, d.Rw, d.left + list_rq<MODE>(d.flip, p.H, p.W, r, q).q);
-    const YuvRow w0 = yuv_row(d, ty.i0), w1 = yuv_row(d, ty.i1);
-    int a[3], b[3], c[3], e[3];
-    switch (yuv_fetch(d)) {
-      case YUV_PACKED: yuv_quad<YUV_PACKED>(d, p.m, w0, w1, tx, a, b, c, e); break;
-      case YUV_PAIRS: yuv_quad<YUV_PAIRS>(d, p.m, w0, w1, tx, a, b, c, e); break;
-      case YUV_PLANES: yuv_quad<YUV_PLANES>(d, p.m, w0, w1, tx, a, b, c, e); break;
-      default: yuv_quad<YUV_GREY>(d, p.m, w0, w1, tx, a, b, c, e); break;
-    }
-    float* yi = p.y + size_t(i) * size_t(p.y_nstride) + px;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      const float up = lerp_rn(float(a[s]), float(b[s]), tx.t);
-      const float lo = lerp_rn(float(c[s]), float(e[s]), tx.t);
-      yi[size_t(p.plane[s]) * size_t(HW)] = norm_rn(lerp_rn(up, lo, ty.t), p.scale[s], p.shift[s]);
-    }
-  }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(RS_THREADS) void resize_aa_yuv_list_kernel(const YuvImage* __restrict__ table, YuvListParams p) {
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<RS_THREADS>(table, p, 3, [&](const YuvImage& d, const YuvListParams& pp, float* yo, int hw, int px, int r, int q) {
-      aa_pixel<3>(aa_image(d, p.m), pp, yo, hw, px, r, q);
-    });
-    return;
-  }
-  const int px = blockIdx.x * RS_THREADS + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const ListRQ m = list_rq<MODE>(table[i].flip, p.H, p.W, r, q);
-    aa_pixel<3>(aa_image(table[i], p.m), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q);
-  }
-}
-
-template <class K, class... A>
-void aa_launch(K k, const dim3& grid, hipStream_t s, A... a) {
-  hipLaunchKernelGGL(k, grid, dim3(RS_THREADS), 0, s, a...);
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // ORE_FILTER_BICUBIC and ORE_FILTER_BICUBIC_AA (include/ore.h has the arithmetic, ore_resize_geom.h the taps and
 // weights): float weights, every operation rounded on its own, no integer sums -- so nothing of the triangle
-// filter's run code above applies.  One thread per output pixel; one device body per filter over a source (Src):
-// where a row starts (at), the C ints of one of its pixels (px) and of four neighbours at once (px4: interleaved
-// bytes as C dwords).  The three kinds of source differ in nothing else.
+// filter's run code above applies, and a source's at, px and px4 are all they read.  One thread per output pixel.
 //
 // The antialiased filter's column weights are the same for every tap row of a pixel: they are computed once per
 // pixel into LDS, laid out [tap][thread] (stride 1 in the thread index: conflict-free; a thread reads only what it
@@ -857,74 +731,6 @@ void aa_launch(K k, const dim3& grid, hipStream_t s, A... a) {
 // that 64 taps are 32 KB.  DESIGN.md 3.8g has the variants measured.
 
 constexpr int CUBIC_AA_THREADS = 128;
-
-struct CubicGeom {
-  int Hs, Ws, Rh, Rw, top, left;
-};
-
-template <class T>
-__device__ __forceinline__ CubicGeom cubic_geom(const T& t) {
-  CubicGeom g;
-  g.Hs = t.Hs; g.Ws = t.Ws; g.Rh = t.Rh; g.Rw = t.Rw; g.top = t.top; g.left = t.left;
-  return g;
-}
-
-template <int C>
-struct CubicSrcU8 {
-  const unsigned char* x;
-  int row;  // bytes between rows
-  using Row = const unsigned char*;
-  __device__ __forceinline__ Row at(int r) const { return x + size_t(r) * size_t(row); }
-  __device__ __forceinline__ void px(Row w, int j, int (&v)[C]) const {
-#pragma unroll
-    for (int s = 0; s < C; ++s) v[s] = int(w[j * C + s]);
-  }
-  // pixels j .. j + 3, all inside the row: their 4 C bytes as C dword loads at the pixels' own (any) alignment
-  __device__ __forceinline__ void px4(Row w, int j, int (&v)[4][C]) const {
-    unsigned d[C];
-#pragma unroll
-    for (int i = 0; i < C; ++i) __builtin_memcpy(&d[i], w + j * C + 4 * i, 4);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int s = 0; s < C; ++s) {
-        const int k = t * C + s;
-        v[t][s] = int((d[k >> 2] >> (8 * (k & 3))) & 0xffu);
-      }
-  }
-};
-
-struct CubicSrcNv12 {
-  const unsigned char* y;
-  const unsigned char* uv;
-  int yrow, uvrow;
-  YuvMatrix m;
-  struct Row {
-    const unsigned char* yr;
-    const unsigned char* ur;
-  };
-  __device__ __forceinline__ Row at(int r) const {
-    return Row{y + size_t(r) * size_t(yrow), uv + size_t(r >> 1) * size_t(uvrow)};
-  }
-  __device__ __forceinline__ void px(const Row& w, int j, int (&v)[3]) const { nv12_pixel(m, w.yr, w.ur, j, v); }
-  __device__ __forceinline__ void px4(const Row& w, int j, int (&v)[4][3]) const {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) px(w, j + t, v[t]);
-  }
-};
-
-template <int F>
-struct CubicSrcYuv {
-  YuvImage d;
-  YuvMatrix m;
-  using Row = YuvRow;
-  __device__ __forceinline__ Row at(int r) const { return yuv_row(d, r); }
-  __device__ __forceinline__ void px(const Row& w, int j, int (&v)[3]) const { yuv_pixel<F>(d, m, w, j, v); }
-  __device__ __forceinline__ void px4(const Row& w, int j, int (&v)[4][3]) const {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) px(w, j + t, v[t]);
-  }
-};
 
 __device__ __forceinline__ float mul_rn(float a, float b) {
 #pragma clang fp contract(off)
@@ -938,7 +744,7 @@ __device__ __forceinline__ float add_rn(float a, float b) {
 
 // ORE_FILTER_BICUBIC: 4 x 4 taps, the border replicated; the tap columns are clamped once, outside the rows
 template <int C, class Src, class P>
-__device__ __forceinline__ void cubic_pixel(const Src& src, const CubicGeom& g, const P& p, float* __restrict__ yi, int HW,
+__device__ __forceinline__ void cubic_pixel(const Src& src, const ResizeGeom& g, const P& p, float* __restrict__ yi, int HW,
                                             int px, int r, int q) {
   const ResizeCubicTap ty = resize_cubic_tap(g.Hs, g.Rh, g.top + r);
   const ResizeCubicTap tx = resize_cubic_tap(g.Ws, g.Rw, g.left + q);
@@ -966,7 +772,7 @@ __device__ __forceinline__ void cubic_pixel(const Src& src, const CubicGeom& g, 
 
 // ORE_FILTER_BICUBIC_AA: u is this thread's column of the LDS weight table, tap j at u[j * CUBIC_AA_THREADS]
 template <int C, class Src, class P>
-__device__ __forceinline__ void cubic_aa_pixel(const Src& src, const CubicGeom& g, const P& p, float* __restrict__ yi, int HW,
+__device__ __forceinline__ void cubic_aa_pixel(const Src& src, const ResizeGeom& g, const P& p, float* __restrict__ yi, int HW,
                                                int px, int r, int q, float* __restrict__ u) {
   const int oy = g.top + r, ox = g.left + q;
   const ResizeCubicSpan sx = resize_cubic_aa_span(g.Ws, g.Rw, ox);
@@ -1016,112 +822,60 @@ __device__ __forceinline__ void cubic_aa_pixel(const Src& src, const CubicGeom& 
   }
 }
 
-// one pixel under either filter: AA selects the body (and with it the workgroup's size, cubic_threads)
-template <bool AA, int C, class Src, class P>
-__device__ __forceinline__ void cubic_any(const Src& src, const CubicGeom& g, const P& p, float* __restrict__ yi, int HW, int px,
-                                          int r, int q, float* __restrict__ u) {
-  if constexpr (AA)
-    cubic_aa_pixel<C>(src, g, p, yi, HW, px, r, q, u);
+// ---------------------------------------------------------------------------------------------------------
+// The kernels.  FILTER is an ore_resize_filter; it selects the body and with it the workgroup's size.
+
+constexpr int filter_threads(int filter) { return filter == ORE_FILTER_BICUBIC_AA ? CUBIC_AA_THREADS : RS_THREADS; }
+
+// output pixel px under FILTER: row r and column q of the window of src, channel s stored at yo[p.plane[s] * HW + px];
+// u as in cubic_aa_pixel.  The way to fetch a YUV descriptor selects is chosen where 3.8f measured it for each filter:
+// around the whole pixel for the cubic bodies (here), around the four fetches in bilinear_pixel, per tap row in aa_pixel.
+template <int FILTER, int C, class Src, class P>
+__device__ __forceinline__ void filter_pixel(const Src& src, const ResizeGeom& g, const P& p, float* yo, int HW, int px, int r,
+                                             int q, float* u) {
+  if constexpr (FILTER == ORE_FILTER_BILINEAR_AA)
+    aa_pixel<C>(src, g, p, yo, HW, px, r, q);
+  else if constexpr (FILTER == ORE_FILTER_BILINEAR)
+    bilinear_pixel<C>(src, g, p, yo + px, HW, r, q);
   else
-    cubic_pixel<C>(src, g, p, yi, HW, px, r, q);
-}
-
-template <bool AA>
-constexpr int cubic_threads() { return AA ? CUBIC_AA_THREADS : RS_THREADS; }
-
-template <bool AA, int C>
-__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_kernel(ResizeParams p) {
-  extern __shared__ float cubic_lds[];
-  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  const CubicGeom g = cubic_geom(p);
-  const int row = p.Ws * p.C;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const CubicSrcU8<C> src{p.x + size_t(i) * size_t(p.Hs) * size_t(row), row};
-    cubic_any<AA, C>(src, g, p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, q, cubic_lds + threadIdx.x);
-  }
-}
-
-// the list descriptor is one scalar load per workgroup, as in resize_u8_list_kernel
-template <bool AA, int C, int MODE>
-__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_list_kernel(const ResizeImage* __restrict__ table,
-                                                                                ResizeListParams p) {
-  extern __shared__ float cubic_lds[];
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<cubic_threads<AA>()>(table, p, C, [&](const ResizeImage& d, const ResizeListParams& pp, float* yo, int hw, int px, int r, int q) {
-      cubic_any<AA, C>(CubicSrcU8<C>{d.x, d.row}, cubic_geom(d), pp, yo, hw, px, r, q, cubic_lds + threadIdx.x);
+    yuv_fetch_as(src, [&](const auto& s) {
+      if constexpr (FILTER == ORE_FILTER_BICUBIC_AA)
+        cubic_aa_pixel<C>(s, g, p, yo, HW, px, r, q, u);
+      else
+        cubic_pixel<C>(s, g, p, yo, HW, px, r, q);
     });
-    return;
-  }
-  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const ResizeImage d = table[i];
-    const CubicSrcU8<C> src{d.x, d.row};
-    const ListRQ m = list_rq<MODE>(d.flip, p.H, p.W, r, q);
-    cubic_any<AA, C>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q, cubic_lds + threadIdx.x);
-  }
 }
 
-template <bool AA, int MODE>
-__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_nv12_list_kernel(const Nv12Image* __restrict__ table,
-                                                                                     Nv12ListParams p) {
+// the dense batch under every filter but the plain one (resize_u8_generic_kernel, whose taps stay outside the image loop)
+template <int FILTER, int C>
+__global__ __launch_bounds__(filter_threads(FILTER)) void resize_dense_kernel(ResizeParams p) {
   extern __shared__ float cubic_lds[];
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<cubic_threads<AA>()>(table, p, 3, [&](const Nv12Image& d, const Nv12ListParams& pp, float* yo, int hw, int px, int r, int q) {
-      cubic_any<AA, 3>(CubicSrcNv12{d.y, d.uv, d.yrow, d.uvrow, p.m}, cubic_geom(d), pp, yo, hw, px, r, q, cubic_lds + threadIdx.x);
-    });
-    return;
-  }
-  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
+  const int px = blockIdx.x * filter_threads(FILTER) + threadIdx.x;
   const int HW = p.H * p.W;
   if (px >= HW) return;
   const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const Nv12Image d = table[i];
-    const CubicSrcNv12 src{d.y, d.uv, d.yrow, d.uvrow, p.m};
-    const ListRQ m = list_rq<MODE>(d.flip, p.H, p.W, r, q);
-    cubic_any<AA, 3>(src, cubic_geom(d), p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q, cubic_lds + threadIdx.x);
-  }
+  const ResizeGeom g = resize_geom(p);
+  for (long long i = blockIdx.y; i < p.N; i += gridDim.y)
+    filter_pixel<FILTER, C>(src_of<C>(p, i), g, p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, r, q, cubic_lds + threadIdx.x);
 }
 
-// the way to fetch is chosen once per image from the descriptor (wave-uniform), as in resize_yuv_list_kernel
-template <bool AA>
-__device__ __forceinline__ void cubic_yuv_pixel(const YuvImage& d, const YuvListParams& p, float* __restrict__ yi, int HW, int px,
-                                                int r, int q, float* __restrict__ u) {
-  const CubicGeom g = cubic_geom(d);
-  switch (yuv_fetch(d)) {
-    case YUV_PACKED: cubic_any<AA, 3>(CubicSrcYuv<YUV_PACKED>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
-    case YUV_PAIRS: cubic_any<AA, 3>(CubicSrcYuv<YUV_PAIRS>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
-    case YUV_PLANES: cubic_any<AA, 3>(CubicSrcYuv<YUV_PLANES>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
-    default: cubic_any<AA, 3>(CubicSrcYuv<YUV_GREY>{d, p.m}, g, p, yi, HW, px, r, q, u); break;
-  }
-}
-
-template <bool AA, int MODE>
-__global__ __launch_bounds__(cubic_threads<AA>()) void resize_cubic_yuv_list_kernel(const YuvImage* __restrict__ table,
-                                                                                    YuvListParams p) {
+// the list of descriptors D under parameters P (interleaved bytes: C = 1..4, or 0 under the plain filter, which takes
+// p.C at run time; NV12 and YUV frames: C = 3)
+template <int FILTER, int C, int MODE, class D, class P>
+__global__ __launch_bounds__(filter_threads(FILTER)) void resize_list_kernel(const D* __restrict__ table, P p) {
   extern __shared__ float cubic_lds[];
-  if constexpr (MODE == LIST_ORIENT) {
-    list_tiled<cubic_threads<AA>()>(table, p, 3, [&](const YuvImage& d, const YuvListParams& pp, float* yo, int hw, int px, int r, int q) {
-      cubic_yuv_pixel<AA>(d, pp, yo, hw, px, r, q, cubic_lds + threadIdx.x);
-    });
-    return;
-  }
-  const int px = blockIdx.x * cubic_threads<AA>() + threadIdx.x;
-  const int HW = p.H * p.W;
-  if (px >= HW) return;
-  const int r = px / p.W, q = px - r * p.W;
-  for (long long i = blockIdx.y; i < p.N; i += gridDim.y) {
-    const YuvImage d = table[i];
-    const ListRQ m = list_rq<MODE>(d.flip, p.H, p.W, r, q);
-    cubic_yuv_pixel<AA>(d, p, p.y + size_t(i) * size_t(p.y_nstride), HW, px, m.r, m.q, cubic_lds + threadIdx.x);
-  }
+  int channels = C;
+  if constexpr (C == 0) channels = p.C;
+  list_pixels<filter_threads(FILTER), MODE>(table, p, channels, [&](const D& d, const P& pp, float* yo, int hw, int px, int r, int q) {
+    if constexpr (C == 0)
+      bilinear_u8_pixel(d, pp, yo + px, hw, r, q);
+    else
+      filter_pixel<FILTER, C>(src_of<C>(d, pp), resize_geom(d), pp, yo, hw, px, r, q, cubic_lds + threadIdx.x);
+  });
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// The launches.
 
 // blocks of T threads for an H x W output: one per T pixels, or under LIST_ORIENT one per tile of T / 16 rows x 16 columns
 inline dim3 list_grid(int H, int W, long long N, int T, int mode = LIST_PLAIN) {
@@ -1130,132 +884,80 @@ inline dim3 list_grid(int H, int W, long long N, int T, int mode = LIST_PLAIN) {
   return dim3(unsigned(((long long)H * W + T - 1) / T), gy);
 }
 
-// the instance of a list kernel template K<..., MODE> for ResizeListParams::flips (a ListMode)
-#define ORE_LIST_KERNEL(mode, K, ...) \
-  ((mode) == LIST_ORIENT ? K<__VA_ARGS__ LIST_ORIENT> : (mode) ? K<__VA_ARGS__ LIST_FLIP> : K<__VA_ARGS__ LIST_PLAIN>)
-
-// grid, workgroup and LDS of a cubic launch: the plain filter takes no LDS; `taps` bounds the antialiased runs' columns
-template <bool AA, class K, class... A>
-void cubic_launch(K k, int H, int W, long long N, int taps, int mode, hipStream_t s, A... a) {
-  constexpr int T = cubic_threads<AA>();
-  const size_t lds = AA ? size_t(taps) * T * sizeof(float) : 0;
-  hipLaunchKernelGGL(k, list_grid(H, W, N, T, mode), dim3(T), lds, s, a...);
+// the antialiased cubic filter's weight table: `taps` bounds its column runs; the other filters take no dynamic LDS
+inline size_t filter_lds(int filter, int taps) {
+  return filter == ORE_FILTER_BICUBIC_AA ? size_t(taps) * CUBIC_AA_THREADS * sizeof(float) : 0;
 }
 
-template <bool AA>
-void cubic_u8(const ResizeParams& p, hipStream_t s) {
-  const int taps = resize_cubic_aa_max_taps(p.Ws, p.Rw);
-  switch (p.C) {
-    case 1: return cubic_launch<AA>(resize_cubic_kernel<AA, 1>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
-    case 2: return cubic_launch<AA>(resize_cubic_kernel<AA, 2>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
-    case 3: return cubic_launch<AA>(resize_cubic_kernel<AA, 3>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
-    default: return cubic_launch<AA>(resize_cubic_kernel<AA, 4>, p.H, p.W, p.N, taps, LIST_PLAIN, s, p);
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// f(Int<FILTER>) for an ore_resize_filter the caller's checks have seen, f(Int<C>) for a channel count 1..4
+template <class F>
+void with_filter(int32_t filter, F&& f) {
+  if (filter & ORE_FILTER_CUBIC_BIT)
+    filter == ORE_FILTER_BICUBIC_AA ? f(Int<ORE_FILTER_BICUBIC_AA>{}) : f(Int<ORE_FILTER_BICUBIC>{});
+  else
+    filter == ORE_FILTER_BILINEAR_AA ? f(Int<ORE_FILTER_BILINEAR_AA>{}) : f(Int<ORE_FILTER_BILINEAR>{});
+}
+
+template <class F>
+void with_channels(int C, F&& f) {
+  switch (C) {
+    case 1: return f(Int<1>{});
+    case 2: return f(Int<2>{});
+    case 3: return f(Int<3>{});
+    default: return f(Int<4>{});
   }
 }
 
-template <bool AA>
-void cubic_u8_list(const ResizeListParams& p, hipStream_t s) {
-  const ResizeImage* table = p.table + p.first;
-  const int m = p.flips;
-  switch (p.C) {
-    case 1: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 1,), p.H, p.W, p.N, p.taps, m, s, table, p);
-    case 2: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 2,), p.H, p.W, p.N, p.taps, m, s, table, p);
-    case 3: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 3,), p.H, p.W, p.N, p.taps, m, s, table, p);
-    default: return cubic_launch<AA>(ORE_LIST_KERNEL(m, resize_cubic_list_kernel, AA, 4,), p.H, p.W, p.N, p.taps, m, s, table, p);
-  }
-}
-
-}  // namespace
-
-void launch_resize_cubic_u8(const ResizeParams& p, bool aa, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  aa ? cubic_u8<true>(p, s) : cubic_u8<false>(p, s);
-}
-
-// The list launches: the three kernel families (cubic_list, aa_list, plain_list) over the three descriptor formats,
-// then launch_resize_list's choice among them, written once.  The cubic ones size the LDS by p.taps: the longest column
+// One list launch: the instance for p.flips (a ListMode), its grid, and the LDS sized by p.taps: the longest column
 // run of the list's last set, or, where a captured launch may meet the descriptors of a later set, the longest the
 // ratio rule allows.
-
-static void cubic_list(const ResizeListParams& p, bool aa, hipStream_t s) { aa ? cubic_u8_list<true>(p, s) : cubic_u8_list<false>(p, s); }
-
-static void cubic_list(const Nv12ListParams& p, bool aa, hipStream_t s) {
-  const Nv12Image* table = p.table + p.first;
-  if (aa)
-    cubic_launch<true>(ORE_LIST_KERNEL(p.flips, resize_cubic_nv12_list_kernel, true,), p.H, p.W, p.N, p.taps, p.flips, s, table, p);
-  else
-    cubic_launch<false>(ORE_LIST_KERNEL(p.flips, resize_cubic_nv12_list_kernel, false,), p.H, p.W, p.N, 0, p.flips, s, table, p);
-}
-
-static void cubic_list(const YuvListParams& p, bool aa, hipStream_t s) {
-  const YuvImage* table = p.table + p.first;
-  if (aa)
-    cubic_launch<true>(ORE_LIST_KERNEL(p.flips, resize_cubic_yuv_list_kernel, true,), p.H, p.W, p.N, p.taps, p.flips, s, table, p);
-  else
-    cubic_launch<false>(ORE_LIST_KERNEL(p.flips, resize_cubic_yuv_list_kernel, false,), p.H, p.W, p.N, 0, p.flips, s, table, p);
-}
-
-void launch_resize_aa_u8(const ResizeParams& p, hipStream_t s) {
-  if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  if (p.Hs <= p.Rh && p.Ws <= p.Rw) return launch_resize_u8(p, s);  // nothing shrinks: the plain filter, bit for bit
-  const dim3 grid = list_grid(p.H, p.W, p.N, RS_THREADS);
-  switch (p.C) {
-    case 1: return aa_launch(resize_aa_pixel_kernel<1>, grid, s, p);
-    case 2: return aa_launch(resize_aa_pixel_kernel<2>, grid, s, p);
-    case 3: return aa_launch(resize_aa_pixel_kernel<3>, grid, s, p);
-    default: return aa_launch(resize_aa_pixel_kernel<4>, grid, s, p);
-  }
-}
-
-static void aa_list(const ResizeListParams& p, hipStream_t s) {
-  const ResizeImage* table = p.table + p.first;
-  const dim3 grid = list_grid(p.H, p.W, p.N, RS_THREADS, p.flips);
-  switch (p.C) {
-    case 1: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 1,), grid, s, table, p);
-    case 2: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 2,), grid, s, table, p);
-    case 3: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 3,), grid, s, table, p);
-    default: return aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_pixel_list_kernel, 4,), grid, s, table, p);
-  }
-}
-
-static void plain_list(const Nv12ListParams& p, hipStream_t s) {
-  aa_launch(ORE_LIST_KERNEL(p.flips, resize_nv12_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
-}
-
-static void aa_list(const Nv12ListParams& p, hipStream_t s) {
-  aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_nv12_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
-}
-
-static void plain_list(const YuvListParams& p, hipStream_t s) {
-  aa_launch(ORE_LIST_KERNEL(p.flips, resize_yuv_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
-}
-
-static void aa_list(const YuvListParams& p, hipStream_t s) {
-  aa_launch(ORE_LIST_KERNEL(p.flips, resize_aa_yuv_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
-}
-
-static void plain_list(const ResizeListParams& p, hipStream_t s) {
-  aa_launch(ORE_LIST_KERNEL(p.flips, resize_u8_list_kernel, ), list_grid(p.H, p.W, p.N, RS_THREADS, p.flips), s, p.table + p.first, p);
+template <int FILTER, int C, class D, class P>
+void list_launch(const D* table, const P& p, hipStream_t s) {
+  constexpr int T = filter_threads(FILTER);
+  const auto k = p.flips == LIST_ORIENT ? resize_list_kernel<FILTER, C, LIST_ORIENT, D, P>
+                 : p.flips              ? resize_list_kernel<FILTER, C, LIST_FLIP, D, P>
+                                        : resize_list_kernel<FILTER, C, LIST_PLAIN, D, P>;
+  hipLaunchKernelGGL(k, list_grid(p.H, p.W, p.N, T, p.flips), dim3(T), filter_lds(FILTER, p.taps), s, table, p);
 }
 
 template <class P>
-static void resize_list(const P& p, int32_t filter, hipStream_t s) {
+void resize_list(const P& p, int32_t filter, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  if (filter & ORE_FILTER_CUBIC_BIT)
-    cubic_list(p, filter == ORE_FILTER_BICUBIC_AA, s);
-  else if (filter == ORE_FILTER_BILINEAR_AA)
-    aa_list(p, s);
-  else
-    plain_list(p, s);
+  with_filter(filter, [&](auto f) {
+    constexpr int FILTER = decltype(f)::value;
+    if constexpr (!std::is_same_v<P, ResizeListParams>)
+      list_launch<FILTER, 3>(p.table + p.first, p, s);
+    else if constexpr (FILTER == ORE_FILTER_BILINEAR)
+      list_launch<FILTER, 0>(p.table + p.first, p, s);  // one instance for every channel count
+    else
+      with_channels(p.C, [&](auto c) { list_launch<FILTER, decltype(c)::value>(p.table + p.first, p, s); });
+  });
 }
+
+}  // namespace
 
 void launch_resize_list(const ResizeListParams& p, int32_t filter, hipStream_t s) { resize_list(p, filter, s); }
 void launch_resize_list(const Nv12ListParams& p, int32_t filter, hipStream_t s) { resize_list(p, filter, s); }
 void launch_resize_list(const YuvListParams& p, int32_t filter, hipStream_t s) { resize_list(p, filter, s); }
 
-void launch_resize_u8(const ResizeParams& p, hipStream_t s) {
+void launch_resize_dense(const ResizeParams& p, int32_t filter, hipStream_t s) {
   if (p.N <= 0 || p.H <= 0 || p.W <= 0) return;
-  hipLaunchKernelGGL(resize_u8_generic_kernel, list_grid(p.H, p.W, p.N, RS_THREADS), dim3(RS_THREADS), 0, s, p);
+  if (filter == ORE_FILTER_BILINEAR_AA && p.Hs <= p.Rh && p.Ws <= p.Rw) filter = ORE_FILTER_BILINEAR;  // nothing shrinks: the plain filter, bit for bit
+  with_filter(filter, [&](auto f) {
+    constexpr int FILTER = decltype(f)::value;
+    if constexpr (FILTER == ORE_FILTER_BILINEAR) {
+      hipLaunchKernelGGL(resize_u8_generic_kernel, list_grid(p.H, p.W, p.N, RS_THREADS), dim3(RS_THREADS), 0, s, p);
+    } else {
+      constexpr int T = filter_threads(FILTER);
+      const size_t lds = FILTER == ORE_FILTER_BICUBIC_AA ? filter_lds(FILTER, resize_cubic_aa_max_taps(p.Ws, p.Rw)) : 0;
+      with_channels(p.C, [&](auto c) {
+        hipLaunchKernelGGL((resize_dense_kernel<FILTER, decltype(c)::value>), list_grid(p.H, p.W, p.N, T), dim3(T), lds, s, p);
+      });
+    }
+  });
 }
 
 }  // namespace ore

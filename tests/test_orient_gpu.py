@@ -323,6 +323,34 @@ def test_oriented_into_a_poisoned_slice(gpu_ctx, name):
             assert bool((body[:, per:].contiguous().view(torch.int32) == nan_bits).all())
 
 
+# ------------------------------------------------------------------------------------------ past the grid's rows
+@pytest.mark.parametrize("name", ["bilinear", "bicubic_aa"])
+def test_oriented_past_the_grid_limit(gpu_ctx, name):
+    """65,539 oriented descriptors, more than a grid's 65,535 rows, so four blocks visit a second descriptor (on the
+    pattern of test_image_list_gpu.py::test_past_the_grid_limit).  Codes cycle with period four, which does not divide
+    65,535: descriptors i and i + 65,535 of a block differ, a transposing one (through the LDS tile) follows an upright
+    one and the other way round.  bicubic_aa is the 128-thread kernel with its weights' dynamic LDS beside the tile."""
+    import ore
+    (aa, cubic), fn = FILTERS[name]
+    n, out_hw = 65539, (2, 3)
+    assert 65535 % 4 != 0
+    codes, flips = (1, 6, 3, 5), (False, True, False, False)
+    pool = [images(hw + (3,), seed=1900 + k) for k, hw in enumerate([(3, 5), (6, 4), (2, 7), (5, 5)])]  # stored sizes
+    geoms = [((3, 5), (1, 1)), ((4, 4), (1, 0)), ((3, 4), (0, 1)), ((4, 5), (2, 2))]  # displayed space: resize and crop
+    scale, shift = _norm(3)
+    refs = np.stack([oriented_ref(fn, pool[k], codes[k], geoms[k][0], geoms[k][1], out_hw, flips[k], scale=scale, shift=shift)
+                     for k in range(4)])
+    assert len({r.tobytes() for r in refs}) == 4
+    dev = [_cuda(x) for x in pool]
+    idx = np.arange(n) % 4
+    with _closing(ore.ImageList(gpu_ctx, n, out_hw, 3, aa, cubic)) as (lst,):
+        lst.set_oriented([dev[k] for k in idx], [codes[k] for k in idx], geometries=[geoms[k] for k in idx],
+                         flips=[flips[k] for k in idx])
+        assert lst.oriented and lst.count == n
+        y = ore.preprocess_list_u8(gpu_ctx, lst, scale=scale, shift=shift).cpu().numpy()
+    np.testing.assert_array_equal(y, refs[idx])
+
+
 # ------------------------------------------------------------------------------------------ the entries' contract
 def _fill(arr, tensors, geoms):
     from ore import _lib
