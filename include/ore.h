@@ -918,6 +918,46 @@ ore_status ore_cam_boxes_f32(ore_ctx* ctx, const float* maps, int64_t planes, in
 ore_status ore_cam_box_host(const float* map, int64_t hm, int64_t wm, int64_t h, int64_t w, float frac, int32_t box[4],
                             int32_t* area);
 ore_status ore_model_set_cam_boxes(ore_model* m, int32_t* d_boxes, int32_t* d_areas, int64_t cap_planes, float frac);
+/* Image retrieval (extension; ore_nearest.hip): the model's embedding, and the k nearest rows of a
+ * gallery by inner product without the score matrix.
+ *  ore_nearest_f32: q is [n, D] f32 on the DEVICE (rows q->dims[0], D the product of the remaining dims, as for
+ *    ore_topk_f32; q->nstride >= D honoured, any 4-byte aligned base), gallery a contiguous DEVICE array [G, D]
+ *    row-major, values and indices contiguous DEVICE arrays [n, k].  The score of query i against row j is
+ *    s[i,j] = sum_d q[i,d] gallery[j,d], accumulated in f32 on the f32 matrix cores; row i of the output is
+ *    ore_topk_f32's order applied to s[i, :]: larger first, equal scores (-0 equal to +0) by lower gallery index,
+ *    every NaN after every number, NaNs by index.  values[i,r] holds the bits of the winning score (a score is never
+ *    -0: the accumulators start at +0; a NaN score comes back as the quiet NaN 0x7fc00000).  The metric is the inner
+ *    product only: L2-normalise both sides for the cosine similarity.
+ *    Position independence: the K dimension is never split across waves or workgroups and never reduced in an order
+ *    that depends on the tile, so the bits of s[i,j] depend only on q[i,:] and gallery[j,:] -- not on n, G, k, where
+ *    row j sits in the gallery, or the launch configuration.  Keys are unique, so the selection is deterministic.
+ *    Checked from the arguments alone, before the context and any device call (ORE_ERR_INVALID, the message names
+ *    the quantity), in this order: null pointers; q not 2-D to 4-D (or n >= 2^31); D < 1; G < 1 or G >= 2^31; k
+ *    outside 1..min(G, 64); the nstride rule at the top of this file.  n == 0 is ORE_OK and launches nothing.
+ *    Offsets into the gallery are 64-bit; only the row index is 32-bit.  Few queries are spread over gallery
+ *    segments whose k-key partial results live in a context-owned buffer, grown on demand (ore_ctx_set_alloc_fill
+ *    honoured) -- never inside a stream capture: ORE_ERR_INVALID asks for one call of the shape outside it first.
+ *  ore_nearest_segments: the number of gallery segments a call with n queries and G rows runs on this context's
+ *    device (1: one launch that writes the outputs itself; above 1: a merge launch follows).
+ *  ore_model_embed_dim: C of the map conv's input X [n, C, Hm, Wm] (the rule of ore_model_cam_dims);
+ *    ORE_ERR_UNSUPPORTED with the same message for a model without a map conv.
+ *  ore_model_set_embed: while d_embed (DEVICE, cap_elems floats) is set, every classify entry that
+ *    ore_model_set_cam governs also writes e[i, c] = the mean of plane (i, c) of X, float32 contiguous [n, C] (per
+ *    image under views), by the walker's GlobalAveragePool launchers on X in the plan's layout (f16 models sum the
+ *    f16 values in f32): what ore_gap_f32 gives for X.  With ORE_EMBED_L2 each row is then divided by sqrt(sum e^2);
+ *    a zero row stays zero.  Launched per chunk behind the top-k launch (and the maps), after the pass's last timing
+ *    event; not an exec step.  X stays live while the maps or the embedding are on: turning the embedding on or off
+ *    is ORE_ERR_INVALID while the stream is capturing and replans when it changes whether X is pinned; changing only
+ *    the pointer, the capacity or the flags does not.  Off (NULL, the default), the plan, the arena and the launches
+ *    are those of a model that never had it on.  A classify call with n * C > cap_elems is ORE_ERR_INVALID before any
+ *    device call; a flag other than ORE_EMBED_L2 or cap_elems < 0 is ORE_ERR_INVALID.  ore_model_read_value of X
+ *    works after a run with the embedding on. */
+#define ORE_EMBED_L2 1
+ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, int32_t k, float* values,
+                           int32_t* indices);
+ore_status ore_nearest_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments);
+ore_status ore_model_embed_dim(ore_model* m, int64_t* dim);
+ore_status ore_model_set_embed(ore_model* m, float* d_embed, int64_t cap_elems, int32_t flags);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);
 int32_t ore_model_step_count(ore_model* m);
 ore_status ore_model_step_info(ore_model* m, int32_t i, const char** op, const char** name, double* flops,

@@ -27,6 +27,9 @@ struct ore_ctx {
   int resize_variant = 0;  // ore_ctx_set_resize_variant: 0 by geometry, 1 thread per pixel -- one kernel today, so nothing reads it
   bool alloc_fill = false;         // ore_ctx_set_alloc_fill (debug): device_alloc fills what the library allocates for itself
   uint32_t alloc_pattern = 0;
+  int ncu = 256;                   // compute units of the device (ore_ctx_create): ore_nearest_f32's segment count
+  void* nearest_part = nullptr;    // ore_nearest_f32's partial keys [n][S][k], grown on demand as the weight scratch is
+  size_t nearest_bytes = 0;
 };
 
 // ore_image_list: a device table of `capacity` packed descriptors for one output shape and its pinned host

@@ -597,5 +597,17 @@ const char* cam_boxes_unsupported(long long hm, long long wm, long long h, long 
 void launch_upsample_maps_f32(const float* maps, long long planes, int hm, int wm, int h, int w, float* out, hipStream_t s);
 void launch_cam_boxes_f32(const float* maps, long long planes, int hm, int wm, int h, int w, float frac, int* boxes, int* areas,
                           hipStream_t s);
+// nearest neighbours by inner product (ore_nearest.hip): for query row i of q (row i at q + i * q_stride, q_stride
+// >= D, any 4-byte aligned base) the k best of s[i, j] = sum_d q[i, d] gallery[j, d] over the contiguous gallery
+// [G][D], in launch_topk's order, as contiguous values / indices [n][k]; 1 <= k <= min(G, 64), G < 2^31.  The bits
+// of s[i, j] depend on the two rows alone.  S = nearest_segments(n, G, CUs of the device) gallery segments; with
+// S > 1 `part` holds nearest_partial_bytes(n, S, k) bytes (every byte read was written by the same call) and a
+// second launch merges.
+int nearest_segments(long long n, long long G, int ncu);
+size_t nearest_partial_bytes(long long n, int S, int k);
+void launch_nearest(const float* q, long long q_stride, int n, int D, const float* gallery, long long G, int k, int S,
+                    void* part, float* values, int* indices, hipStream_t s);
+// rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
+void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 
 }  // namespace ore

@@ -1004,6 +1004,10 @@ static ore_status check_views(ore_model* m, int64_t n) {
 
 // the classify entries' rule under ore_model_set_cam: the maps of n images fit the caller's buffer
 static ore_status check_cam(ore_model* m, int64_t n) {
+  if (m->embed_buf && n * m->values[m->cam_in].dims[1] > m->embed_cap)  // ... and so do their embeddings (ore_model_set_embed)
+    return set_error(m->ctx, ORE_ERR_INVALID, "the embeddings of %lld images (%lld floats each) need %lld floats, the buffer of "
+                     "ore_model_set_embed holds %lld", (long long)n, (long long)m->values[m->cam_in].dims[1],
+                     (long long)(n * m->values[m->cam_in].dims[1]), (long long)m->embed_cap);
   if (!m->cam_buf) return ORE_OK;
   const Value& T = m->values[m->cam_map];
   const int64_t need = n * m->topk * T.dims[2] * T.dims[3];
@@ -1054,6 +1058,28 @@ static ore_status launch_cam_boxes(ore_model* m, int64_t i0, int64_t nc) {
   const int64_t P = T.dims[2] * T.dims[3], p0 = i0 * m->topk;
   launch_cam_boxes_f32(m->cam_buf + p0 * P, nc * m->topk, int(T.dims[2]), int(T.dims[3]), int(iv.dims[2]), int(iv.dims[3]),
                        m->box_frac, m->box_buf + p0 * 4, m->box_areas ? m->box_areas + p0 : nullptr, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+// The embeddings of a chunk (ore_model_set_embed): the plane means of the map conv's input for images [i0, i0 + nc),
+// by the GlobalAveragePool launchers of launch_step / launch_step_f16 in the layout the plan gave the value, then
+// the rows' L2 normalisation
+static ore_status launch_embed(ore_model* m, int64_t i0, int64_t nc) {
+  ore_ctx* ctx = m->ctx;
+  const Value& X = m->values[m->cam_in];
+  const Ref x = ref_of(m, m->cam_in);
+  const int64_t C = X.dims[1], P = X.dims[2] * X.dims[3];
+  float* const e = m->embed_buf + i0 * C;
+  if (!x.p || x.es != (m->f16 ? 2 : 4)) return err(m, ORE_ERR_INVALID, "internal: the map conv's input is not materialised");
+  if (x.es == 2) {
+    launch_gap_nhwc(x.p, e, int(nc), int(C), int(P), int(pixel_stride(x, C)), x.nstride, ctx->stream);
+  } else {
+    const int64_t ps = plane_stride(x, P);
+    if (x.nstride != C * ps) return err(m, ORE_ERR_INVALID, "internal: the embedding of a strided view");
+    launch_gap(x.p, 4, e, nc * C, int(P), int(ps), ctx->stream);
+  }
+  if (m->embed_flags & ORE_EMBED_L2) launch_l2_normalize(e, nc, int(C), ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }
@@ -1149,6 +1175,8 @@ static ore_status run_chunks(ore_model* m, const float* d_input, const uint8_t* 
         if (m->box_buf)
           if (ore_status st = launch_cam_boxes(m, i0, nc)) return st;
       }
+      if (m->embed_buf)
+        if (ore_status st = launch_embed(m, i0, nc)) return st;
     }
   }
   return ORE_OK;
@@ -1233,32 +1261,46 @@ ore_status ore_model_cam_dims(ore_model* m, int64_t hw[2]) {
   return ORE_OK;
 }
 
+// A reader of the map conv's input behind the pass -- `slot` is m->cam_buf or m->embed_buf -- gets the buffer `buf`.
+// On <-> off is refused inside a capture, and replans when it changes whether the plan pins the conv's input
+// (ore_model::cam_in_pinned); a failed replan puts back the plan that stood.
+static ore_status set_cam_in_reader(ore_model* m, const char* who, float*& slot, float* buf) {
+  ore_ctx* ctx = m->ctx;
+  if ((buf != nullptr) == (slot != nullptr)) {  // only the pointer changes
+    slot = buf;
+    return ORE_OK;
+  }
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return set_error(ctx, ORE_ERR_INVALID, "%s inside a stream capture (it replans the model)", who);
+  const bool was = m->cam_in_pinned();
+  float* const old_buf = slot;
+  slot = buf;
+  if (m->cam_in_pinned() == was) return ORE_OK;  // the other reader holds the pin
+  // the arena is sized anew, so that turning the last reader off gives back exactly the arena of a model without
+  // one (plan() alone only ever grows it)
+  slot = old_buf;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ORE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (m->arena_alloc) (void)hipFree(m->arena_alloc);
+  m->arena = m->arena_alloc = nullptr;
+  m->arena_bytes = 0;
+  slot = buf;
+  if (ore_status st = plan(m)) {  // back to the plan that stood
+    const std::string e = ctx->err;
+    slot = old_buf;
+    (void)plan(m);
+    return set_error(ctx, st, "%s", e.c_str());
+  }
+  return ORE_OK;
+}
+
 ore_status ore_model_set_cam(ore_model* m, float* d_maps, int64_t cap_elems) {
   if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
   ore_ctx* ctx = m->ctx;
   if (d_maps && m->cam_conv < 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "%s", m->cam_why.c_str());
   if (d_maps && cap_elems < 0) return set_error(ctx, ORE_ERR_INVALID, "class map buffer of %lld floats", (long long)cap_elems);
-  if ((d_maps != nullptr) != (m->cam_buf != nullptr)) {  // on <-> off: the plan pins (or releases) the conv's input
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return set_error(ctx, ORE_ERR_INVALID, "ore_model_set_cam inside a stream capture (it replans the model)");
-    // the arena is sized anew, so that turning the maps off gives back exactly the arena of a model without them
-    // (plan() alone only ever grows it)
-    ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    ORE_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (m->arena_alloc) (void)hipFree(m->arena_alloc);
-    m->arena = m->arena_alloc = nullptr;
-    m->arena_bytes = 0;
-    float* const old_buf = m->cam_buf;
-    m->cam_buf = d_maps;
-    if (ore_status st = plan(m)) {  // back to the plan that stood
-      const std::string e = ctx->err;
-      m->cam_buf = old_buf;
-      (void)plan(m);
-      return set_error(ctx, st, "%s", e.c_str());
-    }
-  }
-  m->cam_buf = d_maps;
+  if (ore_status st = set_cam_in_reader(m, "ore_model_set_cam", m->cam_buf, d_maps)) return st;
   m->cam_cap = d_maps ? cap_elems : 0;
   if (!d_maps) {  // the boxes are those of the maps
     m->box_buf = m->box_areas = nullptr;
@@ -1292,6 +1334,27 @@ ore_status ore_model_set_cam_boxes(ore_model* m, int32_t* d_boxes, int32_t* d_ar
   m->box_areas = d_boxes ? d_areas : nullptr;
   m->box_cap = d_boxes ? cap_planes : 0;
   m->box_frac = d_boxes ? frac : 0.0f;
+  return ORE_OK;
+}
+
+ore_status ore_model_embed_dim(ore_model* m, int64_t* dim) {
+  if (!m || !dim) return set_error(m ? m->ctx : nullptr, ORE_ERR_INVALID, "null argument");
+  if (m->cam_conv < 0) return set_error(m->ctx, ORE_ERR_UNSUPPORTED, "%s", m->cam_why.c_str());
+  *dim = m->values[m->cam_in].dims[1];
+  return ORE_OK;
+}
+
+ore_status ore_model_set_embed(ore_model* m, float* d_embed, int64_t cap_elems, int32_t flags) {
+  if (!m) return set_error(nullptr, ORE_ERR_INVALID, "null model");
+  ore_ctx* ctx = m->ctx;
+  if (d_embed && (flags & ~ORE_EMBED_L2)) return set_error(ctx, ORE_ERR_INVALID, "embedding flags %d: only ORE_EMBED_L2 is known", int(flags));
+  if (d_embed && cap_elems < 0) return set_error(ctx, ORE_ERR_INVALID, "embedding buffer of %lld floats", (long long)cap_elems);
+  if (d_embed && m->cam_conv < 0) return set_error(ctx, ORE_ERR_UNSUPPORTED, "%s", m->cam_why.c_str());
+  if (d_embed && m->values[m->cam_in].ndim != 4)
+    return set_error(ctx, ORE_ERR_UNSUPPORTED, "no embedding: the map conv's input has %d dims", int(m->values[m->cam_in].ndim));
+  if (ore_status st = set_cam_in_reader(m, "ore_model_set_embed", m->embed_buf, d_embed)) return st;
+  m->embed_cap = d_embed ? cap_elems : 0;
+  m->embed_flags = d_embed ? flags : 0;
   return ORE_OK;
 }
 

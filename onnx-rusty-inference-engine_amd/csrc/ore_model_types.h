@@ -211,6 +211,13 @@ struct ore_model {
   int32_t* box_areas = nullptr;  // DEVICE [n, topk] or null
   int64_t box_cap = 0;           // planes both hold
   float box_frac = 0.0f;         // the threshold's share of the map's range
+  // the embedding (ore_model_set_embed): the plane means of the map conv's input, one launch behind each chunk's top-k
+  float* embed_buf = nullptr;    // DEVICE [n, C]; null: off
+  int64_t embed_cap = 0;         // its capacity in floats
+  int32_t embed_flags = 0;       // ORE_EMBED_L2
+  // the map conv's input has a reader behind the pass (the class maps or the embedding): the plan never elides it
+  // and keeps it live to the end of the pass
+  bool cam_in_pinned() const { return (cam_buf || embed_buf) && cam_in >= 0; }
 };
 
 namespace ore {

@@ -634,6 +634,8 @@ ore_status ore_ctx_create(int32_t device, ore_ctx** out) {
     return set_error(nullptr, ORE_ERR_HIP, "hipStreamCreate failed");
   }
   c->stream = c->own_stream;
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->ncu = ncu;
   *out = c;
   return ORE_OK;
 }
@@ -644,6 +646,7 @@ ore_status ore_ctx_destroy(ore_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   else (void)hipDeviceSynchronize();
   if (ctx->scratch) (void)hipFree(ctx->scratch);
+  if (ctx->nearest_part) (void)hipFree(ctx->nearest_part);
   if (ctx->own_stream) {
     (void)hipStreamSynchronize(ctx->own_stream);
     (void)hipStreamDestroy(ctx->own_stream);
@@ -882,6 +885,55 @@ ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, i
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   launch_topk_mean(x->data, nstride_of(x), rows / views, int(views), int(D), int(k), values, indices, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, int32_t k, float* values,
+                           int32_t* indices) {
+  // the context last, as ore_topk_mean_f32: what can be judged without one is
+  if (!q || !q->data || !gallery || !values || !indices) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (q->ndim < 2 || q->ndim > 4 || q->dims[0] < 0 || !fits_i32(q->dims[0]))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: q of %d dims and %lld rows, expected [n, D] in 2 to 4 dims", int(q->ndim),
+                     (long long)(q->ndim >= 1 && q->ndim <= 4 ? q->dims[0] : 0));
+  const int64_t n = q->dims[0], lim = int64_t(1) << 31;
+  int64_t D = 1;
+  for (int i = 1; i < q->ndim; ++i) D = q->dims[i] >= 1 && D >= 1 && D * q->dims[i] < lim ? D * q->dims[i] : 0;
+  if (D < 1) return set_error(ctx, ORE_ERR_INVALID, "nearest: D, the row length of q, is not in 1..2^31-1");
+  if (G < 1 || G >= lim) return set_error(ctx, ORE_ERR_INVALID, "nearest: G = %lld outside 1..2^31-1", (long long)G);
+  if (k < 1 || k > std::min<int64_t>(G, 64))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: k = %d outside 1..%lld (min(G, 64))", int(k), (long long)std::min<int64_t>(G, 64));
+  if (q->nstride < 0 || (q->nstride && (q->nstride < D || q->nstride >= lim || !fits_i32(q->nstride * std::max<int64_t>(n, 1) + 256))))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: q->nstride %lld with %lld rows of %lld: below the row length or past 32-bit indexing",
+                     (long long)q->nstride, (long long)n, (long long)D);
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int S = nearest_segments(n, G, ctx->ncu);
+  const size_t need = nearest_partial_bytes(n, S, k);
+  if (need > ctx->nearest_bytes) {  // the partial keys, grown on demand as the weight scratch is -- but never inside a capture
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return set_error(ctx, ORE_ERR_INVALID, "nearest: the partial buffer must grow to %zu bytes inside a stream capture: make one "
+                       "call of this shape outside the capture first", need);
+    if (ctx->nearest_part) {
+      (void)hipStreamSynchronize(ctx->stream);
+      (void)hipFree(ctx->nearest_part);
+    }
+    ctx->nearest_part = nullptr;
+    ctx->nearest_bytes = 0;
+    if (device_alloc(ctx, &ctx->nearest_part, need, true) != hipSuccess)
+      return set_error(ctx, ORE_ERR_OOM, "nearest: partial buffer allocation (%zu bytes) failed", need);
+    ctx->nearest_bytes = need;
+  }
+  launch_nearest(q->data, nstride_of(q), int(n), int(D), gallery, G, int(k), S, ctx->nearest_part, values, indices, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments) {
+  if (!ctx || !segments) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
+  *segments = nearest_segments(n, G, ctx->ncu);
   return ORE_OK;
 }
 

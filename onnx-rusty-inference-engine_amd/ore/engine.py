@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -926,6 +926,44 @@ def topk_mean(ctx: Context, x, views: int, k: int):
     return values, indices
 
 
+def nearest(ctx: Context, q, gallery, k: int):
+    """ore_nearest_f32 (extension): for every row of q [n, D] the k rows of gallery [G, D] with the largest inner
+    product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the scores -- the [n, G] score
+    matrix is never formed.  q may be a row slice (q.stride(0) >= D, rows dense); gallery is contiguous.  The bits of
+    a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise both sides for cosine similarity."""
+    torch = _torch()
+    for name, t in (("q", q), ("gallery", gallery)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise OreError(1, f"{name}: expected a 2-D float32 CUDA tensor")
+        if t.device.index != ctx.device:
+            raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
+    n, D = int(q.shape[0]), int(q.shape[1])
+    G = int(gallery.shape[0])
+    if int(gallery.shape[1]) != D or not gallery.is_contiguous():
+        raise OreError(1, f"gallery: expected a contiguous [G, {D}] tensor, got {tuple(gallery.shape)}")
+    if n > 1 and (q.stride(1) != 1 or q.stride(0) < D) or n <= 1 and not q.is_contiguous():
+        raise OreError(1, "q: expected dense rows at a row stride of at least D")
+    if not 1 <= int(k) <= min(G, 64):
+        raise OreError(1, f"k = {k} outside 1..{min(G, 64)} (min(G, 64))")
+    values = torch.empty((n, int(k)), dtype=torch.float32, device=q.device)
+    indices = torch.empty((n, int(k)), dtype=torch.int32, device=q.device)
+    if n == 0:
+        return values, indices
+    d = Tensor()
+    d.data, d.ndim, d.nstride = q.data_ptr(), 2, (int(q.stride(0)) if n > 1 else 0)
+    d.dims[0], d.dims[1] = n, D
+    check(load().ore_nearest_f32(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), G, int(k),
+                                 ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr())), ctx.h)
+    return values, indices
+
+
+def nearest_segments(ctx: Context, n: int, G: int) -> int:
+    """ore_nearest_segments: the gallery segments nearest() runs n queries against G rows on (1: one launch)."""
+    s = ctypes.c_int32()
+    check(load().ore_nearest_segments(ctx.h, int(n), int(G), ctypes.byref(s)), ctx.h)
+    return s.value
+
+
 def class_maps(ctx: Context, x, w, bias, classes, relu: bool = True, views: int = 1):
     """ore_class_maps_f32 (extension): the class activation maps of the selected classes, a gathered 1x1 conv.
     x float32 [n, C, H, W] (images may be strided: x.stride(0) >= C*H*W with dense images), w float32 [M, C]
@@ -1289,6 +1327,68 @@ class Model:
     def classify_cam_u8_list(self, lst):
         """classify_u8_list(lst) with the class activation maps."""
         return self._with_cam(self._check_list(lst), lambda: self.classify_u8_list(lst))
+
+    # ---- the embedding (ore_model_set_embed): the plane means of the map conv's input, for retrieval (nearest)
+    _embed_out = None  # (tensor, normalize) of set_embed_output (kept alive: the library holds its pointer)
+
+    @property
+    def embed_dim(self):
+        """ore_model_embed_dim: the embedding's length C (SqueezeNet: 512); raises ORE_ERR_UNSUPPORTED for a model
+        without a map conv, as cam_hw does."""
+        c = ctypes.c_int64()
+        check(load().ore_model_embed_dim(self.h, ctypes.byref(c)), self.ctx.h)
+        return int(c.value)
+
+    def set_embed_output(self, buf, normalize: bool = True):
+        """ore_model_set_embed: while a float32 CUDA tensor is set, classify* / capture_classify* also write the
+        embeddings of their images into it as [n, embed_dim] (per image under views), L2-normalised unless
+        normalize=False; it must hold n * embed_dim floats for every call.  None turns them off.  Turning them on or
+        off may replan the model (re-capture graphs afterwards); another tensor does not."""
+        torch = _torch()
+        if buf is None:
+            check(load().ore_model_set_embed(self.h, None, 0, 0), self.ctx.h)
+            self._embed_out = None
+        else:
+            if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.float32:
+                raise OreError(1, "buf: expected a float32 CUDA tensor")
+            if buf.device.index != self.ctx.device:
+                raise OreError(1, f"buf: on cuda:{buf.device.index}, the context is on cuda:{self.ctx.device}")
+            if not buf.is_contiguous():
+                raise OreError(1, "buf: expected a contiguous tensor")
+            check(load().ore_model_set_embed(self.h, ctypes.c_void_p(buf.data_ptr()), int(buf.numel()),
+                                             _lib.EMBED_L2 if normalize else 0), self.ctx.h)
+            self._embed_out = (buf, bool(normalize))
+        self.run_batch = int(load().ore_model_run_batch(self.h))
+
+    def _with_embed(self, n: int, call, normalize: bool):
+        """call() with a fresh [n, embed_dim] tensor set as the embedding output; the previous setting is restored."""
+        torch = _torch()
+        emb = torch.empty((n, self.embed_dim), dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        if n == 0:
+            return call() + (emb,)
+        prev = self._embed_out
+        self.set_embed_output(emb, normalize)
+        try:
+            return call() + (emb,)
+        finally:
+            self.set_embed_output(*(prev or (None,)))
+
+    def classify_embed(self, x, normalize: bool = True):
+        """classify(x) with the embeddings: (scores, classes, emb [n, embed_dim]).  A convenience with two replans per
+        call from off, as classify_cam; for repeated calls set_embed_output once and use classify_into."""
+        return self._with_embed(self._check_classify_in(x, False), lambda: self.classify(x), normalize)
+
+    def classify_embed_u8(self, x, normalize: bool = True):
+        """classify_u8(x) with the embeddings."""
+        return self._with_embed(self._check_classify_in(x, True), lambda: self.classify_u8(x), normalize)
+
+    def classify_embed_u8_list(self, lst, normalize: bool = True):
+        """classify_u8_list(lst) with the embeddings."""
+        return self._with_embed(self._check_list(lst), lambda: self.classify_u8_list(lst), normalize)
+
+    def embed(self, x, normalize: bool = True):
+        """The embeddings of classify_embed(x) alone."""
+        return self.classify_embed(x, normalize)[2]
 
     # ---- boxes of the class activation maps (ore_model_set_cam_boxes)
     _cam_boxes = None  # (boxes, areas, frac) of set_cam_boxes (kept alive: the library holds their pointers)

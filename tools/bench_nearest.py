@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""Cost of the nearest-neighbour search and of the embedding on the GPU: prints one JSON line.
+ (a) ore.nearest for n in {1, 32, 256} queries against G in {10^4, 10^6} rows at D = 512, k = 5, beside what a
+     caller did before on the same tensors: q @ g.T followed by torch.topk.  Each case with its two floors: one read
+     of the gallery per query tile of 64 at --hbm-tbs, and 2 n G D FLOPs at --mfma-tflops (the f32 matrix peak); the
+     larger is the floor that binds.  The share of rows on which both return the same index set is reported.
+ (b) Model.classify_into (SqueezeNet at --hw, --batch images, k = 5, f32 and f16, autotuned, set_streams(2)) with
+     the normalised embedding on against off.
+Every figure is the median over --rounds windows of back-to-back calls timed by HIP events on the context stream,
+with the smallest and largest window beside it; the variants of one comparison alternate inside a round.  Needs an
+MI355X (no fallback).
+usage: python tools/bench_nearest.py [--batch 256] [--hw 224] [--rounds 9] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "onnx-rusty-inference-engine_amd"))
+sys.path.insert(0, os.path.join(REPO, "tools"))
+
+from bench_ingest import alternate  # noqa: E402  (the same windows and alternation)
+
+D, K = 512, 5
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--hw", type=int, default=224)
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--hbm-tbs", type=float, default=8.0)
+    ap.add_argument("--mfma-tflops", type=float, default=157.3)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import torch
+    import ore
+    from ore import squeezenet
+    if not torch.cuda.is_available():
+        sys.exit("bench_nearest.py: no GPU visible")
+    ctx = ore.Context(0)
+    gen = torch.Generator(device="cuda").manual_seed(1000)
+    res = {"tool": "bench_nearest", "D": D, "k": K, "rounds": a.rounds, "hbm_tbs": a.hbm_tbs, "mfma_tflops": a.mfma_tflops,
+           "nearest": {}, "model": {}}
+    for G in (10 ** 4, 10 ** 6):
+        g = torch.nn.functional.normalize(torch.randn((G, D), device="cuda", generator=gen))
+        for n in (1, 32, 256):
+            q = torch.nn.functional.normalize(torch.randn((n, D), device="cuda", generator=gen))
+            reps = 20 if G * n <= 10 ** 7 else 3
+            r = alternate({"ore_nearest": (lambda: ore.nearest(ctx, q, g, K), reps),
+                           "matmul_topk": (lambda: torch.topk(q @ g.T, K, dim=1), reps)}, a.rounds)
+            ours, theirs = ore.nearest(ctx, q, g, K)[1], torch.topk(q @ g.T, K, dim=1)[1]
+            torch.cuda.synchronize()
+            same = (ours.long().sort(1)[0] == theirs.sort(1)[0]).all(1).float().mean()
+            read_us = -(-n // 64) * G * D * 4 / (a.hbm_tbs * 1e6)
+            mfma_us = 2.0 * n * G * D / (a.mfma_tflops * 1e6)
+            us = r["ore_nearest"]["us"]
+            res["nearest"][f"n{n}_G{G}"] = dict(
+                r, segments=ore.nearest_segments(ctx, n, G), floor_read_us=round(read_us, 2), floor_mfma_us=round(mfma_us, 2),
+                bound="mfma" if mfma_us > read_us else "read", share_of_floor=round(max(read_us, mfma_us) / us, 4),
+                gallery_gbs=round(-(-n // 64) * G * D * 4 / us / 1e3, 1), tflops=round(2.0 * n * G * D / us / 1e6, 2),
+                speedup=round(r["matmul_topk"]["us"] / us, 3), same_index_set_share=round(float(same), 4))
+        del g
+    B, S = a.batch, a.hw
+    x = torch.randn((B, 3, S, S), device="cuda", generator=gen)
+    for precision in ("f32", "f16"):
+        m = ore.Model(ctx, squeezenet.build(S), max_batch=B, precision=precision)
+        m.set_streams(2)
+        m.set_topk(K)
+        m.autotune(x, torch.empty((B, m.output_elems), device="cuda"))
+        scores = torch.empty((B, K), dtype=torch.float32, device="cuda")
+        classes = torch.empty((B, K), dtype=torch.int32, device="cuda")
+        emb = torch.empty((B, m.embed_dim), dtype=torch.float32, device="cuda")
+        # on <-> off replans, so the two settings are timed one after the other, off - on - off
+        off1 = alternate({"classify_into": (lambda: m.classify_into(x, scores, classes), 10)}, a.rounds)["classify_into"]
+        m.set_embed_output(emb)
+        on = alternate({"classify_into": (lambda: m.classify_into(x, scores, classes), 10)}, a.rounds)["classify_into"]
+        m.set_embed_output(None)
+        off2 = alternate({"classify_into": (lambda: m.classify_into(x, scores, classes), 10)}, a.rounds)["classify_into"]
+        res["model"][precision] = {"embed_off": off1, "embed_on": on, "embed_off_again": off2,
+                                   "added_us": round(on["us"] - (off1["us"] + off2["us"]) / 2, 2)}
+        m.close()
+    ctx.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
