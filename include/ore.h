@@ -956,6 +956,28 @@ ore_status ore_model_set_cam_boxes(ore_model* m, int32_t* d_boxes, int32_t* d_ar
 ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, int32_t k, float* values,
                            int32_t* indices);
 ore_status ore_nearest_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments);
+/* The same search on an f16 gallery (extension; ore_nearest_f16.hip): half the memory and half the
+ * read, on the f16 matrix cores.
+ *  ore_gallery_f16: src is a contiguous DEVICE f32 array [G, D], dst a contiguous DEVICE IEEE binary16 array [G, D];
+ *    one launch.  Round to nearest even; a magnitude past 65504 becomes +-inf (a plain cast with no clamp, the rule
+ *    of ORE_LOAD_F16), subnormals are kept, a NaN stays a NaN.  ORE_ERR_INVALID from the arguments alone, before the
+ *    context and any device call: null pointers; G or D outside 1..2^31-1.
+ *  ore_nearest_f16: q is f32 exactly as for ore_nearest_f32 (2-D to 4-D, q->nstride >= D honoured, any 4-byte aligned
+ *    base), gallery a contiguous DEVICE binary16 array [G, D] at any 2-byte aligned base.  The score is
+ *    s[i,j] = sum_d RNE_f16(q[i,d]) gallery[j,d]: the queries are rounded inside the kernel (no f16 copy of q is
+ *    written to memory), the products are exact in f32, and they are accumulated in f32 on the f16 matrix cores
+ *    (the accumulation contract above: within 2e-6 sum_d |q^ g| of the exact sum).  The output order, the value
+ *    rules (a score is never -0; a NaN score is 0x7fc00000), the argument checks with their order and messages,
+ *    n == 0, the partial buffer with its capture rule and ore_ctx_set_alloc_fill are ore_nearest_f32's.
+ *    Position independence: the K dimension is never split across waves or workgroups and never reduced in an order
+ *    that depends on the tile, so the bits of s[i,j] depend only on q[i,:] and gallery[j,:] -- not on n, G, k, where
+ *    row j sits in the gallery, the segments or the load path.
+ *  ore_nearest_segments_f16: the gallery segments of such a call with n queries and G rows on this context's device,
+ *    and the gallery rows one workgroup takes per step. */
+ore_status ore_gallery_f16(ore_ctx* ctx, const float* src, int64_t G, int64_t D, uint16_t* dst);
+ore_status ore_nearest_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, int32_t k, float* values,
+                           int32_t* indices);
+ore_status ore_nearest_segments_f16(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows);
 ore_status ore_model_embed_dim(ore_model* m, int64_t* dim);
 ore_status ore_model_set_embed(ore_model* m, float* d_embed, int64_t cap_elems, int32_t flags);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);

@@ -607,6 +607,18 @@ int nearest_segments(long long n, long long G, int ncu);
 size_t nearest_partial_bytes(long long n, int S, int k);
 void launch_nearest(const float* q, long long q_stride, int n, int D, const float* gallery, long long G, int k, int S,
                     void* part, float* values, int* indices, hipStream_t s);
+// the merge of part[n][S][k] (k keys per segment, descending, 0 from the first empty slot on; 2 <= S <= 512) into
+// values / indices: the second launch of launch_nearest and of launch_nearest_f16
+void launch_nearest_merge(const void* part, long long n, int S, int k, float* values, int* indices, hipStream_t s);
+// the same search on an f16 gallery (ore_nearest_f16.hip): s[i, j] = sum_d RNE_f16(q[i, d]) gallery[j, d] on the f16
+// matrix cores, q as above, gallery contiguous binary16 [G][D] at any 2-byte aligned base; S =
+// nearest_f16_segments(n, G, CUs), part as above.  nearest_f16_step_rows: the gallery rows a workgroup takes per step.
+// launch_gallery_f16: contiguous f32 [G][D] -> binary16 [G][D], round to nearest even, no clamp, one launch.
+int nearest_f16_segments(long long n, long long G, int ncu);
+int nearest_f16_step_rows();
+void launch_nearest_f16(const float* q, long long q_stride, int n, int D, const void* gallery, long long G, int k, int S,
+                        void* part, float* values, int* indices, hipStream_t s);
+void launch_gallery_f16(const float* src, long long G, long long D, void* dst, hipStream_t s);
 // rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 

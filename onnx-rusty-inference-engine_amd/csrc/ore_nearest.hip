@@ -287,9 +287,12 @@ void launch_nearest(const float* q, long long q_stride, int n, int D, const floa
   else if (vg) nearest_launch<false, true>(a, s);
   else if (vq) nearest_launch<true, false>(a, s);
   else nearest_launch<false, false>(a, s);
-  if (S > 1)
-    hipLaunchKernelGGL(nearest_merge_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, static_cast<const u64*>(part),
-                       (long long)n, S, k, values, indices);
+  if (S > 1) launch_nearest_merge(part, n, S, k, values, indices, s);
+}
+
+void launch_nearest_merge(const void* part, long long n, int S, int k, float* values, int* indices, hipStream_t s) {
+  hipLaunchKernelGGL(nearest_merge_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, static_cast<const u64*>(part), n, S,
+                     k, values, indices);
 }
 
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s) {

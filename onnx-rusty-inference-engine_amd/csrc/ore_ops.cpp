@@ -888,9 +888,9 @@ ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, i
   return ORE_OK;
 }
 
-ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, int32_t k, float* values,
-                           int32_t* indices) {
-  // the context last, as ore_topk_mean_f32: what can be judged without one is
+// ore_nearest_f32 / ore_nearest_f16: the checks that need no context, in the header's order (ORE_OK: n and D are set)
+static ore_status nearest_check(ore_ctx* ctx, const ore_tensor* q, const void* gallery, int64_t G, int32_t k, const float* values,
+                                const int32_t* indices, int64_t* n_out, int64_t* D_out) {
   if (!q || !q->data || !gallery || !values || !indices) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (q->ndim < 2 || q->ndim > 4 || q->dims[0] < 0 || !fits_i32(q->dims[0]))
     return set_error(ctx, ORE_ERR_INVALID, "nearest: q of %d dims and %lld rows, expected [n, D] in 2 to 4 dims", int(q->ndim),
@@ -905,27 +905,74 @@ ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* galle
   if (q->nstride < 0 || (q->nstride && (q->nstride < D || q->nstride >= lim || !fits_i32(q->nstride * std::max<int64_t>(n, 1) + 256))))
     return set_error(ctx, ORE_ERR_INVALID, "nearest: q->nstride %lld with %lld rows of %lld: below the row length or past 32-bit indexing",
                      (long long)q->nstride, (long long)n, (long long)D);
+  *n_out = n;
+  *D_out = D;
+  return ORE_OK;
+}
+
+// the partial keys [n][S][k] of both entries, grown on demand as the weight scratch is -- but never inside a capture
+static ore_status nearest_grow_part(ore_ctx* ctx, size_t need) {
+  if (need <= ctx->nearest_bytes) return ORE_OK;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: the partial buffer must grow to %zu bytes inside a stream capture: make one "
+                     "call of this shape outside the capture first", need);
+  if (ctx->nearest_part) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(ctx->nearest_part);
+  }
+  ctx->nearest_part = nullptr;
+  ctx->nearest_bytes = 0;
+  if (device_alloc(ctx, &ctx->nearest_part, need, true) != hipSuccess)
+    return set_error(ctx, ORE_ERR_OOM, "nearest: partial buffer allocation (%zu bytes) failed", need);
+  ctx->nearest_bytes = need;
+  return ORE_OK;
+}
+
+ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, int32_t k, float* values,
+                           int32_t* indices) {
+  // the context last, as ore_topk_mean_f32: what can be judged without one is
+  int64_t n = 0, D = 0;
+  if (const ore_status st = nearest_check(ctx, q, gallery, G, k, values, indices, &n, &D)) return st;
   if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (n == 0) return ORE_OK;
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int S = nearest_segments(n, G, ctx->ncu);
-  const size_t need = nearest_partial_bytes(n, S, k);
-  if (need > ctx->nearest_bytes) {  // the partial keys, grown on demand as the weight scratch is -- but never inside a capture
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (ctx->stream && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return set_error(ctx, ORE_ERR_INVALID, "nearest: the partial buffer must grow to %zu bytes inside a stream capture: make one "
-                       "call of this shape outside the capture first", need);
-    if (ctx->nearest_part) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipFree(ctx->nearest_part);
-    }
-    ctx->nearest_part = nullptr;
-    ctx->nearest_bytes = 0;
-    if (device_alloc(ctx, &ctx->nearest_part, need, true) != hipSuccess)
-      return set_error(ctx, ORE_ERR_OOM, "nearest: partial buffer allocation (%zu bytes) failed", need);
-    ctx->nearest_bytes = need;
-  }
+  if (const ore_status st = nearest_grow_part(ctx, nearest_partial_bytes(n, S, k))) return st;
   launch_nearest(q->data, nstride_of(q), int(n), int(D), gallery, G, int(k), S, ctx->nearest_part, values, indices, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, int32_t k, float* values,
+                           int32_t* indices) {
+  int64_t n = 0, D = 0;
+  if (const ore_status st = nearest_check(ctx, q, gallery, G, k, values, indices, &n, &D)) return st;
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int S = nearest_f16_segments(n, G, ctx->ncu);
+  if (const ore_status st = nearest_grow_part(ctx, nearest_partial_bytes(n, S, k))) return st;
+  launch_nearest_f16(q->data, nstride_of(q), int(n), int(D), gallery, G, int(k), S, ctx->nearest_part, values, indices, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_segments_f16(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
+  if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
+  *segments = nearest_f16_segments(n, G, ctx->ncu);
+  *step_rows = nearest_f16_step_rows();
+  return ORE_OK;
+}
+
+ore_status ore_gallery_f16(ore_ctx* ctx, const float* src, int64_t G, int64_t D, uint16_t* dst) {
+  if (!src || !dst) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (G < 1 || G >= (int64_t(1) << 31) || D < 1 || D >= (int64_t(1) << 31))
+    return set_error(ctx, ORE_ERR_INVALID, "gallery: G = %lld, D = %lld outside 1..2^31-1", (long long)G, (long long)D);
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_gallery_f16(src, G, D, dst, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

@@ -11,6 +11,7 @@ from .engine import (Context, ImageList, Model, Nv12ImageList, YuvImageList, add
                      global_average_pool, inference, max_pool, mul, multi_crop_geometries, nv12_to_rgb, pool_out_shape, preprocess_list_u8, preprocess_resize_u8,
                      preprocess_u8, relu, reshape, resize_aa_taps, resize_cubic_taps, resize_taps, softmax, topk, topk_mean, yuv_planes_to_rgb, yuv_to_rgb,
                      apply_orientation, orient_geometry, oriented_hw, rotation_orientation,
-                     box_to_source, cam_box_reference, cam_boxes, upsample_maps, nearest, nearest_segments)
+                     box_to_source, cam_box_reference, cam_boxes, upsample_maps, nearest, nearest_segments, gallery_f16,
+                     nearest_segments_f16)
 
 __version__ = "0.1.0"

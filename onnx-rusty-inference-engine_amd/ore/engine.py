@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -927,14 +927,17 @@ def topk_mean(ctx: Context, x, views: int, k: int):
 
 
 def nearest(ctx: Context, q, gallery, k: int):
-    """ore_nearest_f32 (extension): for every row of q [n, D] the k rows of gallery [G, D] with the largest inner
-    product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the scores -- the [n, G] score
-    matrix is never formed.  q may be a row slice (q.stride(0) >= D, rows dense); gallery is contiguous.  The bits of
-    a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise both sides for cosine similarity."""
+    """ore_nearest_f32 / ore_nearest_f16 (extension): for every row of q [n, D] the k rows of gallery [G, D] with the
+    largest inner product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the scores -- the
+    [n, G] score matrix is never formed.  q is float32 and may be a row slice (q.stride(0) >= D, rows dense); gallery
+    is contiguous, float32 or float16 (gallery_f16(): q is then rounded to f16 inside the kernel, f32 accumulation on
+    the f16 matrix cores).  The bits of a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise
+    both sides for cosine similarity."""
     torch = _torch()
-    for name, t in (("q", q), ("gallery", gallery)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
-            raise OreError(1, f"{name}: expected a 2-D float32 CUDA tensor")
+    f16 = isinstance(gallery, torch.Tensor) and gallery.dtype == torch.float16
+    for name, t, dt in (("q", q, torch.float32), ("gallery", gallery, torch.float16 if f16 else torch.float32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or t.dim() != 2:
+            raise OreError(1, f"{name}: expected a 2-D {'float16' if dt == torch.float16 else 'float32'} CUDA tensor")
         if t.device.index != ctx.device:
             raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
     n, D = int(q.shape[0]), int(q.shape[1])
@@ -952,8 +955,9 @@ def nearest(ctx: Context, q, gallery, k: int):
     d = Tensor()
     d.data, d.ndim, d.nstride = q.data_ptr(), 2, (int(q.stride(0)) if n > 1 else 0)
     d.dims[0], d.dims[1] = n, D
-    check(load().ore_nearest_f32(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), G, int(k),
-                                 ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr())), ctx.h)
+    entry = load().ore_nearest_f16 if f16 else load().ore_nearest_f32
+    check(entry(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), G, int(k),
+                ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr())), ctx.h)
     return values, indices
 
 
@@ -962,6 +966,29 @@ def nearest_segments(ctx: Context, n: int, G: int) -> int:
     s = ctypes.c_int32()
     check(load().ore_nearest_segments(ctx.h, int(n), int(G), ctypes.byref(s)), ctx.h)
     return s.value
+
+
+def gallery_f16(ctx: Context, gallery):
+    """ore_gallery_f16: a contiguous float32 [G, D] gallery as a torch.float16 [G, D] tensor for nearest() -- round
+    to nearest even, no clamp (past 65504: inf), subnormals kept."""
+    torch = _torch()
+    if (not isinstance(gallery, torch.Tensor) or not gallery.is_cuda or gallery.dtype != torch.float32 or gallery.dim() != 2
+            or not gallery.is_contiguous() or gallery.numel() == 0):
+        raise OreError(1, "gallery: expected a contiguous, non-empty 2-D float32 CUDA tensor")
+    if gallery.device.index != ctx.device:
+        raise OreError(1, f"gallery: on cuda:{gallery.device.index}, the context is on cuda:{ctx.device}")
+    out = torch.empty(gallery.shape, dtype=torch.float16, device=gallery.device)
+    check(load().ore_gallery_f16(ctx.h, ctypes.c_void_p(gallery.data_ptr()), int(gallery.shape[0]), int(gallery.shape[1]),
+                                 ctypes.c_void_p(out.data_ptr())), ctx.h)
+    return out
+
+
+def nearest_segments_f16(ctx: Context, n: int, G: int):
+    """ore_nearest_segments_f16: (gallery segments, gallery rows a workgroup takes per step) of nearest() on a float16
+    gallery."""
+    s, r = ctypes.c_int32(), ctypes.c_int32()
+    check(load().ore_nearest_segments_f16(ctx.h, int(n), int(G), ctypes.byref(s), ctypes.byref(r)), ctx.h)
+    return s.value, r.value
 
 
 def class_maps(ctx: Context, x, w, bias, classes, relu: bool = True, views: int = 1):

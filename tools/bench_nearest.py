@@ -4,6 +4,9 @@
      caller did before on the same tensors: q @ g.T followed by torch.topk.  Each case with its two floors: one read
      of the gallery per query tile of 64 at --hbm-tbs, and 2 n G D FLOPs at --mfma-tflops (the f32 matrix peak); the
      larger is the floor that binds.  The share of rows on which both return the same index set is reported.
+     Beside them the same search on the packed f16 copy of the gallery (ore.gallery_f16), the three alternating
+     inside a round: its floors are the read at 2 bytes per element and the FLOPs at --mfma-f16-tflops (the f16
+     matrix peak), with the share of rows on which the f16 and the f32 search return the same index set.
  (b) Model.classify_into (SqueezeNet at --hw, --batch images, k = 5, f32 and f16, autotuned, set_streams(2)) with
      the normalised embedding on against off.
 Every figure is the median over --rounds windows of back-to-back calls timed by HIP events on the context stream,
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--hbm-tbs", type=float, default=8.0)
     ap.add_argument("--mfma-tflops", type=float, default=157.3)
+    ap.add_argument("--mfma-f16-tflops", type=float, default=2500.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -41,17 +45,31 @@ def main():
     ctx = ore.Context(0)
     gen = torch.Generator(device="cuda").manual_seed(1000)
     res = {"tool": "bench_nearest", "D": D, "k": K, "rounds": a.rounds, "hbm_tbs": a.hbm_tbs, "mfma_tflops": a.mfma_tflops,
-           "nearest": {}, "model": {}}
+           "mfma_f16_tflops": a.mfma_f16_tflops, "nearest": {}, "nearest_f16": {}, "model": {}}
     for G in (10 ** 4, 10 ** 6):
         g = torch.nn.functional.normalize(torch.randn((G, D), device="cuda", generator=gen))
+        gh = ore.gallery_f16(ctx, g)
         for n in (1, 32, 256):
             q = torch.nn.functional.normalize(torch.randn((n, D), device="cuda", generator=gen))
             reps = 20 if G * n <= 10 ** 7 else 3
             r = alternate({"ore_nearest": (lambda: ore.nearest(ctx, q, g, K), reps),
+                           "ore_nearest_f16": (lambda: ore.nearest(ctx, q, gh, K), reps),
                            "matmul_topk": (lambda: torch.topk(q @ g.T, K, dim=1), reps)}, a.rounds)
             ours, theirs = ore.nearest(ctx, q, g, K)[1], torch.topk(q @ g.T, K, dim=1)[1]
+            halves = ore.nearest(ctx, q, gh, K)[1]
             torch.cuda.synchronize()
             same = (ours.long().sort(1)[0] == theirs.sort(1)[0]).all(1).float().mean()
+            same_h = (ours.sort(1)[0] == halves.sort(1)[0]).all(1).float().mean()
+            h = r.pop("ore_nearest_f16")
+            read_h, mfma_h = -(-n // 64) * G * D * 2 / (a.hbm_tbs * 1e6), 2.0 * n * G * D / (a.mfma_f16_tflops * 1e6)
+            segments_h, step_rows = ore.nearest_segments_f16(ctx, n, G)
+            res["nearest_f16"][f"n{n}_G{G}"] = dict(
+                h, segments=segments_h, step_rows=step_rows, floor_read_us=round(read_h, 2), floor_mfma_us=round(mfma_h, 2),
+                bound="mfma" if mfma_h > read_h else "read", share_of_floor=round(max(read_h, mfma_h) / h["us"], 4),
+                gallery_gbs=round(-(-n // 64) * G * D * 2 / h["us"] / 1e3, 1), tflops=round(2.0 * n * G * D / h["us"] / 1e6, 2),
+                speedup_vs_f32=round(r["ore_nearest"]["us"] / h["us"], 3),
+                f32_window_spread_us=round(r["ore_nearest"]["max_us"] - r["ore_nearest"]["min_us"], 2),
+                same_index_set_share_vs_f32=round(float(same_h), 4))
             read_us = -(-n // 64) * G * D * 4 / (a.hbm_tbs * 1e6)
             mfma_us = 2.0 * n * G * D / (a.mfma_tflops * 1e6)
             us = r["ore_nearest"]["us"]
@@ -60,7 +78,7 @@ def main():
                 bound="mfma" if mfma_us > read_us else "read", share_of_floor=round(max(read_us, mfma_us) / us, 4),
                 gallery_gbs=round(-(-n // 64) * G * D * 4 / us / 1e3, 1), tflops=round(2.0 * n * G * D / us / 1e6, 2),
                 speedup=round(r["matmul_topk"]["us"] / us, 3), same_index_set_share=round(float(same), 4))
-        del g
+        del g, gh
     B, S = a.batch, a.hw
     x = torch.randn((B, 3, S, S), device="cuda", generator=gen)
     for precision in ("f32", "f16"):
