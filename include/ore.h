@@ -978,6 +978,39 @@ ore_status ore_gallery_f16(ore_ctx* ctx, const float* src, int64_t G, int64_t D,
 ore_status ore_nearest_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, int32_t k, float* values,
                            int32_t* indices);
 ore_status ore_nearest_segments_f16(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows);
+/* The same search on an int8 gallery with one f32 scale per row (extension; ore_nearest_i8.hip): a
+ * quarter of the f32 gallery's memory, exact integer accumulation on the int8 matrix cores.
+ *  Quantising a row x[0..D) of f32 -- the packer's rule and the kernel's rule for a query row.  Every operation is
+ *    rounded on its own (IEEE division, no fused multiply-add, subnormals kept):
+ *      a   = max_d |x_d|, NaN elements skipped (0 when there is none)
+ *      t   = a / 127                                   the row's scale
+ *      inv = 127 / a
+ *      r_d = x_d * inv
+ *      c_d = r_d is NaN ? 0 : (int8) rint_ties_even(min(max(r_d, -127), 127))
+ *    What follows from it, and is not special-cased: a zero row gives t = 0 and codes 0 (0 * inf is NaN); a row holding
+ *    +-inf gives t = inf and codes 0; a NaN element gives code 0; a row whose 127 / a overflows (a subnormal maximum)
+ *    gives codes +-127 and 0; -128 is never emitted.
+ *  Score.  dot = sum_d cq[i,d] cg[j,d] is an exact int32 sum, and
+ *      s[i,j] = ((float)dot * tq[i]) * tg[j]
+ *    with (float)dot rounded to nearest even and the two products rounded separately.  Row i of the output is
+ *    ore_topk_f32's order applied to s[i, :] (larger first, ties by lower gallery index, NaNs last by index), 1 <= k <=
+ *    min(G, 64); values are decoded from the keys (a NaN comes out as 0x7fc00000, -0 as +0).  The bits of s[i,j] depend
+ *    only on q[i,:], gallery[j,:] and scales[j] -- a consequence of exactness, not of a fixed order of the d.
+ *  ore_gallery_i8: src is a contiguous DEVICE f32 array [G, D], dst a contiguous DEVICE int8 array [G, D], scales a
+ *    DEVICE f32 array [G]; one launch.  Checks: null src / dst / scales, G and D in 1..2^31-1, then the context.
+ *  ore_nearest_i8: q is f32 exactly as for ore_nearest_f16 (2-D to 4-D, q->nstride >= D honoured, any 4-byte aligned
+ *    base) and is quantised inside the kernel: no int8 copy of q is written to memory.  gallery is a contiguous DEVICE
+ *    int8 array [G, D] at any byte alignment, scales a DEVICE f32 array [G].  A caller's own gallery may use any code,
+ *    -128 included, and any scales: the scales are not checked.  127 * 128 * D must stay below 2^31: D <= 131072.
+ *    Checks: ore_nearest_f32's in their order, then a null scales, then D > 131072 (ORE_ERR_INVALID, "D" in the
+ *    message), then the context.  Apart from q, the codes and the scales nothing is read.  n == 0, the partial buffer
+ *    with its capture rule and ore_ctx_set_alloc_fill are ore_nearest_f32's.
+ *  ore_nearest_segments_i8: the gallery segments of such a call with n queries and G rows on this context's device,
+ *    and the gallery rows one workgroup takes per step. */
+ore_status ore_gallery_i8(ore_ctx* ctx, const float* src, int64_t G, int64_t D, int8_t* dst, float* scales);
+ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G, int32_t k,
+                          float* values, int32_t* indices);
+ore_status ore_nearest_segments_i8(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows);
 ore_status ore_model_embed_dim(ore_model* m, int64_t* dim);
 ore_status ore_model_set_embed(ore_model* m, float* d_embed, int64_t cap_elems, int32_t flags);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);

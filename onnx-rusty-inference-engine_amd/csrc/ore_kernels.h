@@ -619,6 +619,17 @@ int nearest_f16_step_rows();
 void launch_nearest_f16(const float* q, long long q_stride, int n, int D, const void* gallery, long long G, int k, int S,
                         void* part, float* values, int* indices, hipStream_t s);
 void launch_gallery_f16(const float* src, long long G, long long D, void* dst, hipStream_t s);
+// the same search on an int8 gallery with one f32 scale per row (ore_nearest_i8.hip): s[i, j] = ((float)dot * tq[i]) *
+// scales[j], dot the exact int32 sum of code products on the int8 matrix cores, the query rows quantised inside the
+// kernel by include/ore.h's rule; gallery contiguous int8 [G][D] at any alignment, D <= nearest_i8_max_d(); S =
+// nearest_i8_segments(n, G, CUs), part as above.  launch_gallery_i8: contiguous f32 [G][D] -> codes [G][D] and
+// scales [G] by the same rule, one launch.
+int nearest_i8_segments(long long n, long long G, int ncu);
+int nearest_i8_step_rows();
+int nearest_i8_max_d();
+void launch_nearest_i8(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
+                       int k, int S, void* part, float* values, int* indices, hipStream_t s);
+void launch_gallery_i8(const float* src, long long G, long long D, void* dst, float* scales, hipStream_t s);
 // rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 

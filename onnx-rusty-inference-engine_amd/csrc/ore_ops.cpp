@@ -888,7 +888,7 @@ ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, i
   return ORE_OK;
 }
 
-// ore_nearest_f32 / ore_nearest_f16: the checks that need no context, in the header's order (ORE_OK: n and D are set)
+// ore_nearest_f32 / ore_nearest_f16 / ore_nearest_i8: the checks that need no context, in the header's order (ORE_OK: n and D are set)
 static ore_status nearest_check(ore_ctx* ctx, const ore_tensor* q, const void* gallery, int64_t G, int32_t k, const float* values,
                                 const int32_t* indices, int64_t* n_out, int64_t* D_out) {
   if (!q || !q->data || !gallery || !values || !indices) return set_error(ctx, ORE_ERR_INVALID, "null argument");
@@ -910,7 +910,7 @@ static ore_status nearest_check(ore_ctx* ctx, const ore_tensor* q, const void* g
   return ORE_OK;
 }
 
-// the partial keys [n][S][k] of both entries, grown on demand as the weight scratch is -- but never inside a capture
+// the partial keys [n][S][k] of the three entries, grown on demand as the weight scratch is -- but never inside a capture
 static ore_status nearest_grow_part(ore_ctx* ctx, size_t need) {
   if (need <= ctx->nearest_bytes) return ORE_OK;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -973,6 +973,43 @@ ore_status ore_gallery_f16(ore_ctx* ctx, const float* src, int64_t G, int64_t D,
   if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   launch_gallery_f16(src, G, D, dst, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G, int32_t k,
+                          float* values, int32_t* indices) {
+  int64_t n = 0, D = 0;
+  if (const ore_status st = nearest_check(ctx, q, gallery, G, k, values, indices, &n, &D)) return st;
+  if (!scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (D > nearest_i8_max_d())  // 127 * 128 * D stays below 2^31
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: D = %lld above %d, the int32 dot product's limit", (long long)D, nearest_i8_max_d());
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int S = nearest_i8_segments(n, G, ctx->ncu);
+  if (const ore_status st = nearest_grow_part(ctx, nearest_partial_bytes(n, S, k))) return st;
+  launch_nearest_i8(q->data, nstride_of(q), int(n), int(D), gallery, scales, G, int(k), S, ctx->nearest_part, values, indices,
+                    ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_segments_i8(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
+  if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
+  *segments = nearest_i8_segments(n, G, ctx->ncu);
+  *step_rows = nearest_i8_step_rows();
+  return ORE_OK;
+}
+
+ore_status ore_gallery_i8(ore_ctx* ctx, const float* src, int64_t G, int64_t D, int8_t* dst, float* scales) {
+  if (!src || !dst || !scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (G < 1 || G >= (int64_t(1) << 31) || D < 1 || D >= (int64_t(1) << 31))
+    return set_error(ctx, ORE_ERR_INVALID, "gallery: G = %lld, D = %lld outside 1..2^31-1", (long long)G, (long long)D);
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_gallery_i8(src, G, D, dst, scales, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

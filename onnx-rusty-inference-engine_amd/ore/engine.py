@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "gallery_i8", "nearest_segments_i8", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -926,18 +926,30 @@ def topk_mean(ctx: Context, x, views: int, k: int):
     return values, indices
 
 
-def nearest(ctx: Context, q, gallery, k: int):
-    """ore_nearest_f32 / ore_nearest_f16 (extension): for every row of q [n, D] the k rows of gallery [G, D] with the
-    largest inner product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the scores -- the
-    [n, G] score matrix is never formed.  q is float32 and may be a row slice (q.stride(0) >= D, rows dense); gallery
-    is contiguous, float32 or float16 (gallery_f16(): q is then rounded to f16 inside the kernel, f32 accumulation on
-    the f16 matrix cores).  The bits of a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise
-    both sides for cosine similarity."""
+def nearest(ctx: Context, q, gallery, k: int, scales=None):
+    """ore_nearest_f32 / ore_nearest_f16 / ore_nearest_i8 (extension): for every row of q [n, D] the k rows of gallery
+    [G, D] with the largest inner product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the
+    scores -- the [n, G] score matrix is never formed.  q is float32 and may be a row slice (q.stride(0) >= D, rows
+    dense); gallery is contiguous, float32, float16 (gallery_f16(): q is then rounded to f16 inside the kernel, f32
+    accumulation on the f16 matrix cores) or int8 with scales, a contiguous float32 [G] (gallery_i8(): q is then
+    quantised per row inside the kernel, the code products summed exactly on the int8 matrix cores and scaled by the two
+    rows' scales).  The bits of a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise both sides
+    for cosine similarity."""
     torch = _torch()
-    f16 = isinstance(gallery, torch.Tensor) and gallery.dtype == torch.float16
-    for name, t, dt in (("q", q, torch.float32), ("gallery", gallery, torch.float16 if f16 else torch.float32)):
+    gdt = gallery.dtype if isinstance(gallery, torch.Tensor) and gallery.dtype in (torch.float16, torch.int8) else torch.float32
+    names = {torch.float32: "float32", torch.float16: "float16", torch.int8: "int8"}
+    if gdt != torch.int8 and scales is not None:
+        raise OreError(1, f"scales: given with a {names[gdt]} gallery; only an int8 gallery has scales")
+    if gdt == torch.int8:  # the scales first: a call without them stays as it was
+        rows = int(gallery.shape[0]) if gallery.dim() else 0
+        if scales is None:
+            raise OreError(1, "scales: an int8 gallery needs its scales (gallery_i8() returns both)")
+        if (not isinstance(scales, torch.Tensor) or scales.dtype != torch.float32 or tuple(scales.shape) != (rows,)
+                or not scales.is_contiguous() or not scales.is_cuda or scales.device.index != ctx.device):
+            raise OreError(1, f"scales: expected a contiguous float32 [{rows}] CUDA tensor on cuda:{ctx.device}")
+    for name, t, dt in (("q", q, torch.float32), ("gallery", gallery, gdt)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or t.dim() != 2:
-            raise OreError(1, f"{name}: expected a 2-D {'float16' if dt == torch.float16 else 'float32'} CUDA tensor")
+            raise OreError(1, f"{name}: expected a 2-D {names[dt]} CUDA tensor")
         if t.device.index != ctx.device:
             raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
     n, D = int(q.shape[0]), int(q.shape[1])
@@ -955,9 +967,13 @@ def nearest(ctx: Context, q, gallery, k: int):
     d = Tensor()
     d.data, d.ndim, d.nstride = q.data_ptr(), 2, (int(q.stride(0)) if n > 1 else 0)
     d.dims[0], d.dims[1] = n, D
-    entry = load().ore_nearest_f16 if f16 else load().ore_nearest_f32
-    check(entry(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), G, int(k),
-                ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr())), ctx.h)
+    out = (G, int(k), ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr()))
+    if gdt == torch.int8:
+        check(load().ore_nearest_i8(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()),
+                                    ctypes.c_void_p(scales.data_ptr()), *out), ctx.h)
+    else:
+        entry = load().ore_nearest_f16 if gdt == torch.float16 else load().ore_nearest_f32
+        check(entry(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), *out), ctx.h)
     return values, indices
 
 
@@ -988,6 +1004,31 @@ def nearest_segments_f16(ctx: Context, n: int, G: int):
     gallery."""
     s, r = ctypes.c_int32(), ctypes.c_int32()
     check(load().ore_nearest_segments_f16(ctx.h, int(n), int(G), ctypes.byref(s), ctypes.byref(r)), ctx.h)
+    return s.value, r.value
+
+
+def gallery_i8(ctx: Context, gallery):
+    """ore_gallery_i8: a contiguous float32 [G, D] gallery as (codes torch.int8 [G, D], scales torch.float32 [G]) for
+    nearest(): per row the scale is max|x| / 127 (NaNs skipped) and a code is x * (127 / max|x|) rounded to nearest
+    even, every operation rounded on its own; a NaN element, a zero row and a row holding an inf give codes 0."""
+    torch = _torch()
+    if (not isinstance(gallery, torch.Tensor) or not gallery.is_cuda or gallery.dtype != torch.float32 or gallery.dim() != 2
+            or not gallery.is_contiguous() or gallery.numel() == 0):
+        raise OreError(1, "gallery: expected a contiguous, non-empty 2-D float32 CUDA tensor")
+    if gallery.device.index != ctx.device:
+        raise OreError(1, f"gallery: on cuda:{gallery.device.index}, the context is on cuda:{ctx.device}")
+    codes = torch.empty(gallery.shape, dtype=torch.int8, device=gallery.device)
+    scales = torch.empty((gallery.shape[0],), dtype=torch.float32, device=gallery.device)
+    check(load().ore_gallery_i8(ctx.h, ctypes.c_void_p(gallery.data_ptr()), int(gallery.shape[0]), int(gallery.shape[1]),
+                                ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(scales.data_ptr())), ctx.h)
+    return codes, scales
+
+
+def nearest_segments_i8(ctx: Context, n: int, G: int):
+    """ore_nearest_segments_i8: (gallery segments, gallery rows a workgroup takes per step) of nearest() on an int8
+    gallery."""
+    s, r = ctypes.c_int32(), ctypes.c_int32()
+    check(load().ore_nearest_segments_i8(ctx.h, int(n), int(G), ctypes.byref(s), ctypes.byref(r)), ctx.h)
     return s.value, r.value
 
 

@@ -7,12 +7,18 @@
      Beside them the same search on the packed f16 copy of the gallery (ore.gallery_f16), the three alternating
      inside a round: its floors are the read at 2 bytes per element and the FLOPs at --mfma-f16-tflops (the f16
      matrix peak), with the share of rows on which the f16 and the f32 search return the same index set.
+     And the same search on the int8 copy with a scale per row (ore.gallery_i8), the four alternating inside a round:
+     its floors are the read of G D bytes of codes and 4 G bytes of scales per query tile, and the operations at
+     --mfma-i8-tops (the dense int8 matrix peak of AMD's MI355X data sheet, 5.0 POPS: twice the f16 figure, as
+     v_mfma_i32_16x16x64_i8 has twice the k-depth of v_mfma_f32_16x16x32_f16 at the same issue rate); with the share
+     of rows on which the int8 and the f32 search return the same index set, the mean overlap of the two sets, and
+     the ratio to the f16 search of the same rounds beside the two min - max spreads it has to exceed.
  (b) Model.classify_into (SqueezeNet at --hw, --batch images, k = 5, f32 and f16, autotuned, set_streams(2)) with
      the normalised embedding on against off.
 Every figure is the median over --rounds windows of back-to-back calls timed by HIP events on the context stream,
 with the smallest and largest window beside it; the variants of one comparison alternate inside a round.  Needs an
 MI355X (no fallback).
-usage: python tools/bench_nearest.py [--batch 256] [--hw 224] [--rounds 9] [--out FILE]"""
+usage: python tools/bench_nearest.py [--batch 256] [--hw 224] [--rounds 9] [--skip-model] [--out FILE]"""
 import argparse
 import json
 import os
@@ -35,6 +41,8 @@ def main():
     ap.add_argument("--hbm-tbs", type=float, default=8.0)
     ap.add_argument("--mfma-tflops", type=float, default=157.3)
     ap.add_argument("--mfma-f16-tflops", type=float, default=2500.0)
+    ap.add_argument("--mfma-i8-tops", type=float, default=5000.0)
+    ap.add_argument("--skip-model", action="store_true", help="part (a) only")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -45,22 +53,39 @@ def main():
     ctx = ore.Context(0)
     gen = torch.Generator(device="cuda").manual_seed(1000)
     res = {"tool": "bench_nearest", "D": D, "k": K, "rounds": a.rounds, "hbm_tbs": a.hbm_tbs, "mfma_tflops": a.mfma_tflops,
-           "mfma_f16_tflops": a.mfma_f16_tflops, "nearest": {}, "nearest_f16": {}, "model": {}}
+           "mfma_f16_tflops": a.mfma_f16_tflops, "mfma_i8_tops": a.mfma_i8_tops, "nearest": {}, "nearest_f16": {}, "nearest_i8": {},
+           "model": {}}
     for G in (10 ** 4, 10 ** 6):
         g = torch.nn.functional.normalize(torch.randn((G, D), device="cuda", generator=gen))
         gh = ore.gallery_f16(ctx, g)
+        gi, si = ore.gallery_i8(ctx, g)
         for n in (1, 32, 256):
             q = torch.nn.functional.normalize(torch.randn((n, D), device="cuda", generator=gen))
             reps = 20 if G * n <= 10 ** 7 else 3
             r = alternate({"ore_nearest": (lambda: ore.nearest(ctx, q, g, K), reps),
                            "ore_nearest_f16": (lambda: ore.nearest(ctx, q, gh, K), reps),
+                           "ore_nearest_i8": (lambda: ore.nearest(ctx, q, gi, K, scales=si), reps),
                            "matmul_topk": (lambda: torch.topk(q @ g.T, K, dim=1), reps)}, a.rounds)
             ours, theirs = ore.nearest(ctx, q, g, K)[1], torch.topk(q @ g.T, K, dim=1)[1]
             halves = ore.nearest(ctx, q, gh, K)[1]
+            bytes_ = ore.nearest(ctx, q, gi, K, scales=si)[1]
             torch.cuda.synchronize()
             same = (ours.long().sort(1)[0] == theirs.sort(1)[0]).all(1).float().mean()
             same_h = (ours.sort(1)[0] == halves.sort(1)[0]).all(1).float().mean()
-            h = r.pop("ore_nearest_f16")
+            same_i = (ours.sort(1)[0] == bytes_.sort(1)[0]).all(1).float().mean()
+            overlap_i = (ours[:, :, None] == bytes_[:, None, :]).any(2).float().mean()
+            h, b = r.pop("ore_nearest_f16"), r.pop("ore_nearest_i8")
+            read_b, mfma_b = -(-n // 64) * (G * D + 4 * G) / (a.hbm_tbs * 1e6), 2.0 * n * G * D / (a.mfma_i8_tops * 1e6)
+            segments_b, step_rows_b = ore.nearest_segments_i8(ctx, n, G)
+            spread = max(h["max_us"] - h["min_us"], b["max_us"] - b["min_us"])
+            res["nearest_i8"][f"n{n}_G{G}"] = dict(
+                b, segments=segments_b, step_rows=step_rows_b, floor_read_us=round(read_b, 2), floor_mfma_us=round(mfma_b, 2),
+                bound="mfma" if mfma_b > read_b else "read", share_of_floor=round(max(read_b, mfma_b) / b["us"], 4),
+                gallery_gbs=round(-(-n // 64) * (G * D + 4 * G) / b["us"] / 1e3, 1), tops=round(2.0 * n * G * D / b["us"] / 1e6, 2),
+                speedup_vs_f16=round(h["us"] / b["us"], 3), speedup_vs_f32=round(r["ore_nearest"]["us"] / b["us"], 3),
+                f16_minus_i8_us=round(h["us"] - b["us"], 2), larger_window_spread_us=round(spread, 2),
+                faster_than_f16=bool(h["us"] - b["us"] > spread),
+                same_index_set_share_vs_f32=round(float(same_i), 4), mean_overlap_vs_f32=round(float(overlap_i), 4))
             read_h, mfma_h = -(-n // 64) * G * D * 2 / (a.hbm_tbs * 1e6), 2.0 * n * G * D / (a.mfma_f16_tflops * 1e6)
             segments_h, step_rows = ore.nearest_segments_f16(ctx, n, G)
             res["nearest_f16"][f"n{n}_G{G}"] = dict(
@@ -78,10 +103,10 @@ def main():
                 bound="mfma" if mfma_us > read_us else "read", share_of_floor=round(max(read_us, mfma_us) / us, 4),
                 gallery_gbs=round(-(-n // 64) * G * D * 4 / us / 1e3, 1), tflops=round(2.0 * n * G * D / us / 1e6, 2),
                 speedup=round(r["matmul_topk"]["us"] / us, 3), same_index_set_share=round(float(same), 4))
-        del g, gh
+        del g, gh, gi, si
     B, S = a.batch, a.hw
     x = torch.randn((B, 3, S, S), device="cuda", generator=gen)
-    for precision in ("f32", "f16"):
+    for precision in () if a.skip_model else ("f32", "f16"):
         m = ore.Model(ctx, squeezenet.build(S), max_batch=B, precision=precision)
         m.set_streams(2)
         m.set_topk(K)
