@@ -600,32 +600,29 @@ void launch_cam_boxes_f32(const float* maps, long long planes, int hm, int wm, i
 // nearest neighbours by inner product (ore_nearest.hip): for query row i of q (row i at q + i * q_stride, q_stride
 // >= D, any 4-byte aligned base) the k best of s[i, j] = sum_d q[i, d] gallery[j, d] over the contiguous gallery
 // [G][D], in launch_topk's order, as contiguous values / indices [n][k]; 1 <= k <= min(G, 64), G < 2^31.  The bits
-// of s[i, j] depend on the two rows alone.  S = nearest_segments(n, G, CUs of the device) gallery segments; with
-// S > 1 `part` holds nearest_partial_bytes(n, S, k) bytes (every byte read was written by the same call) and a
-// second launch merges.
-int nearest_segments(long long n, long long G, int ncu);
+// of s[i, j] depend on the two rows alone.  S = nearest_segments(n, G, CUs of the device, nearest_step_rows(format))
+// gallery segments, nearest_step_rows being the gallery rows a workgroup takes per step; with S > 1 `part` holds
+// nearest_partial_bytes(n, S, k) bytes (every byte read was written by the same call) and a second launch merges.
+// The three launches have one signature; `scales` is null but for the int8 gallery.
+enum class NearestFmt { F32, F16, I8 };
+int nearest_step_rows(NearestFmt f);
+int nearest_segments(long long n, long long G, int ncu, int step_rows);
 size_t nearest_partial_bytes(long long n, int S, int k);
-void launch_nearest(const float* q, long long q_stride, int n, int D, const float* gallery, long long G, int k, int S,
-                    void* part, float* values, int* indices, hipStream_t s);
+void launch_nearest(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G, int k,
+                    int S, void* part, float* values, int* indices, hipStream_t s);
 // the merge of part[n][S][k] (k keys per segment, descending, 0 from the first empty slot on; 2 <= S <= 512) into
-// values / indices: the second launch of launch_nearest and of launch_nearest_f16
+// values / indices: the second launch of the three searches
 void launch_nearest_merge(const void* part, long long n, int S, int k, float* values, int* indices, hipStream_t s);
 // the same search on an f16 gallery (ore_nearest_f16.hip): s[i, j] = sum_d RNE_f16(q[i, d]) gallery[j, d] on the f16
-// matrix cores, q as above, gallery contiguous binary16 [G][D] at any 2-byte aligned base; S =
-// nearest_f16_segments(n, G, CUs), part as above.  nearest_f16_step_rows: the gallery rows a workgroup takes per step.
+// matrix cores, q as above, gallery contiguous binary16 [G][D] at any 2-byte aligned base.
 // launch_gallery_f16: contiguous f32 [G][D] -> binary16 [G][D], round to nearest even, no clamp, one launch.
-int nearest_f16_segments(long long n, long long G, int ncu);
-int nearest_f16_step_rows();
-void launch_nearest_f16(const float* q, long long q_stride, int n, int D, const void* gallery, long long G, int k, int S,
-                        void* part, float* values, int* indices, hipStream_t s);
+void launch_nearest_f16(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
+                        int k, int S, void* part, float* values, int* indices, hipStream_t s);
 void launch_gallery_f16(const float* src, long long G, long long D, void* dst, hipStream_t s);
 // the same search on an int8 gallery with one f32 scale per row (ore_nearest_i8.hip): s[i, j] = ((float)dot * tq[i]) *
 // scales[j], dot the exact int32 sum of code products on the int8 matrix cores, the query rows quantised inside the
-// kernel by include/ore.h's rule; gallery contiguous int8 [G][D] at any alignment, D <= nearest_i8_max_d(); S =
-// nearest_i8_segments(n, G, CUs), part as above.  launch_gallery_i8: contiguous f32 [G][D] -> codes [G][D] and
-// scales [G] by the same rule, one launch.
-int nearest_i8_segments(long long n, long long G, int ncu);
-int nearest_i8_step_rows();
+// kernel by include/ore.h's rule; gallery contiguous int8 [G][D] at any alignment, D <= nearest_i8_max_d().
+// launch_gallery_i8: contiguous f32 [G][D] -> codes [G][D] and scales [G] by the same rule, one launch.
 int nearest_i8_max_d();
 void launch_nearest_i8(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
                        int k, int S, void* part, float* values, int* indices, hipStream_t s);

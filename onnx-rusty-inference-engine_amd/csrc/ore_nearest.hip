@@ -34,57 +34,25 @@
 // segment held fewer rows) to part[n][S][k]; nearest_merge_kernel, one wave per query, merges the S sorted
 // lists through their heads held in registers (S + k keys read).  Every slot of part it reads was written by the
 // first kernel.  values are decoded from the keys (topk_key_bits).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <atomic>
 
-#include "ore_kernels.h"
-#include "ore_topk_key.h"
+#include "ore_nearest.h"
 
 namespace ore {
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-constexpr int NN_QT = 64;             // queries per workgroup
 constexpr int NN_GT = 64;             // gallery rows per step
 constexpr int NN_KC = 32;             // d per staged chunk
 constexpr int NN_PITCH = NN_KC + 4;   // LDS row pitch in floats
 constexpr int NN_CB = NN_GT;          // candidate slots per query
-constexpr int NN_SMAX = 512;           // segments at most: NN_ML lists per lane of the merge's wave
-constexpr int NN_ML = NN_SMAX / 64;
+constexpr int NN_ML = NN_SMAX / 64;    // lists per lane of the merge's wave
 constexpr int NN_STAGE = NN_QT * NN_PITCH;  // floats of one staged tile (NN_QT == NN_GT)
 static_assert(NN_QT == NN_GT && NN_QT * NN_KC == 2 * 256 * 4, "two 16-byte groups per thread, tile and chunk");
 
 // dynamic LDS: the two staged tiles, then per query the threshold, k keys, NN_CB candidates and the counter
 __host__ __device__ constexpr size_t nn_lds_bytes(int k) {
   return size_t(2) * NN_STAGE * 4 + size_t(NN_QT) * (8 + 8 * size_t(k) + 8 * NN_CB + 4);
-}
-
-struct NearestArgs {
-  const float* q;
-  const float* g;
-  u64* part;       // [n][S][k], S > 1
-  float* values;   // [n][k]
-  int* indices;
-  long long q_stride, G, seg_rows;  // seg_rows: gallery rows per segment, a multiple of NN_GT
-  int n, D, k, S;
-};
-
-// four consecutive d of a row, masked: nothing past D or of a row that is not there is read
-template <bool VEC>
-__device__ __forceinline__ floatx4 nn_load4(bool row_ok, const float* __restrict__ row, int d, int D) {
-  floatx4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (VEC) {  // D % 4 == 0: the group is inside the row or outside it
-    if (row_ok && d < D) v = *reinterpret_cast<const floatx4*>(row + d);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (row_ok && d + e < D) v[e] = row[d + e];
-  }
-  return v;
 }
 
 template <bool VQ, bool VG>  // 16-byte loads of the queries / of the gallery
@@ -104,6 +72,7 @@ __global__ __launch_bounds__(256) void nearest_kernel(NearestArgs p) {
   const long long jbeg = (long long)seg * p.seg_rows, jend = min(p.G, jbeg + p.seg_rows);
   const int nsteps = int((jend - jbeg + NN_GT - 1) / NN_GT);  // >= 1: the launcher leaves no segment empty
   const int nchunks = (p.D + NN_KC - 1) / NN_KC;
+  const float* const g = static_cast<const float*>(p.g);
 
   for (int i = tid; i < NN_QT; i += 256) {
     sthr[i] = 0ull;
@@ -120,7 +89,7 @@ __global__ __launch_bounds__(256) void nearest_kernel(NearestArgs p) {
     for (int u = 0; u < 2; ++u) {
       const long long qi = q0 + srow + 32 * u, gj = j0 + srow + 32 * u;
       rq[u] = nn_load4<VQ>(qi < p.n, p.q + qi * p.q_stride, d, p.D);
-      rg[u] = nn_load4<VG>(gj < jend, p.g + gj * p.D, d, p.D);
+      rg[u] = nn_load4<VG>(gj < jend, g + gj * p.D, d, p.D);
     }
   };
 
@@ -256,18 +225,20 @@ __global__ __launch_bounds__(256) void l2_normalize_kernel(float* __restrict__ e
   for (int i = lane; i < C; i += 64) er[i] = er[i] / norm;
 }
 
-template <bool VQ, bool VG>
-void nearest_launch(const NearestArgs& a, hipStream_t s) {
-  static std::atomic<unsigned long long> raised{0};
-  ore_raise_lds_once(raised, reinterpret_cast<const void*>(nearest_kernel<VQ, VG>), int(nn_lds_bytes(64)));
-  const dim3 grid((unsigned)((a.n + NN_QT - 1) / NN_QT), (unsigned)a.S);
-  hipLaunchKernelGGL((nearest_kernel<VQ, VG>), grid, dim3(256), nn_lds_bytes(a.k), s, a);
-}
+struct NearestF32 {
+  static constexpr int GT = NN_GT, VGE = 4;
+  static constexpr size_t LDS_MAX = nn_lds_bytes(64);
+  static constexpr size_t lds(int, int k) { return nn_lds_bytes(k); }
+  template <bool VQ, bool VG>
+  static auto kernel() { return &nearest_kernel<VQ, VG>; }
+};
 
 }  // namespace
 
-int nearest_segments(long long n, long long G, int ncu) {
-  const long long qt = std::max<long long>((n + NN_QT - 1) / NN_QT, 1), steps = (G + NN_GT - 1) / NN_GT;
+int nearest_step_rows(NearestFmt f) { return f == NearestFmt::F32 ? NN_GT : NS_GT; }
+
+int nearest_segments(long long n, long long G, int ncu, int step_rows) {
+  const long long qt = std::max<long long>((n + NN_QT - 1) / NN_QT, 1), steps = (G + step_rows - 1) / step_rows;
   // about two workgroups per CU, at most NN_SMAX segments (the merge's lists per lane) and a step each
   const long long want = std::min<long long>(std::min(std::max<long long>(2LL * ncu / qt, 1), steps), NN_SMAX);
   const long long per = (steps + want - 1) / want;
@@ -276,18 +247,9 @@ int nearest_segments(long long n, long long G, int ncu) {
 
 size_t nearest_partial_bytes(long long n, int S, int k) { return S > 1 ? size_t(n) * size_t(S) * size_t(k) * 8 : 0; }
 
-void launch_nearest(const float* q, long long q_stride, int n, int D, const float* gallery, long long G, int k, int S,
-                    void* part, float* values, int* indices, hipStream_t s) {
-  if (n <= 0) return;
-  const long long steps = (G + NN_GT - 1) / NN_GT, per = (steps + S - 1) / S;
-  const NearestArgs a{q, gallery, static_cast<u64*>(part), values, indices, q_stride, G, per * NN_GT, n, D, k, S};
-  const bool vg = D % 4 == 0 && (reinterpret_cast<uintptr_t>(gallery) & 15) == 0;
-  const bool vq = D % 4 == 0 && q_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(q) & 15) == 0;
-  if (vq && vg) nearest_launch<true, true>(a, s);
-  else if (vg) nearest_launch<false, true>(a, s);
-  else if (vq) nearest_launch<true, false>(a, s);
-  else nearest_launch<false, false>(a, s);
-  if (S > 1) launch_nearest_merge(part, n, S, k, values, indices, s);
+void launch_nearest(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G, int k,
+                    int S, void* part, float* values, int* indices, hipStream_t s) {
+  nearest_launch<NearestF32>(q, q_stride, n, D, gallery, scales, G, k, S, part, values, indices, s);
 }
 
 void launch_nearest_merge(const void* part, long long n, int S, int k, float* values, int* indices, hipStream_t s) {

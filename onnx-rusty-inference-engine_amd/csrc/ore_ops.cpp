@@ -929,41 +929,63 @@ static ore_status nearest_grow_part(ore_ctx* ctx, size_t need) {
   return ORE_OK;
 }
 
-ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, int32_t k, float* values,
-                           int32_t* indices) {
-  // the context last, as ore_topk_mean_f32: what can be judged without one is
+// the three searches: the checks in the header's order, the context last, as ore_topk_mean_f32 (what can be judged
+// without one is); `scales` is the int8 gallery's and is looked at for that format alone
+static ore_status nearest_run(ore_ctx* ctx, NearestFmt fmt, const ore_tensor* q, const void* gallery, const float* scales, int64_t G,
+                              int32_t k, float* values, int32_t* indices) {
   int64_t n = 0, D = 0;
   if (const ore_status st = nearest_check(ctx, q, gallery, G, k, values, indices, &n, &D)) return st;
+  if (fmt == NearestFmt::I8) {
+    if (!scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+    if (D > nearest_i8_max_d())  // 127 * 128 * D stays below 2^31
+      return set_error(ctx, ORE_ERR_INVALID, "nearest: D = %lld above %d, the int32 dot product's limit", (long long)D, nearest_i8_max_d());
+  }
   if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (n == 0) return ORE_OK;
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const int S = nearest_segments(n, G, ctx->ncu);
+  const int S = nearest_segments(n, G, ctx->ncu, nearest_step_rows(fmt));
   if (const ore_status st = nearest_grow_part(ctx, nearest_partial_bytes(n, S, k))) return st;
-  launch_nearest(q->data, nstride_of(q), int(n), int(D), gallery, G, int(k), S, ctx->nearest_part, values, indices, ctx->stream);
+  const auto launch = fmt == NearestFmt::I8 ? launch_nearest_i8 : fmt == NearestFmt::F16 ? launch_nearest_f16 : launch_nearest;
+  launch(q->data, nstride_of(q), int(n), int(D), gallery, scales, G, int(k), S, ctx->nearest_part, values, indices, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
+}
+
+ore_status ore_nearest_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, int32_t k, float* values,
+                           int32_t* indices) {
+  return nearest_run(ctx, NearestFmt::F32, q, gallery, nullptr, G, k, values, indices);
 }
 
 ore_status ore_nearest_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, int32_t k, float* values,
                            int32_t* indices) {
-  int64_t n = 0, D = 0;
-  if (const ore_status st = nearest_check(ctx, q, gallery, G, k, values, indices, &n, &D)) return st;
-  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (n == 0) return ORE_OK;
-  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const int S = nearest_f16_segments(n, G, ctx->ncu);
-  if (const ore_status st = nearest_grow_part(ctx, nearest_partial_bytes(n, S, k))) return st;
-  launch_nearest_f16(q->data, nstride_of(q), int(n), int(D), gallery, G, int(k), S, ctx->nearest_part, values, indices, ctx->stream);
-  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return nearest_run(ctx, NearestFmt::F16, q, gallery, nullptr, G, k, values, indices);
+}
+
+ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G, int32_t k,
+                          float* values, int32_t* indices) {
+  return nearest_run(ctx, NearestFmt::I8, q, gallery, scales, G, k, values, indices);
+}
+
+// the three ore_nearest_segments entries: segments and the format's gallery rows per step
+static ore_status nearest_split(ore_ctx* ctx, NearestFmt fmt, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
+  if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
+  *step_rows = nearest_step_rows(fmt);
+  *segments = nearest_segments(n, G, ctx->ncu, *step_rows);
   return ORE_OK;
 }
 
+ore_status ore_nearest_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments) {
+  int32_t step_rows = 0;
+  return nearest_split(ctx, NearestFmt::F32, n, G, segments, &step_rows);
+}
+
 ore_status ore_nearest_segments_f16(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
-  if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
-  *segments = nearest_f16_segments(n, G, ctx->ncu);
-  *step_rows = nearest_f16_step_rows();
-  return ORE_OK;
+  return nearest_split(ctx, NearestFmt::F16, n, G, segments, step_rows);
+}
+
+ore_status ore_nearest_segments_i8(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
+  return nearest_split(ctx, NearestFmt::I8, n, G, segments, step_rows);
 }
 
 ore_status ore_gallery_f16(ore_ctx* ctx, const float* src, int64_t G, int64_t D, uint16_t* dst) {
@@ -977,32 +999,6 @@ ore_status ore_gallery_f16(ore_ctx* ctx, const float* src, int64_t G, int64_t D,
   return ORE_OK;
 }
 
-ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G, int32_t k,
-                          float* values, int32_t* indices) {
-  int64_t n = 0, D = 0;
-  if (const ore_status st = nearest_check(ctx, q, gallery, G, k, values, indices, &n, &D)) return st;
-  if (!scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (D > nearest_i8_max_d())  // 127 * 128 * D stays below 2^31
-    return set_error(ctx, ORE_ERR_INVALID, "nearest: D = %lld above %d, the int32 dot product's limit", (long long)D, nearest_i8_max_d());
-  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (n == 0) return ORE_OK;
-  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const int S = nearest_i8_segments(n, G, ctx->ncu);
-  if (const ore_status st = nearest_grow_part(ctx, nearest_partial_bytes(n, S, k))) return st;
-  launch_nearest_i8(q->data, nstride_of(q), int(n), int(D), gallery, scales, G, int(k), S, ctx->nearest_part, values, indices,
-                    ctx->stream);
-  ORE_HIP_CHECK(ctx, hipGetLastError());
-  return ORE_OK;
-}
-
-ore_status ore_nearest_segments_i8(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
-  if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
-  *segments = nearest_i8_segments(n, G, ctx->ncu);
-  *step_rows = nearest_i8_step_rows();
-  return ORE_OK;
-}
-
 ore_status ore_gallery_i8(ore_ctx* ctx, const float* src, int64_t G, int64_t D, int8_t* dst, float* scales) {
   if (!src || !dst || !scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (G < 1 || G >= (int64_t(1) << 31) || D < 1 || D >= (int64_t(1) << 31))
@@ -1011,13 +1007,6 @@ ore_status ore_gallery_i8(ore_ctx* ctx, const float* src, int64_t G, int64_t D, 
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   launch_gallery_i8(src, G, D, dst, scales, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
-  return ORE_OK;
-}
-
-ore_status ore_nearest_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments) {
-  if (!ctx || !segments) return set_error(ctx, ORE_ERR_INVALID, "null argument");
-  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
-  *segments = nearest_segments(n, G, ctx->ncu);
   return ORE_OK;
 }
 

@@ -984,27 +984,36 @@ def nearest_segments(ctx: Context, n: int, G: int) -> int:
     return s.value
 
 
-def gallery_f16(ctx: Context, gallery):
-    """ore_gallery_f16: a contiguous float32 [G, D] gallery as a torch.float16 [G, D] tensor for nearest() -- round
-    to nearest even, no clamp (past 65504: inf), subnormals kept."""
-    torch = _torch()
+def _check_gallery_f32(ctx, torch, gallery):
+    """The argument rule of gallery_f16() and gallery_i8()."""
     if (not isinstance(gallery, torch.Tensor) or not gallery.is_cuda or gallery.dtype != torch.float32 or gallery.dim() != 2
             or not gallery.is_contiguous() or gallery.numel() == 0):
         raise OreError(1, "gallery: expected a contiguous, non-empty 2-D float32 CUDA tensor")
     if gallery.device.index != ctx.device:
         raise OreError(1, f"gallery: on cuda:{gallery.device.index}, the context is on cuda:{ctx.device}")
+
+
+def gallery_f16(ctx: Context, gallery):
+    """ore_gallery_f16: a contiguous float32 [G, D] gallery as a torch.float16 [G, D] tensor for nearest() -- round
+    to nearest even, no clamp (past 65504: inf), subnormals kept."""
+    torch = _torch()
+    _check_gallery_f32(ctx, torch, gallery)
     out = torch.empty(gallery.shape, dtype=torch.float16, device=gallery.device)
     check(load().ore_gallery_f16(ctx.h, ctypes.c_void_p(gallery.data_ptr()), int(gallery.shape[0]), int(gallery.shape[1]),
                                  ctypes.c_void_p(out.data_ptr())), ctx.h)
     return out
 
 
+def _nearest_split(ctx, entry, n, G):
+    s, r = ctypes.c_int32(), ctypes.c_int32()
+    check(entry(ctx.h, int(n), int(G), ctypes.byref(s), ctypes.byref(r)), ctx.h)
+    return s.value, r.value
+
+
 def nearest_segments_f16(ctx: Context, n: int, G: int):
     """ore_nearest_segments_f16: (gallery segments, gallery rows a workgroup takes per step) of nearest() on a float16
     gallery."""
-    s, r = ctypes.c_int32(), ctypes.c_int32()
-    check(load().ore_nearest_segments_f16(ctx.h, int(n), int(G), ctypes.byref(s), ctypes.byref(r)), ctx.h)
-    return s.value, r.value
+    return _nearest_split(ctx, load().ore_nearest_segments_f16, n, G)
 
 
 def gallery_i8(ctx: Context, gallery):
@@ -1012,11 +1021,7 @@ def gallery_i8(ctx: Context, gallery):
     nearest(): per row the scale is max|x| / 127 (NaNs skipped) and a code is x * (127 / max|x|) rounded to nearest
     even, every operation rounded on its own; a NaN element, a zero row and a row holding an inf give codes 0."""
     torch = _torch()
-    if (not isinstance(gallery, torch.Tensor) or not gallery.is_cuda or gallery.dtype != torch.float32 or gallery.dim() != 2
-            or not gallery.is_contiguous() or gallery.numel() == 0):
-        raise OreError(1, "gallery: expected a contiguous, non-empty 2-D float32 CUDA tensor")
-    if gallery.device.index != ctx.device:
-        raise OreError(1, f"gallery: on cuda:{gallery.device.index}, the context is on cuda:{ctx.device}")
+    _check_gallery_f32(ctx, torch, gallery)
     codes = torch.empty(gallery.shape, dtype=torch.int8, device=gallery.device)
     scales = torch.empty((gallery.shape[0],), dtype=torch.float32, device=gallery.device)
     check(load().ore_gallery_i8(ctx.h, ctypes.c_void_p(gallery.data_ptr()), int(gallery.shape[0]), int(gallery.shape[1]),
@@ -1027,9 +1032,7 @@ def gallery_i8(ctx: Context, gallery):
 def nearest_segments_i8(ctx: Context, n: int, G: int):
     """ore_nearest_segments_i8: (gallery segments, gallery rows a workgroup takes per step) of nearest() on an int8
     gallery."""
-    s, r = ctypes.c_int32(), ctypes.c_int32()
-    check(load().ore_nearest_segments_i8(ctx.h, int(n), int(G), ctypes.byref(s), ctypes.byref(r)), ctx.h)
-    return s.value, r.value
+    return _nearest_split(ctx, load().ore_nearest_segments_i8, n, G)
 
 
 def class_maps(ctx: Context, x, w, bias, classes, relu: bool = True, views: int = 1):

@@ -175,3 +175,16 @@ def test_pooled_squeeze_occupancy():
     assert regs("pool_conv1x1_f32_kernelILi2ELi8ELi6ELi2E") <= 168
     assert regs("pool_conv1x1_f32_kernelILi1ELi0ELi0ELi1E") <= 512 // 6 // 8 * 8
     assert regs("conv_winol_kernel") <= 256
+
+
+@pytest.mark.skipif(not _tools() or not os.path.exists(os.path.join(LLVM, "llvm-readelf")),
+                    reason="ROCm binutils / objcopy not present")
+def test_nearest_kernels_have_no_scratch():
+    """The nearest-neighbour kernels hold a ring of gallery operands and 32 accumulators in registers; a spill to
+    scratch inside a turn of the ring is a defect.  Every kernel whose name contains
+    `nearest`: the f32 kernel, the streaming kernel's f16 and int8 instances, the merge."""
+    ore.load()
+    rows = {k: v for k, v in _kernel_meta().items() if "nearest" in k}
+    assert len(rows) >= 13, sorted(rows)  # 4 load-path instances of each of the three searches, and the merge
+    bad = {k: v["private_segment_fixed_size"] for k, v in rows.items() if v["private_segment_fixed_size"] != 0}
+    assert not bad, bad

@@ -33,9 +33,11 @@ def _ints(seed, n, G, D):
 
 
 # (n, G, D, k): every D of {1, 7, 8, 9, 33, 520} and 513 (one past the resident tile, two chunks), n of {1, 15, 17, 65},
-# G of {1, step - 1, step + 1, 1000, 4099} and k of {1, 5, min(G, 64)} at least once; the last on several segments
+# G of {1, step - 1, step + 1, 1000, 4099} and k of {1, 5, min(G, 64)} at least once; D = 1025 is three chunks of the
+# staged tile (512 + 512 + 1) on 2-byte gallery loads, every sum at most 64 * 1025 < 2^24; the last on several segments
 @pytest.mark.parametrize("n, G, D, k", [(1, 1, 1, 1), (15, 127, 7, 64), (17, 129, 8, 5), (65, 1000, 9, 64), (17, 4099, 33, 1),
-                                        (1, 1000, 520, 5), (15, 4099, 513, 64), (65, 129, 520, 1), (65, 40000, 8, 5)])
+                                        (1, 1000, 520, 5), (15, 4099, 513, 64), (65, 129, 520, 1), (17, 1000, 1025, 5),
+                                        (65, 40000, 8, 5)])
 def test_exact_with_ties(gpu_ctx, n, G, D, k):
     import ore
     segments, step = ore.nearest_segments_f16(gpu_ctx, n, G)
