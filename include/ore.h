@@ -1011,6 +1011,33 @@ ore_status ore_gallery_i8(ore_ctx* ctx, const float* src, int64_t G, int64_t D, 
 ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G, int32_t k,
                           float* values, int32_t* indices);
 ore_status ore_nearest_segments_i8(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows);
+/* Exact re-ranking of an approximate search (extension; ore_nearest_rerank.hip): the second stage
+ * behind a cheap search.  Take k' > k candidates from ore_nearest_i8 or ore_nearest_f16, rescore only those rows against
+ * the f32 (or the f16) gallery, keep the best k.
+ *  q is f32 exactly as for ore_nearest_f32 (2-D to 4-D, q->nstride >= D honoured, any 4-byte aligned base); gallery a
+ *    contiguous DEVICE array [G, D], f32 or binary16, at any element-aligned base; candidates a DEVICE int32 array, row
+ *    i of it the C entries at candidates + i * cand_stride; values and indices contiguous DEVICE arrays [n, k].
+ *    1 <= C <= 256, cand_stride >= C, 1 <= k <= min(C, 64).
+ *  Candidate rule.  An entry outside [0, G) is padding (pad with -1): nothing is read for it and it takes part in
+ *    nothing.  A row index that occurs more than once counts once.  When fewer than k distinct valid rows exist, the
+ *    ranks past them hold index -1 and the value bits 0x7fc00000.
+ *  Value rule.  The order among the valid rows is ore_topk_f32's over their scores: larger first, equal scores (-0
+ *    equal to +0) by lower gallery index, every NaN after every number, NaNs by index; values hold the bits of the
+ *    score, a NaN as 0x7fc00000 and -0 as +0.
+ *  Bit contract.  The value of (query i, row j) is, to the bit, what the search of the same gallery returns for that
+ *    pair: ore_nearest_f32 for the f32 gallery, ore_nearest_f16 (the query rounded to nearest even to f16 inside the
+ *    kernel) for the f16 gallery -- the same matrix instruction, order of the d and operand roles, and those bits depend
+ *    on the two rows alone.  So re-ranking the candidates of a search of the same gallery returns that search's values,
+ *    and re-ranking an int8 search's candidates against the f32 gallery returns the f32 search's values for them.
+ *  Checked from the arguments alone, before the context and any device call (ORE_ERR_INVALID, the message names the
+ *    quantity), in this order: null pointers; q not 2-D to 4-D (or n >= 2^31); D < 1; G < 1 or G >= 2^31; C outside
+ *    1..256; cand_stride < C; k outside 1..min(C, 64); the nstride rule at the top of this file.  n == 0 is ORE_OK and
+ *    launches nothing.  Offsets into the gallery are 64-bit.  One launch and no context-owned memory: legal inside a
+ *    stream capture. */
+ore_status ore_nearest_rerank_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, const int32_t* candidates,
+                                  int64_t cand_stride, int32_t C, int32_t k, float* values, int32_t* indices);
+ore_status ore_nearest_rerank_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, const int32_t* candidates,
+                                  int64_t cand_stride, int32_t C, int32_t k, float* values, int32_t* indices);
 ore_status ore_model_embed_dim(ore_model* m, int64_t* dim);
 ore_status ore_model_set_embed(ore_model* m, float* d_embed, int64_t cap_elems, int32_t flags);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);

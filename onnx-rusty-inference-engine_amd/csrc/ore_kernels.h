@@ -627,6 +627,12 @@ int nearest_i8_max_d();
 void launch_nearest_i8(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
                        int k, int S, void* part, float* values, int* indices, hipStream_t s);
 void launch_gallery_i8(const float* src, long long G, long long D, void* dst, float* scales, hipStream_t s);
+// the second stage of a search (ore_nearest_rerank.hip): for query row i the k best of the gallery rows candidates[i *
+// cand_stride + c], c < C <= 256, scored against the f32 or the f16 gallery (fmt F32 / F16) to the bits of that
+// gallery's search, in launch_topk's order; an entry outside [0, G) is padding, a row given twice counts once, and the
+// ranks past the distinct valid rows hold index -1 and the quiet NaN.  1 <= k <= min(C, 64).  One launch, no buffer.
+void launch_nearest_rerank(NearestFmt fmt, const float* q, long long q_stride, int n, int D, const void* gallery, long long G,
+                           const int* candidates, long long cand_stride, int C, int k, float* values, int* indices, hipStream_t s);
 // rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 

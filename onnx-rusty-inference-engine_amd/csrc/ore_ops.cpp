@@ -966,6 +966,46 @@ ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* galle
   return nearest_run(ctx, NearestFmt::I8, q, gallery, scales, G, k, values, indices);
 }
 
+// ore_nearest_rerank_f32 / ore_nearest_rerank_f16: the checks in the header's order, the context last; one launch
+static ore_status nearest_rerank_run(ore_ctx* ctx, NearestFmt fmt, const ore_tensor* q, const void* gallery, int64_t G,
+                                     const int32_t* candidates, int64_t cand_stride, int32_t C, int32_t k, float* values,
+                                     int32_t* indices) {
+  if (!q || !q->data || !gallery || !candidates || !values || !indices) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (q->ndim < 2 || q->ndim > 4 || q->dims[0] < 0 || !fits_i32(q->dims[0]))
+    return set_error(ctx, ORE_ERR_INVALID, "rerank: q of %d dims and %lld rows, expected [n, D] in 2 to 4 dims", int(q->ndim),
+                     (long long)(q->ndim >= 1 && q->ndim <= 4 ? q->dims[0] : 0));
+  const int64_t n = q->dims[0], lim = int64_t(1) << 31;
+  int64_t D = 1;
+  for (int i = 1; i < q->ndim; ++i) D = q->dims[i] >= 1 && D >= 1 && D * q->dims[i] < lim ? D * q->dims[i] : 0;
+  if (D < 1) return set_error(ctx, ORE_ERR_INVALID, "rerank: D, the row length of q, is not in 1..2^31-1");
+  if (G < 1 || G >= lim) return set_error(ctx, ORE_ERR_INVALID, "rerank: G = %lld outside 1..2^31-1", (long long)G);
+  if (C < 1 || C > 256) return set_error(ctx, ORE_ERR_INVALID, "rerank: C = %d candidates per query outside 1..256", int(C));
+  if (cand_stride < C)
+    return set_error(ctx, ORE_ERR_INVALID, "rerank: cand_stride %lld below C = %d", (long long)cand_stride, int(C));
+  if (k < 1 || k > std::min<int32_t>(C, 64))
+    return set_error(ctx, ORE_ERR_INVALID, "rerank: k = %d outside 1..%d (min(C, 64))", int(k), int(std::min<int32_t>(C, 64)));
+  if (q->nstride < 0 || (q->nstride && (q->nstride < D || q->nstride >= lim || !fits_i32(q->nstride * std::max<int64_t>(n, 1) + 256))))
+    return set_error(ctx, ORE_ERR_INVALID, "rerank: q->nstride %lld with %lld rows of %lld: below the row length or past 32-bit indexing",
+                     (long long)q->nstride, (long long)n, (long long)D);
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_nearest_rerank(fmt, q->data, nstride_of(q), int(n), int(D), gallery, G, candidates, cand_stride, int(C), int(k), values,
+                        indices, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_rerank_f32(ore_ctx* ctx, const ore_tensor* q, const float* gallery, int64_t G, const int32_t* candidates,
+                                  int64_t cand_stride, int32_t C, int32_t k, float* values, int32_t* indices) {
+  return nearest_rerank_run(ctx, NearestFmt::F32, q, gallery, G, candidates, cand_stride, C, k, values, indices);
+}
+
+ore_status ore_nearest_rerank_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, const int32_t* candidates,
+                                  int64_t cand_stride, int32_t C, int32_t k, float* values, int32_t* indices) {
+  return nearest_rerank_run(ctx, NearestFmt::F16, q, gallery, G, candidates, cand_stride, C, k, values, indices);
+}
+
 // the three ore_nearest_segments entries: segments and the format's gallery rows per step
 static ore_status nearest_split(ore_ctx* ctx, NearestFmt fmt, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
   if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");

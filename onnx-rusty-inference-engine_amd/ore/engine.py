@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "gallery_i8", "nearest_segments_i8", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "gallery_i8", "nearest_segments_i8", "rerank", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -926,7 +926,51 @@ def topk_mean(ctx: Context, x, views: int, k: int):
     return values, indices
 
 
-def nearest(ctx: Context, q, gallery, k: int, scales=None):
+def rerank(ctx: Context, q, gallery, candidates, k: int):
+    """ore_nearest_rerank_f32 / ore_nearest_rerank_f16 (extension): the second stage of a search.  For every row of q
+    [n, D] the k best of the gallery rows its row of candidates [n, C] names, scored against gallery [G, D] (float32 or
+    float16, contiguous) to the bits of nearest() on that gallery, as (values float32 [n, k], indices int32 [n, k]) in
+    topk()'s order.  candidates is int32 with candidates.stride(1) == 1 and candidates.stride(0) >= C, so a column slice
+    of a search's indices goes in as it is; an entry outside [0, G) is padding (pad with -1), a row named twice counts
+    once, and ranks past the distinct valid rows hold index -1 and a NaN.  1 <= C <= 256, 1 <= k <= min(C, 64)."""
+    torch = _torch()
+    gdt = torch.float16 if isinstance(gallery, torch.Tensor) and gallery.dtype == torch.float16 else torch.float32
+    names = {torch.float32: "float32", torch.float16: "float16", torch.int32: "int32"}
+    for name, t, dt in (("q", q, torch.float32), ("gallery", gallery, gdt), ("candidates", candidates, torch.int32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or t.dim() != 2:
+            raise OreError(1, f"{name}: expected a 2-D {names[dt]} CUDA tensor" + (" (or float16)" if name == "gallery" else ""))
+        if t.device.index != ctx.device:
+            raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
+    n, D = int(q.shape[0]), int(q.shape[1])
+    G, C = int(gallery.shape[0]), int(candidates.shape[1])
+    if int(gallery.shape[1]) != D or not gallery.is_contiguous():
+        raise OreError(1, f"gallery: expected a contiguous [G, {D}] tensor, got {tuple(gallery.shape)}")
+    if n > 1 and (q.stride(1) != 1 or q.stride(0) < D) or n <= 1 and not q.is_contiguous():
+        raise OreError(1, "q: expected dense rows at a row stride of at least D")
+    if int(candidates.shape[0]) != n or not 1 <= C <= 256:
+        raise OreError(1, f"candidates: expected [{n}, C] with C in 1..256, got {tuple(candidates.shape)}")
+    if C > 1 and candidates.stride(1) != 1 or n > 1 and candidates.stride(0) < C:
+        raise OreError(1, "candidates: expected dense rows at a row stride of at least C")
+    if not 1 <= int(k) <= min(C, 64):
+        raise OreError(1, f"k = {k} outside 1..{min(C, 64)} (min(C, 64))")
+    values = torch.empty((n, int(k)), dtype=torch.float32, device=q.device)
+    indices = torch.empty((n, int(k)), dtype=torch.int32, device=q.device)
+    if n == 0:
+        return values, indices
+    d = Tensor()
+    d.data, d.ndim, d.nstride = q.data_ptr(), 2, (int(q.stride(0)) if n > 1 else 0)
+    d.dims[0], d.dims[1] = n, D
+    entry = load().ore_nearest_rerank_f16 if gdt == torch.float16 else load().ore_nearest_rerank_f32
+    check(entry(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), G, ctypes.c_void_p(candidates.data_ptr()),
+                int(candidates.stride(0)) if n > 1 else C, C, int(k), ctypes.c_void_p(values.data_ptr()),
+                ctypes.c_void_p(indices.data_ptr())), ctx.h)
+    return values, indices
+
+
+_rerank = rerank  # nearest() has a parameter of this name
+
+
+def nearest(ctx: Context, q, gallery, k: int, scales=None, rerank=None, candidates=None):
     """ore_nearest_f32 / ore_nearest_f16 / ore_nearest_i8 (extension): for every row of q [n, D] the k rows of gallery
     [G, D] with the largest inner product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the
     scores -- the [n, G] score matrix is never formed.  q is float32 and may be a row slice (q.stride(0) >= D, rows
@@ -934,7 +978,23 @@ def nearest(ctx: Context, q, gallery, k: int, scales=None):
     accumulation on the f16 matrix cores) or int8 with scales, a contiguous float32 [G] (gallery_i8(): q is then
     quantised per row inside the kernel, the code products summed exactly on the int8 matrix cores and scaled by the two
     rows' scales).  The bits of a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise both sides
-    for cosine similarity."""
+    for cosine similarity.
+    Two-stage form: with `rerank`, a float32 or float16 [G, D] gallery of the same G and D, the search above is run with
+    `candidates` results per query (default min(G, 64, 8 k); in k..min(G, 64)) and rerank() of those against `rerank`
+    is returned, [n, k].  `candidates` without `rerank` is an error."""
+    if rerank is None and candidates is not None:
+        raise OreError(1, "candidates: given without rerank; only the two-stage form has candidates")
+    if rerank is not None:
+        torch = _torch()
+        if not isinstance(rerank, torch.Tensor) or rerank.dtype not in (torch.float32, torch.float16) or rerank.dim() != 2:
+            raise OreError(1, "rerank: expected a 2-D float32 or float16 CUDA tensor")
+        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2 or tuple(rerank.shape) != tuple(gallery.shape):
+            raise OreError(1, f"rerank: expected the gallery's [G, D], got {tuple(rerank.shape)}")
+        G = int(gallery.shape[0])
+        c = min(G, 64, 8 * int(k)) if candidates is None else int(candidates)
+        if not int(k) <= c <= min(G, 64):
+            raise OreError(1, f"candidates = {c} outside {int(k)}..{min(G, 64)} (k..min(G, 64))")
+        return _rerank(ctx, q, rerank, nearest(ctx, q, gallery, c, scales)[1], k)
     torch = _torch()
     gdt = gallery.dtype if isinstance(gallery, torch.Tensor) and gallery.dtype in (torch.float16, torch.int8) else torch.float32
     names = {torch.float32: "float32", torch.float16: "float16", torch.int8: "int8"}

@@ -13,6 +13,10 @@
      v_mfma_i32_16x16x64_i8 has twice the k-depth of v_mfma_f32_16x16x32_f16 at the same issue rate); with the share
      of rows on which the int8 and the f32 search return the same index set, the mean overlap of the two sets, and
      the ratio to the f16 search of the same rounds beside the two min - max spreads it has to exceed.
+     And the two-stage search in the same rounds: the int8 search with 32 candidates, then ore.rerank of those against
+     the f32 gallery (ore.nearest(..., rerank=g, candidates=32)), k = 5, and the rerank launch alone on the same
+     candidates.  The rerank's floor is its gathered read, n 32 D 4 bytes at --hbm-tbs; the two-stage time stands
+     against the f32 search of the same rounds, with the same index-set share and mean overlap against it.
  (b) Model.classify_into (SqueezeNet at --hw, --batch images, k = 5, f32 and f16, autotuned, set_streams(2)) with
      the normalised embedding on against off.
 Every figure is the median over --rounds windows of back-to-back calls timed by HIP events on the context stream,
@@ -30,7 +34,7 @@ sys.path.insert(0, os.path.join(REPO, "tools"))
 
 from bench_ingest import alternate  # noqa: E402  (the same windows and alternation)
 
-D, K = 512, 5
+D, K, KC = 512, 5, 32  # KC: the candidates of the two-stage search
 
 
 def main():
@@ -54,7 +58,7 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(1000)
     res = {"tool": "bench_nearest", "D": D, "k": K, "rounds": a.rounds, "hbm_tbs": a.hbm_tbs, "mfma_tflops": a.mfma_tflops,
            "mfma_f16_tflops": a.mfma_f16_tflops, "mfma_i8_tops": a.mfma_i8_tops, "nearest": {}, "nearest_f16": {}, "nearest_i8": {},
-           "model": {}}
+           "nearest_rerank": {}, "rerank_candidates": KC, "model": {}}
     for G in (10 ** 4, 10 ** 6):
         g = torch.nn.functional.normalize(torch.randn((G, D), device="cuda", generator=gen))
         gh = ore.gallery_f16(ctx, g)
@@ -62,7 +66,10 @@ def main():
         for n in (1, 32, 256):
             q = torch.nn.functional.normalize(torch.randn((n, D), device="cuda", generator=gen))
             reps = 20 if G * n <= 10 ** 7 else 3
+            cand = ore.nearest(ctx, q, gi, min(G, KC), scales=si)[1]
             r = alternate({"ore_nearest": (lambda: ore.nearest(ctx, q, g, K), reps),
+                           "ore_two_stage": (lambda: ore.nearest(ctx, q, gi, K, scales=si, rerank=g, candidates=KC), reps),
+                           "ore_rerank": (lambda: ore.rerank(ctx, q, g, cand, K), reps),
                            "ore_nearest_f16": (lambda: ore.nearest(ctx, q, gh, K), reps),
                            "ore_nearest_i8": (lambda: ore.nearest(ctx, q, gi, K, scales=si), reps),
                            "matmul_topk": (lambda: torch.topk(q @ g.T, K, dim=1), reps)}, a.rounds)
@@ -75,6 +82,17 @@ def main():
             same_i = (ours.sort(1)[0] == bytes_.sort(1)[0]).all(1).float().mean()
             overlap_i = (ours[:, :, None] == bytes_[:, None, :]).any(2).float().mean()
             h, b = r.pop("ore_nearest_f16"), r.pop("ore_nearest_i8")
+            two, rr = r.pop("ore_two_stage"), r.pop("ore_rerank")
+            staged = ore.nearest(ctx, q, gi, K, scales=si, rerank=g, candidates=KC)[1]
+            torch.cuda.synchronize()
+            gather_us = n * KC * D * 4 / (a.hbm_tbs * 1e6)
+            res["nearest_rerank"][f"n{n}_G{G}"] = dict(
+                two, rerank_alone=rr, floor_gather_us=round(gather_us, 3), rerank_share_of_floor=round(gather_us / rr["us"], 4),
+                i8_search_us=b["us"], f32_search_us=r["ore_nearest"]["us"], speedup_vs_f32=round(r["ore_nearest"]["us"] / two["us"], 3),
+                f32_window_spread_us=round(r["ore_nearest"]["max_us"] - r["ore_nearest"]["min_us"], 2),
+                ahead_of_f32=bool(r["ore_nearest"]["min_us"] > two["max_us"]),
+                same_index_set_share_vs_f32=round(float((ours.sort(1)[0] == staged.sort(1)[0]).all(1).float().mean()), 4),
+                mean_overlap_vs_f32=round(float((ours[:, :, None] == staged[:, None, :]).any(2).float().mean()), 4))
             read_b, mfma_b = -(-n // 64) * (G * D + 4 * G) / (a.hbm_tbs * 1e6), 2.0 * n * G * D / (a.mfma_i8_tops * 1e6)
             segments_b, step_rows_b = ore.nearest_segments_i8(ctx, n, G)
             spread = max(h["max_us"] - h["min_us"], b["max_us"] - b["min_us"])
