@@ -1011,6 +1011,32 @@ ore_status ore_gallery_i8(ore_ctx* ctx, const float* src, int64_t G, int64_t D, 
 ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G, int32_t k,
                           float* values, int32_t* indices);
 ore_status ore_nearest_segments_i8(ore_ctx* ctx, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows);
+/* Candidate search for the rerank (extension; ore_nearest_bins.h, ore_nearest_bins.hip): the best row
+ * of every bin of consecutive gallery rows, then the c best of those winners -- the partial reduce of Chern et al.,
+ * "TPU-KNN" (2022).  A first stage needs c good candidates cheaply, not the exact top c of an approximate score.
+ *  Definition.  For query i and a bin size B = bin_rows: bin b holds the gallery rows [b B, min(G, (b + 1) B)), NB =
+ *    ceil(G / B).  winner(i, b) is the first row of bin b in ore_topk_f32's order of s[i, .]: larger first, -0 equal to
+ *    +0, ties by lower index, every NaN after every number (a bin of NaNs has its lowest row as the winner).  Output row
+ *    i is the first c winners in that same order over the NB winners: values f32 [n, c] hold the score bits as the keys
+ *    give them (a NaN as 0x7fc00000, -0 as +0), indices int32 [n, c] the gallery rows.
+ *  s[i, j] is, to the bit, what ore_nearest_f16 / ore_nearest_i8 returns for the pair: the same format rule (the query
+ *    rounded or quantised inside the kernel, no converted copy of q in memory), the same matrix instruction, one
+ *    accumulator chain over the d ascending from +0, gallery row and query in the same operand roles.  So the result
+ *    depends on q[i, :], the gallery, B and c alone -- not on n, the segments or the load path -- and whenever the exact
+ *    top c rows lie in c different bins it is the exact search's.  A true neighbour is lost only when a better row
+ *    shares its bin: for k neighbours placed at random some two share a bin with a chance of about k (k - 1) / 2 * B / G.
+ *  Limits: B a power of two in 32..1024; 1 <= c <= min(NB, 256); q, gallery, scales and D as for the format's search.
+ *  Checks: the search's in their order without k (null pointers, q's dims, D, G, the nstride rule; int8: a null
+ *    scales, D > 131072), then bin_rows, then c (ORE_ERR_INVALID, "bin_rows" / "c" in the message), then the context.
+ *    n == 0 is ORE_OK and launches nothing.  Offsets are 64-bit.  The winners [n][NB] live in the searches' partial
+ *    buffer, under its capture rule; two launches per 256 MiB of them.
+ *  ore_nearest_bins_segments: the gallery segments (each a whole number of 4 B rows) of such a call with n queries, and
+ *    NB. */
+ore_status ore_nearest_bins_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, int32_t bin_rows, int32_t c,
+                                float* values, int32_t* indices);
+ore_status ore_nearest_bins_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G,
+                               int32_t bin_rows, int32_t c, float* values, int32_t* indices);
+ore_status ore_nearest_bins_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t bin_rows, int32_t* segments, int32_t* bins);
 /* Exact re-ranking of an approximate search (extension; ore_nearest_rerank.hip): the second stage
  * behind a cheap search.  Take k' > k candidates from ore_nearest_i8 or ore_nearest_f16, rescore only those rows against
  * the f32 (or the f16) gallery, keep the best k.

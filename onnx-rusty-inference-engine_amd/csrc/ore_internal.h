@@ -28,7 +28,8 @@ struct ore_ctx {
   bool alloc_fill = false;         // ore_ctx_set_alloc_fill (debug): device_alloc fills what the library allocates for itself
   uint32_t alloc_pattern = 0;
   int ncu = 256;                   // compute units of the device (ore_ctx_create): ore_nearest_f32's segment count
-  void* nearest_part = nullptr;    // ore_nearest_f32's partial keys [n][S][k], grown on demand as the weight scratch is
+  void* nearest_part = nullptr;    // ore_nearest_f32's partial keys [n][S][k], grown on demand as the weight scratch is;
+                                   // ore_nearest_bins_*'s winners [n][NB] too: calls on one context are stream-ordered
   size_t nearest_bytes = 0;
 };
 

@@ -633,6 +633,18 @@ void launch_gallery_i8(const float* src, long long G, long long D, void* dst, fl
 // ranks past the distinct valid rows hold index -1 and the quiet NaN.  1 <= k <= min(C, 64).  One launch, no buffer.
 void launch_nearest_rerank(NearestFmt fmt, const float* q, long long q_stride, int n, int D, const void* gallery, long long G,
                            const int* candidates, long long cand_stride, int C, int k, float* values, int* indices, hipStream_t s);
+// the candidate search in front of it (ore_nearest_bins.h, ore_nearest_bins.hip): per query the best row of every bin of
+// bin_rows (a power of two, 32 .. 1024) consecutive gallery rows, scored to the bits of the format's search, as one
+// ore_topk_key.h key per bin in win [n][NB], NB = ceil(G / bin_rows), nearest_bins_bytes(n, G, bin_rows) bytes, on S =
+// nearest_bins_segments(n, G, CUs of the device, bin_rows) segments of whole 4 bin_rows; then the c <= min(NB, 256)
+// best of a query's winners in launch_topk's order as contiguous values / indices [n][c].  Two launches, no merge.
+int nearest_bins_segments(long long n, long long G, int ncu, int bin_rows);
+size_t nearest_bins_bytes(long long n, long long G, int bin_rows);
+void launch_nearest_bins_f16(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
+                             int bin_rows, int S, void* win, hipStream_t s);
+void launch_nearest_bins_i8(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
+                            int bin_rows, int S, void* win, hipStream_t s);
+void launch_nearest_bins_select(const void* win, int n, long long NB, int c, float* values, int* indices, hipStream_t s);
 // rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 

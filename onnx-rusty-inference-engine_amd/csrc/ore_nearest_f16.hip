@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "ore_nearest.h"
+#include "ore_nearest_bins.h"
 
 namespace ore {
 
@@ -100,6 +101,12 @@ void launch_gallery_f16(const float* src, long long G, long long D, void* dst, h
 void launch_nearest_f16(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
                         int k, int S, void* part, float* values, int* indices, hipStream_t s) {
   nearest_launch<NearestStream<FmtF16>>(q, q_stride, n, D, gallery, scales, G, k, S, part, values, indices, s);
+}
+
+// ore_nearest_bins.h's kernel over the same format: 64 rows of 520 halves twice on a compute unit
+void launch_nearest_bins_f16(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
+                             int bin_rows, int S, void* win, hipStream_t s) {
+  nearest_bins_launch<FmtF16, 512>(q, q_stride, n, D, gallery, scales, G, bin_rows, S, win, s);
 }
 
 }  // namespace ore

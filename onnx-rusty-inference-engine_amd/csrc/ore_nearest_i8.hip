@@ -26,6 +26,7 @@
 #pragma clang fp contract(off)
 
 #include "ore_nearest.h"
+#include "ore_nearest_bins.h"
 
 namespace ore {
 
@@ -178,6 +179,12 @@ void launch_gallery_i8(const float* src, long long G, long long D, void* dst, fl
 void launch_nearest_i8(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
                        int k, int S, void* part, float* values, int* indices, hipStream_t s) {
   nearest_launch<NearestStream<FmtI8>>(q, q_stride, n, D, gallery, scales, G, k, S, part, values, indices, s);
+}
+
+// ore_nearest_bins.h's kernel over the same format: 64 rows of 1040 codes and the queries' scales twice on a compute unit
+void launch_nearest_bins_i8(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
+                            int bin_rows, int S, void* win, hipStream_t s) {
+  nearest_bins_launch<FmtI8, 1024>(q, q_stride, n, D, gallery, scales, G, bin_rows, S, win, s);
 }
 
 }  // namespace ore

@@ -889,8 +889,9 @@ ore_status ore_topk_mean_f32(ore_ctx* ctx, const ore_tensor* x, int32_t views, i
 }
 
 // ore_nearest_f32 / ore_nearest_f16 / ore_nearest_i8: the checks that need no context, in the header's order (ORE_OK: n and D are set)
+// has_k: ore_nearest_bins_* have no k, their c is judged behind the format's own checks
 static ore_status nearest_check(ore_ctx* ctx, const ore_tensor* q, const void* gallery, int64_t G, int32_t k, const float* values,
-                                const int32_t* indices, int64_t* n_out, int64_t* D_out) {
+                                const int32_t* indices, int64_t* n_out, int64_t* D_out, bool has_k = true) {
   if (!q || !q->data || !gallery || !values || !indices) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   if (q->ndim < 2 || q->ndim > 4 || q->dims[0] < 0 || !fits_i32(q->dims[0]))
     return set_error(ctx, ORE_ERR_INVALID, "nearest: q of %d dims and %lld rows, expected [n, D] in 2 to 4 dims", int(q->ndim),
@@ -900,7 +901,7 @@ static ore_status nearest_check(ore_ctx* ctx, const ore_tensor* q, const void* g
   for (int i = 1; i < q->ndim; ++i) D = q->dims[i] >= 1 && D >= 1 && D * q->dims[i] < lim ? D * q->dims[i] : 0;
   if (D < 1) return set_error(ctx, ORE_ERR_INVALID, "nearest: D, the row length of q, is not in 1..2^31-1");
   if (G < 1 || G >= lim) return set_error(ctx, ORE_ERR_INVALID, "nearest: G = %lld outside 1..2^31-1", (long long)G);
-  if (k < 1 || k > std::min<int64_t>(G, 64))
+  if (has_k && (k < 1 || k > std::min<int64_t>(G, 64)))
     return set_error(ctx, ORE_ERR_INVALID, "nearest: k = %d outside 1..%lld (min(G, 64))", int(k), (long long)std::min<int64_t>(G, 64));
   if (q->nstride < 0 || (q->nstride && (q->nstride < D || q->nstride >= lim || !fits_i32(q->nstride * std::max<int64_t>(n, 1) + 256))))
     return set_error(ctx, ORE_ERR_INVALID, "nearest: q->nstride %lld with %lld rows of %lld: below the row length or past 32-bit indexing",
@@ -964,6 +965,61 @@ ore_status ore_nearest_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* ga
 ore_status ore_nearest_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G, int32_t k,
                           float* values, int32_t* indices) {
   return nearest_run(ctx, NearestFmt::I8, q, gallery, scales, G, k, values, indices);
+}
+
+// ore_nearest_bins_f16 / ore_nearest_bins_i8: the search's checks in their order, then bin_rows, then c, the context
+// last.  The winners [n][NB] share the searches' partial buffer and its capture rule; above NEAREST_BINS_SLAB bytes of
+// them the queries go through in slabs of whole tiles, two launches each
+constexpr size_t NEAREST_BINS_SLAB = size_t(256) << 20;
+
+static ore_status nearest_bins_run(ore_ctx* ctx, NearestFmt fmt, const ore_tensor* q, const void* gallery, const float* scales,
+                                   int64_t G, int32_t bin_rows, int32_t c, float* values, int32_t* indices) {
+  int64_t n = 0, D = 0;
+  if (const ore_status st = nearest_check(ctx, q, gallery, G, 0, values, indices, &n, &D, false)) return st;
+  if (fmt == NearestFmt::I8) {
+    if (!scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+    if (D > nearest_i8_max_d())
+      return set_error(ctx, ORE_ERR_INVALID, "nearest: D = %lld above %d, the int32 dot product's limit", (long long)D, nearest_i8_max_d());
+  }
+  if (bin_rows < 32 || bin_rows > 1024 || (bin_rows & (bin_rows - 1)))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: bin_rows = %d is no power of two in 32..1024", int(bin_rows));
+  const int64_t NB = (G + bin_rows - 1) / bin_rows;
+  if (c < 1 || c > std::min<int64_t>(NB, 256))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: c = %d outside 1..%lld (min(bins, 256))", int(c), (long long)std::min<int64_t>(NB, 256));
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int64_t slab = std::min<int64_t>(n, std::max<int64_t>(int64_t(NEAREST_BINS_SLAB / (size_t(NB) * 8)) / 64 * 64, 64));
+  if (const ore_status st = nearest_grow_part(ctx, nearest_bins_bytes(slab, G, bin_rows))) return st;
+  const auto launch = fmt == NearestFmt::I8 ? launch_nearest_bins_i8 : launch_nearest_bins_f16;
+  for (int64_t i0 = 0; i0 < n; i0 += slab) {
+    const int m = int(std::min(slab, n - i0));
+    launch(q->data + i0 * nstride_of(q), nstride_of(q), m, int(D), gallery, scales, G, int(bin_rows),
+           nearest_bins_segments(m, G, ctx->ncu, bin_rows), ctx->nearest_part, ctx->stream);
+    launch_nearest_bins_select(ctx->nearest_part, m, NB, int(c), values + i0 * c, indices + i0 * c, ctx->stream);
+  }
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_bins_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, int32_t bin_rows, int32_t c,
+                                float* values, int32_t* indices) {
+  return nearest_bins_run(ctx, NearestFmt::F16, q, gallery, nullptr, G, bin_rows, c, values, indices);
+}
+
+ore_status ore_nearest_bins_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G,
+                               int32_t bin_rows, int32_t c, float* values, int32_t* indices) {
+  return nearest_bins_run(ctx, NearestFmt::I8, q, gallery, scales, G, bin_rows, c, values, indices);
+}
+
+ore_status ore_nearest_bins_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t bin_rows, int32_t* segments, int32_t* bins) {
+  if (!ctx || !segments || !bins) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
+  if (bin_rows < 32 || bin_rows > 1024 || (bin_rows & (bin_rows - 1)))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: bin_rows = %d is no power of two in 32..1024", int(bin_rows));
+  *segments = nearest_bins_segments(n, G, ctx->ncu, bin_rows);
+  *bins = int32_t((G + bin_rows - 1) / bin_rows);
+  return ORE_OK;
 }
 
 // ore_nearest_rerank_f32 / ore_nearest_rerank_f16: the checks in the header's order, the context last; one launch

@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "gallery_i8", "nearest_segments_i8", "rerank", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "gallery_i8", "nearest_segments_i8", "rerank", "nearest_bins", "nearest_bins_segments", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -970,31 +970,8 @@ def rerank(ctx: Context, q, gallery, candidates, k: int):
 _rerank = rerank  # nearest() has a parameter of this name
 
 
-def nearest(ctx: Context, q, gallery, k: int, scales=None, rerank=None, candidates=None):
-    """ore_nearest_f32 / ore_nearest_f16 / ore_nearest_i8 (extension): for every row of q [n, D] the k rows of gallery
-    [G, D] with the largest inner product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the
-    scores -- the [n, G] score matrix is never formed.  q is float32 and may be a row slice (q.stride(0) >= D, rows
-    dense); gallery is contiguous, float32, float16 (gallery_f16(): q is then rounded to f16 inside the kernel, f32
-    accumulation on the f16 matrix cores) or int8 with scales, a contiguous float32 [G] (gallery_i8(): q is then
-    quantised per row inside the kernel, the code products summed exactly on the int8 matrix cores and scaled by the two
-    rows' scales).  The bits of a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise both sides
-    for cosine similarity.
-    Two-stage form: with `rerank`, a float32 or float16 [G, D] gallery of the same G and D, the search above is run with
-    `candidates` results per query (default min(G, 64, 8 k); in k..min(G, 64)) and rerank() of those against `rerank`
-    is returned, [n, k].  `candidates` without `rerank` is an error."""
-    if rerank is None and candidates is not None:
-        raise OreError(1, "candidates: given without rerank; only the two-stage form has candidates")
-    if rerank is not None:
-        torch = _torch()
-        if not isinstance(rerank, torch.Tensor) or rerank.dtype not in (torch.float32, torch.float16) or rerank.dim() != 2:
-            raise OreError(1, "rerank: expected a 2-D float32 or float16 CUDA tensor")
-        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2 or tuple(rerank.shape) != tuple(gallery.shape):
-            raise OreError(1, f"rerank: expected the gallery's [G, D], got {tuple(rerank.shape)}")
-        G = int(gallery.shape[0])
-        c = min(G, 64, 8 * int(k)) if candidates is None else int(candidates)
-        if not int(k) <= c <= min(G, 64):
-            raise OreError(1, f"candidates = {c} outside {int(k)}..{min(G, 64)} (k..min(G, 64))")
-        return _rerank(ctx, q, rerank, nearest(ctx, q, gallery, c, scales)[1], k)
+def _nearest_operands(ctx, q, gallery, scales):
+    """The tensor checks of nearest() and nearest_bins(): (gallery dtype, n, D, G, q's descriptor)."""
     torch = _torch()
     gdt = gallery.dtype if isinstance(gallery, torch.Tensor) and gallery.dtype in (torch.float16, torch.int8) else torch.float32
     names = {torch.float32: "float32", torch.float16: "float16", torch.int8: "int8"}
@@ -1018,15 +995,95 @@ def nearest(ctx: Context, q, gallery, k: int, scales=None, rerank=None, candidat
         raise OreError(1, f"gallery: expected a contiguous [G, {D}] tensor, got {tuple(gallery.shape)}")
     if n > 1 and (q.stride(1) != 1 or q.stride(0) < D) or n <= 1 and not q.is_contiguous():
         raise OreError(1, "q: expected dense rows at a row stride of at least D")
+    d = Tensor()
+    d.data, d.ndim, d.nstride = q.data_ptr(), 2, (int(q.stride(0)) if n > 1 else 0)
+    d.dims[0], d.dims[1] = n, D
+    return gdt, n, D, G, d
+
+
+def nearest_bins(ctx: Context, q, gallery, c: int, bin_rows: int = 128, scales=None):
+    """ore_nearest_bins_f16 / ore_nearest_bins_i8 (extension): the candidate search in front of rerank().  The gallery
+    is cut into bins of bin_rows consecutive rows (a power of two in 32..1024); per row of q the best row of every bin
+    is kept, and the c best of those winners are returned as (values float32 [n, c], indices int32 [n, c]) in topk()'s
+    order, 1 <= c <= min(ceil(G / bin_rows), 256).  Scores are nearest()'s of the same gallery to the bit, so whenever
+    the exact top c rows lie in c different bins the result is nearest()'s; a neighbour is lost only to a better row
+    of its own bin.  gallery is float16 (gallery_f16()) or int8 with scales (gallery_i8()); q as for nearest()."""
+    torch = _torch()
+    if isinstance(gallery, torch.Tensor) and gallery.dtype == torch.float32:
+        raise OreError(1, "gallery: nearest_bins() runs on a float16 or an int8 gallery (gallery_f16(), gallery_i8()), not float32")
+    gdt, n, D, G, d = _nearest_operands(ctx, q, gallery, scales)
+    B, c = int(bin_rows), int(c)
+    if not 32 <= B <= 1024 or B & (B - 1):
+        raise OreError(1, f"bin_rows = {bin_rows} is no power of two in 32..1024")
+    bins = -(-G // B)
+    if not 1 <= c <= min(bins, 256):
+        raise OreError(1, f"c = {c} outside 1..{min(bins, 256)} (min(bins, 256))")
+    values = torch.empty((n, c), dtype=torch.float32, device=q.device)
+    indices = torch.empty((n, c), dtype=torch.int32, device=q.device)
+    if n == 0:
+        return values, indices
+    out = (G, B, c, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr()))
+    if gdt == torch.int8:
+        check(load().ore_nearest_bins_i8(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()),
+                                         ctypes.c_void_p(scales.data_ptr()), *out), ctx.h)
+    else:
+        check(load().ore_nearest_bins_f16(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), *out), ctx.h)
+    return values, indices
+
+
+def nearest_bins_segments(ctx: Context, n: int, G: int, bin_rows: int = 128):
+    """ore_nearest_bins_segments: (gallery segments, bins) of nearest_bins() with n queries against G rows."""
+    s, b = ctypes.c_int32(), ctypes.c_int32()
+    check(load().ore_nearest_bins_segments(ctx.h, int(n), int(G), int(bin_rows), ctypes.byref(s), ctypes.byref(b)), ctx.h)
+    return s.value, b.value
+
+
+def nearest(ctx: Context, q, gallery, k: int, scales=None, rerank=None, candidates=None, bin_rows=None):
+    """ore_nearest_f32 / ore_nearest_f16 / ore_nearest_i8 (extension): for every row of q [n, D] the k rows of gallery
+    [G, D] with the largest inner product, as (values float32 [n, k], indices int32 [n, k]) in topk()'s order over the
+    scores -- the [n, G] score matrix is never formed.  q is float32 and may be a row slice (q.stride(0) >= D, rows
+    dense); gallery is contiguous, float32, float16 (gallery_f16(): q is then rounded to f16 inside the kernel, f32
+    accumulation on the f16 matrix cores) or int8 with scales, a contiguous float32 [G] (gallery_i8(): q is then
+    quantised per row inside the kernel, the code products summed exactly on the int8 matrix cores and scaled by the two
+    rows' scales).  The bits of a score depend on its two rows alone.  1 <= k <= min(G, 64).  L2-normalise both sides
+    for cosine similarity.
+    Two-stage form: with `rerank`, a float32 or float16 [G, D] gallery of the same G and D, the search above is run with
+    `candidates` results per query (default min(G, 64, 8 k); in k..min(G, 64)) and rerank() of those against `rerank`
+    is returned, [n, k].  `candidates` without `rerank` is an error.  With `bin_rows` as well the first stage is
+    nearest_bins() on a float16 or int8 gallery: `candidates` (default min(bins, 256, 8 k)) is then in k..min(bins, 256),
+    bins = ceil(G / bin_rows).  `bin_rows` without `rerank` is an error."""
+    if rerank is None and candidates is not None:
+        raise OreError(1, "candidates: given without rerank; only the two-stage form has candidates")
+    if rerank is None and bin_rows is not None:
+        raise OreError(1, "bin_rows: given without rerank; only the two-stage form has a binned first stage")
+    if rerank is not None:
+        torch = _torch()
+        if not isinstance(rerank, torch.Tensor) or rerank.dtype not in (torch.float32, torch.float16) or rerank.dim() != 2:
+            raise OreError(1, "rerank: expected a 2-D float32 or float16 CUDA tensor")
+        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2 or tuple(rerank.shape) != tuple(gallery.shape):
+            raise OreError(1, f"rerank: expected the gallery's [G, D], got {tuple(rerank.shape)}")
+        G = int(gallery.shape[0])
+        if bin_rows is not None:
+            B = int(bin_rows)
+            if not 32 <= B <= 1024 or B & (B - 1):
+                raise OreError(1, f"bin_rows = {bin_rows} is no power of two in 32..1024")
+            most = min(-(-G // B), 256)
+            c = min(most, 8 * int(k)) if candidates is None else int(candidates)
+            if not int(k) <= c <= most:
+                raise OreError(1, f"candidates = {c} outside {int(k)}..{most} (k..min(bins, 256))")
+            return _rerank(ctx, q, rerank, nearest_bins(ctx, q, gallery, c, B, scales)[1], k)
+        c = min(G, 64, 8 * int(k)) if candidates is None else int(candidates)
+        if not int(k) <= c <= min(G, 64):
+            raise OreError(1, f"candidates = {c} outside {int(k)}..{min(G, 64)} (k..min(G, 64))")
+        return _rerank(ctx, q, rerank, nearest(ctx, q, gallery, c, scales)[1], k)
+    torch = _torch()
+    gdt, n, D, G, d = _nearest_operands(ctx, q, gallery, scales)
     if not 1 <= int(k) <= min(G, 64):
         raise OreError(1, f"k = {k} outside 1..{min(G, 64)} (min(G, 64))")
     values = torch.empty((n, int(k)), dtype=torch.float32, device=q.device)
     indices = torch.empty((n, int(k)), dtype=torch.int32, device=q.device)
     if n == 0:
         return values, indices
-    d = Tensor()
-    d.data, d.ndim, d.nstride = q.data_ptr(), 2, (int(q.stride(0)) if n > 1 else 0)
-    d.dims[0], d.dims[1] = n, D
     out = (G, int(k), ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr()))
     if gdt == torch.int8:
         check(load().ore_nearest_i8(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()),

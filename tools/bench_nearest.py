@@ -22,7 +22,8 @@
 Every figure is the median over --rounds windows of back-to-back calls timed by HIP events on the context stream,
 with the smallest and largest window beside it; the variants of one comparison alternate inside a round.  Needs an
 MI355X (no fallback).
-usage: python tools/bench_nearest.py [--batch 256] [--hw 224] [--rounds 9] [--skip-model] [--out FILE]"""
+ (c) --bins, instead of (a) and (b): the binned candidate search, see bins_part().
+usage: python tools/bench_nearest.py [--batch 256] [--hw 224] [--rounds 9] [--skip-model] [--bins] [--out FILE]"""
 import argparse
 import json
 import os
@@ -37,8 +38,49 @@ from bench_ingest import alternate  # noqa: E402  (the same windows and alternat
 D, K, KC = 512, 5, 32  # KC: the candidates of the two-stage search
 
 
+def bins_part(a, ctx, torch, ore, gen):
+    """--bins: the binned candidate search.  Per cell of n x G, alternating inside a round: the f32
+    search, the int8 search at k = 5 and at k = 32, and for the int8 and the f16 gallery, B in {32, 128}, c in {32,
+    128}: ore.nearest_bins (both kernels) and the two-stage ore.nearest(..., rerank=g, candidates=c, bin_rows=B), with
+    the share of queries whose five indices equal the f32 search's.  The read floors are those of part (a)."""
+    res = {"tool": "bench_nearest --bins", "D": D, "k": K, "rounds": a.rounds, "hbm_tbs": a.hbm_tbs, "cells": {}}
+    for G in (10 ** 4, 10 ** 6):
+        g = torch.nn.functional.normalize(torch.randn((G, D), device="cuda", generator=gen))
+        gh = ore.gallery_f16(ctx, g)
+        gi, si = ore.gallery_i8(ctx, g)
+        for n in (1, 32, 256):
+            q = torch.nn.functional.normalize(torch.randn((n, D), device="cuda", generator=gen))
+            reps = 20 if G * n <= 10 ** 7 else 3
+            v = {"f32_k5": (lambda: ore.nearest(ctx, q, g, K), reps),
+                 "i8_k5": (lambda: ore.nearest(ctx, q, gi, K, scales=si), reps),
+                 "i8_k32": (lambda: ore.nearest(ctx, q, gi, KC, scales=si), reps),
+                 "i8_k32_two_stage": (lambda: ore.nearest(ctx, q, gi, K, scales=si, rerank=g, candidates=KC), reps)}
+            # c no larger than the bins there are: G = 10^4 at B = 128 has 79, and that setting is named c79
+            settings = [(f, B, min(c, -(-G // B))) for f in ("i8", "f16") for B in (32, 128) for c in (32, 128)]
+            for f, B, c in settings:
+                gal, sc = (gi, si) if f == "i8" else (gh, None)
+                v[f"{f}_B{B}_c{c}_bins"] = (lambda gal=gal, sc=sc, B=B, c=c: ore.nearest_bins(ctx, q, gal, c, B, scales=sc), reps)
+                v[f"{f}_B{B}_c{c}_two_stage"] = (lambda gal=gal, sc=sc, B=B, c=c: ore.nearest(ctx, q, gal, K, scales=sc, rerank=g,
+                                                                                             candidates=c, bin_rows=B), reps)
+            r = alternate(v, a.rounds)
+            exact = ore.nearest(ctx, q, g, K)[1].sort(1)[0]
+            for f, B, c in settings:
+                gal, sc = (gi, si) if f == "i8" else (gh, None)
+                got = ore.nearest(ctx, q, gal, K, scales=sc, rerank=g, candidates=c, bin_rows=B)[1].sort(1)[0]
+                r[f"{f}_B{B}_c{c}_two_stage"]["same_index_set_share_vs_f32"] = round(float((got == exact).all(1).float().mean()), 4)
+            got = ore.nearest(ctx, q, gi, K, scales=si, rerank=g, candidates=KC)[1].sort(1)[0]
+            r["i8_k32_two_stage"]["same_index_set_share_vs_f32"] = round(float((got == exact).all(1).float().mean()), 4)
+            tiles = -(-n // 64)
+            r["floor_read_us"] = {"i8": round(tiles * (G * D + 4 * G) / (a.hbm_tbs * 1e6), 2), "f16": round(tiles * G * D * 2 / (a.hbm_tbs * 1e6), 2)}
+            r["segments"] = {f"B{B}": ore.nearest_bins_segments(ctx, n, G, B)[0] for B in (32, 128)}
+            res["cells"][f"n{n}_G{G}"] = r
+        del g, gh, gi, si
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bins", action="store_true", help="the binned candidate search only (DESIGN.md 3.13f)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--hw", type=int, default=224)
     ap.add_argument("--rounds", type=int, default=9)
@@ -56,6 +98,14 @@ def main():
         sys.exit("bench_nearest.py: no GPU visible")
     ctx = ore.Context(0)
     gen = torch.Generator(device="cuda").manual_seed(1000)
+    if a.bins:
+        line = json.dumps(bins_part(a, ctx, torch, ore, gen))
+        ctx.close()
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     res = {"tool": "bench_nearest", "D": D, "k": K, "rounds": a.rounds, "hbm_tbs": a.hbm_tbs, "mfma_tflops": a.mfma_tflops,
            "mfma_f16_tflops": a.mfma_f16_tflops, "mfma_i8_tops": a.mfma_i8_tops, "nearest": {}, "nearest_f16": {}, "nearest_i8": {},
            "nearest_rerank": {}, "rerank_candidates": KC, "model": {}}
