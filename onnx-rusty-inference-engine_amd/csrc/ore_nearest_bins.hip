@@ -8,9 +8,12 @@
 // prefix.  The four bytes of the image come first and the four of the complemented row after them, so equal images
 // are resolved by the lower row with no code of their own.  The passes stop as soon as the keys at or above the cut
 // bucket are at most NBS_CAP (the last pass leaves one key in its bucket, keys being unique): typically after two or
-// three of the eight.  Those survivors -- the c wanted ones among them -- go to LDS through a counter, each is ranked
-// by counting the survivors above it (unique keys: rank = position) and the ranks below c are written.  Work:
-// O(passes NB + NBS_CAP^2 / 256) per thread row, whatever c is; NB of any size by striding over the row.
+// three of the eight.  Any pass but the last can be the one that ends it: the last never is, the cut bucket of the
+// pass before it holding the bins of 256 consecutive rows, at most 8; the pass over the row's top byte is only on a
+// gallery past 2^24 rows (tests/test_nearest_select_gpu.py takes the select to each of the seven).  Those survivors
+// -- the c wanted ones among them -- go to LDS through a counter, each is ranked by counting the survivors above it
+// (unique keys: rank = position) and the ranks below c are written.  Work: O(passes NB + NBS_CAP^2 / 256) per thread
+// row, whatever c is; NB of any size by striding over the row.
 #include "ore_kernels.h"
 #include "ore_nearest.h"
 

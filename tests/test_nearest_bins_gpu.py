@@ -7,20 +7,10 @@ import pytest
 import torch
 
 import ore
-from _nearest_i8 import best, quant, scores
+from _nearest_i8 import bins_ref, quant, scores
 
 pytestmark = pytest.mark.gpu
 NAN = 0x7FC00000
-
-
-def bins_ref(s, B, c):
-    n, G = s.shape
-    NB = -(-G // B)
-    p = np.full((n, NB * B), np.nan, np.float32)  # absent rows: NaNs behind every row of their bin
-    p[:, :G] = s
-    rows = (best(p.reshape(n * NB, B), 1)[1][:, 0] + B * (np.arange(n * NB) % NB)).reshape(n, NB)
-    v, i = best(np.take_along_axis(s, rows, 1), c)  # the winners stand in row order: ties by lower row
-    return v, np.take_along_axis(rows, i, 1)
 
 
 def _given(fmt, seed, n, G, D):
