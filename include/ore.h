@@ -1037,6 +1037,47 @@ ore_status ore_nearest_bins_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_
 ore_status ore_nearest_bins_i8(ore_ctx* ctx, const ore_tensor* q, const int8_t* gallery, const float* scales, int64_t G,
                                int32_t bin_rows, int32_t c, float* values, int32_t* indices);
 ore_status ore_nearest_bins_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t bin_rows, int32_t* segments, int32_t* bins);
+/* The candidate search on an MXFP4 gallery (extension; ore_nearest_fp4.hip): 4.25 bits per element, on
+ * gfx950's scaled matrix instruction v_mfma_scale_f32_16x16x128_f8f6f4.  A first stage only: its scores are too coarse
+ * for an answer, ore_nearest_rerank_* makes the survivors exact.  There is no full top-k on these scores.
+ *  The format (OCP microscaling MXFP4).  A row of D elements is nb = ceil(D / 32) blocks of 32.
+ *    codes   uint8 [G, 16 nb], two elements per byte, element 2 i the low nibble of byte i.  A code is a sign (bit 3) and
+ *            an E2M1 magnitude (bits 0..2), one of {0, 0.5, 1, 1.5, 2, 3, 4, 6}.  Elements from D up to 32 nb are code 0.
+ *    scales  uint8 [G, nb], one E8M0 byte per block: a byte b means 2^(b - 127).
+ *  Quantising a block x[0..32) of f32 -- the packer's rule and the kernel's rule for a query row (elements past D are 0):
+ *      a    = min(max_d |x_d|, FLT_MAX), NaN elements skipped (fmaxf; 0 when there is none)
+ *      b    = clamp((biased exponent field of a) - 2, 0, 254)               the block's scale byte
+ *      m_d  = |x_d| / 2^(b - 127), an exact scaling (ldexp)
+ *      code = sign bit of x_d, and m_d rounded to the nearest magnitude, ties to the even code, saturated at 6
+ *    A NaN element is code 0.  Branch-free on a: an all-zero block has byte 0 and zero codes (a negative zero code 8),
+ *    a block whose maximum is subnormal has byte 0, +-inf is +-6 under the byte of FLT_MAX (252).  The largest magnitude
+ *    of a block lands in [4, 8): it is code 6 (4), or 7 (6, also for what lies above 6).  Byte 255 is never emitted.
+ *  Score.  s[i, j] = sum over the blocks of 2^(eq + eg) sum_d cq cg, the query row quantised by the same rule inside the
+ *    kernel (no converted copy of q reaches memory): one accumulator chain of the instruction over the k-groups of 128 d,
+ *    ascending from +0, gallery row as the A operand and query as the B operand.  The bits of s[i, j] depend on q[i, :]
+ *    and gallery row j alone -- not on n, G, the bin size, where row j sits, the segments or the load path.
+ *    Accumulation contract: within ORE_MXFP4_KAPPA sum_d |q^ g^| of the exact sum of the decoded operands' products.
+ *    The instruction's internal rounding is not documented, so the figure is twice the largest ratio measured on
+ *    MI355X (tests/test_nearest_mxfp4_gpu.py: normals, D = 33 and 512): that ratio was 0 -- every score came out as
+ *    the exact sum, whose partial sums are all representable in f32 on such data -- and so is the constant.  Nothing
+ *    is claimed for rows whose blocks' scales lie so far apart that the exact sum is not an f32 number.
+ *  ore_gallery_mxfp4: src a contiguous DEVICE f32 array [G, D], codes [G, 16 nb] and scales [G, nb] DEVICE uint8; one
+ *    launch.  Checks: null src / codes / scales, G and D in 1..2^31-1, codes 16-byte aligned ("codes"), then the context.
+ *  ore_nearest_bins_mxfp4: q is f32 exactly as for every search (2-D to 4-D, q->nstride >= D honoured, any 4-byte
+ *    aligned base).  codes must be 16-byte aligned: rows are whole 16-byte blocks and there is no element-wise gallery
+ *    path.  1 <= D <= 4096 (ORE_MXFP4_MAX_D): the quantised query tile is always resident.  A caller's own gallery may
+ *    hold any code and any scale byte; they are not checked (byte 255 is the format's NaN).  bin_rows, c, the definition
+ *    of a winner, the output order, NaN handling, n == 0, the winner buffer with its slabs and its capture rule are
+ *    ore_nearest_bins_i8's, and the c best are picked by the same second kernel.
+ *    Checks: ore_nearest_bins_i8's in their order -- the search's without k, then a null scales, then D > 4096 ("D" in
+ *    the message), then a misaligned codes ("codes"), then bin_rows, then c, then the context.
+ *  ore_nearest_bins_segments_mxfp4: the gallery segments (each a whole number of 4 B rows) of such a call, and NB. */
+#define ORE_MXFP4_MAX_D 4096
+#define ORE_MXFP4_KAPPA 0.0f
+ore_status ore_gallery_mxfp4(ore_ctx* ctx, const float* src, int64_t G, int64_t D, uint8_t* codes, uint8_t* scales);
+ore_status ore_nearest_bins_mxfp4(ore_ctx* ctx, const ore_tensor* q, const uint8_t* codes, const uint8_t* scales, int64_t G,
+                                  int32_t bin_rows, int32_t c, float* values, int32_t* indices);
+ore_status ore_nearest_bins_segments_mxfp4(ore_ctx* ctx, int64_t n, int64_t G, int32_t bin_rows, int32_t* segments, int32_t* bins);
 /* Exact re-ranking of an approximate search (extension; ore_nearest_rerank.hip): the second stage
  * behind a cheap search.  Take k' > k candidates from ore_nearest_i8 or ore_nearest_f16, rescore only those rows against
  * the f32 (or the f16) gallery, keep the best k.

@@ -645,6 +645,15 @@ void launch_nearest_bins_f16(const float* q, long long q_stride, int n, int D, c
 void launch_nearest_bins_i8(const float* q, long long q_stride, int n, int D, const void* gallery, const float* scales, long long G,
                             int bin_rows, int S, void* win, hipStream_t s);
 void launch_nearest_bins_select(const void* win, int n, long long NB, int c, float* values, int* indices, hipStream_t s);
+// the candidate search on an MXFP4 gallery (ore_nearest_fp4.hip; include/ore.h states the format): codes [G][16 nb]
+// 16-byte aligned, scale bytes [G][nb], nb = ceil(D / 32), D <= nearest_mxfp4_max_d(); the winners as above, on S =
+// nearest_bins_segments_mxfp4(n, G, CUs of the device, bin_rows) segments, picked by launch_nearest_bins_select.
+// launch_gallery_mxfp4: contiguous f32 [G][D] -> codes and scale bytes by the same rule, one launch.
+int nearest_mxfp4_max_d();
+int nearest_bins_segments_mxfp4(long long n, long long G, int ncu, int bin_rows);
+void launch_gallery_mxfp4(const float* src, long long G, long long D, void* codes, void* scales, hipStream_t s);
+void launch_nearest_bins_mxfp4(const float* q, long long q_stride, int n, int D, const void* codes, const void* scales, long long G,
+                               int bin_rows, int S, void* win, hipStream_t s);
 // rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 

@@ -1022,6 +1022,46 @@ ore_status ore_nearest_bins_segments(ore_ctx* ctx, int64_t n, int64_t G, int32_t
   return ORE_OK;
 }
 
+// ore_nearest_bins_mxfp4: ore_nearest_bins_i8's checks in their order with the format's own (null scales, D, codes) in
+// the int8 ones' place; the winners, the slabs and the select are nearest_bins_run's
+ore_status ore_nearest_bins_mxfp4(ore_ctx* ctx, const ore_tensor* q, const uint8_t* codes, const uint8_t* scales, int64_t G,
+                                  int32_t bin_rows, int32_t c, float* values, int32_t* indices) {
+  int64_t n = 0, D = 0;
+  if (const ore_status st = nearest_check(ctx, q, codes, G, 0, values, indices, &n, &D, false)) return st;
+  if (!scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (D > nearest_mxfp4_max_d())
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: D = %lld above %d, the resident MXFP4 query tile's limit", (long long)D, nearest_mxfp4_max_d());
+  if (reinterpret_cast<uintptr_t>(codes) & 15) return set_error(ctx, ORE_ERR_INVALID, "nearest: codes is not 16-byte aligned");
+  if (bin_rows < 32 || bin_rows > 1024 || (bin_rows & (bin_rows - 1)))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: bin_rows = %d is no power of two in 32..1024", int(bin_rows));
+  const int64_t NB = (G + bin_rows - 1) / bin_rows;
+  if (c < 1 || c > std::min<int64_t>(NB, 256))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: c = %d outside 1..%lld (min(bins, 256))", int(c), (long long)std::min<int64_t>(NB, 256));
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int64_t slab = std::min<int64_t>(n, std::max<int64_t>(int64_t(NEAREST_BINS_SLAB / (size_t(NB) * 8)) / 64 * 64, 64));
+  if (const ore_status st = nearest_grow_part(ctx, nearest_bins_bytes(slab, G, bin_rows))) return st;
+  for (int64_t i0 = 0; i0 < n; i0 += slab) {
+    const int m = int(std::min(slab, n - i0));
+    launch_nearest_bins_mxfp4(q->data + i0 * nstride_of(q), nstride_of(q), m, int(D), codes, scales, G, int(bin_rows),
+                              nearest_bins_segments_mxfp4(m, G, ctx->ncu, bin_rows), ctx->nearest_part, ctx->stream);
+    launch_nearest_bins_select(ctx->nearest_part, m, NB, int(c), values + i0 * c, indices + i0 * c, ctx->stream);
+  }
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_nearest_bins_segments_mxfp4(ore_ctx* ctx, int64_t n, int64_t G, int32_t bin_rows, int32_t* segments, int32_t* bins) {
+  if (!ctx || !segments || !bins) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n < 0 || !fits_i32(n) || G < 1 || !fits_i32(G)) return set_error(ctx, ORE_ERR_INVALID, "nearest: n = %lld, G = %lld", (long long)n, (long long)G);
+  if (bin_rows < 32 || bin_rows > 1024 || (bin_rows & (bin_rows - 1)))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest: bin_rows = %d is no power of two in 32..1024", int(bin_rows));
+  *segments = nearest_bins_segments_mxfp4(n, G, ctx->ncu, bin_rows);
+  *bins = int32_t((G + bin_rows - 1) / bin_rows);
+  return ORE_OK;
+}
+
 // ore_nearest_rerank_f32 / ore_nearest_rerank_f16: the checks in the header's order, the context last; one launch
 static ore_status nearest_rerank_run(ore_ctx* ctx, NearestFmt fmt, const ore_tensor* q, const void* gallery, int64_t G,
                                      const int32_t* candidates, int64_t cand_stride, int32_t C, int32_t k, float* values,
@@ -1102,6 +1142,18 @@ ore_status ore_gallery_i8(ore_ctx* ctx, const float* src, int64_t G, int64_t D, 
   if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
   ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   launch_gallery_i8(src, G, D, dst, scales, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
+ore_status ore_gallery_mxfp4(ore_ctx* ctx, const float* src, int64_t G, int64_t D, uint8_t* codes, uint8_t* scales) {
+  if (!src || !codes || !scales) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (G < 1 || G >= (int64_t(1) << 31) || D < 1 || D >= (int64_t(1) << 31))
+    return set_error(ctx, ORE_ERR_INVALID, "gallery: G = %lld, D = %lld outside 1..2^31-1", (long long)G, (long long)D);
+  if (reinterpret_cast<uintptr_t>(codes) & 15) return set_error(ctx, ORE_ERR_INVALID, "gallery: codes is not 16-byte aligned");
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  launch_gallery_mxfp4(src, G, D, codes, scales, ctx->stream);
   ORE_HIP_CHECK(ctx, hipGetLastError());
   return ORE_OK;
 }

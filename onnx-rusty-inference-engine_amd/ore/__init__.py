@@ -12,6 +12,7 @@ from .engine import (Context, ImageList, Model, Nv12ImageList, YuvImageList, add
                      preprocess_u8, relu, reshape, resize_aa_taps, resize_cubic_taps, resize_taps, softmax, topk, topk_mean, yuv_planes_to_rgb, yuv_to_rgb,
                      apply_orientation, orient_geometry, oriented_hw, rotation_orientation,
                      box_to_source, cam_box_reference, cam_boxes, upsample_maps, nearest, nearest_segments, gallery_f16,
-                     nearest_segments_f16, gallery_i8, nearest_segments_i8, rerank, nearest_bins, nearest_bins_segments)
+                     nearest_segments_f16, gallery_i8, nearest_segments_i8, rerank, nearest_bins, nearest_bins_segments,
+                     gallery_mxfp4, mxfp4_decode, nearest_bins_segments_mxfp4)
 
 __version__ = "0.1.0"

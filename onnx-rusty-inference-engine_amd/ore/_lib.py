@@ -78,6 +78,7 @@ EXPORTED = [
     "ore_gallery_i8", "ore_nearest_i8", "ore_nearest_segments_i8",
     "ore_nearest_rerank_f32", "ore_nearest_rerank_f16",
     "ore_nearest_bins_f16", "ore_nearest_bins_i8", "ore_nearest_bins_segments",
+    "ore_gallery_mxfp4", "ore_nearest_bins_mxfp4", "ore_nearest_bins_segments_mxfp4",
 ]
 
 
@@ -249,6 +250,9 @@ def load():
         "ore_nearest_bins_f16": (i32, [vp, T, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_bins_i8": (i32, [vp, T, vp, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_bins_segments": (i32, [vp, i64, i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "ore_gallery_mxfp4": (i32, [vp, vp, i64, i64, vp, vp]),
+        "ore_nearest_bins_mxfp4": (i32, [vp, T, vp, vp, i64, i32, i32, vp, vp]),
+        "ore_nearest_bins_segments_mxfp4": (i32, [vp, i64, i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "ore_model_embed_dim": (i32, [vp, I64P]),
         "ore_model_set_embed": (i32, [vp, vp, i64, i32]),
         "ore_model_parse": (i32, [ctypes.c_char_p, ctypes.c_size_t]),

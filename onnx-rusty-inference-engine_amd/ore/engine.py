@@ -20,7 +20,7 @@ from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, 
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
-           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "gallery_i8", "nearest_segments_i8", "rerank", "nearest_bins", "nearest_bins_segments", "inference",
+           "global_average_pool", "concatenation", "drop_out", "reshape", "preprocess_u8", "preprocess_resize_u8", "ImageList", "Nv12ImageList", "YuvImageList", "yuv_to_rgb", "nv12_to_rgb", "yuv_planes_to_rgb", "preprocess_list_u8", "resize_taps", "resize_aa_taps", "resize_cubic_taps", "center_crop_geometry", "topk", "nearest", "nearest_segments", "gallery_f16", "nearest_segments_f16", "gallery_i8", "nearest_segments_i8", "rerank", "nearest_bins", "nearest_bins_segments", "gallery_mxfp4", "mxfp4_decode", "nearest_bins_segments_mxfp4", "inference",
            "conv_out_shape", "pool_out_shape"]
 
 
@@ -973,10 +973,17 @@ _rerank = rerank  # nearest() has a parameter of this name
 def _nearest_operands(ctx, q, gallery, scales):
     """The tensor checks of nearest() and nearest_bins(): (gallery dtype, n, D, G, q's descriptor)."""
     torch = _torch()
-    gdt = gallery.dtype if isinstance(gallery, torch.Tensor) and gallery.dtype in (torch.float16, torch.int8) else torch.float32
-    names = {torch.float32: "float32", torch.float16: "float16", torch.int8: "int8"}
-    if gdt != torch.int8 and scales is not None:
+    gdt = gallery.dtype if isinstance(gallery, torch.Tensor) and gallery.dtype in (torch.float16, torch.int8, torch.uint8) else torch.float32
+    names = {torch.float32: "float32", torch.float16: "float16", torch.int8: "int8", torch.uint8: "uint8"}
+    if gdt not in (torch.int8, torch.uint8) and scales is not None:
         raise OreError(1, f"scales: given with a {names[gdt]} gallery; only an int8 gallery has scales")
+    if gdt == torch.uint8:  # MXFP4 codes [G, 16 nb] with scale bytes [G, nb], nb from q's D
+        rows, nb = (int(gallery.shape[0]) if gallery.dim() else 0), (-(-int(q.shape[1]) // 32) if isinstance(q, torch.Tensor) and q.dim() == 2 else 0)
+        if scales is None:
+            raise OreError(1, "scales: an MXFP4 gallery needs its scale bytes (gallery_mxfp4() returns both)")
+        if (not isinstance(scales, torch.Tensor) or scales.dtype != torch.uint8 or tuple(scales.shape) != (rows, nb)
+                or not scales.is_contiguous() or not scales.is_cuda or scales.device.index != ctx.device):
+            raise OreError(1, f"scales: expected a contiguous uint8 [{rows}, {nb}] (ceil(D / 32) blocks) CUDA tensor on cuda:{ctx.device}")
     if gdt == torch.int8:  # the scales first: a call without them stays as it was
         rows = int(gallery.shape[0]) if gallery.dim() else 0
         if scales is None:
@@ -991,8 +998,9 @@ def _nearest_operands(ctx, q, gallery, scales):
             raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
     n, D = int(q.shape[0]), int(q.shape[1])
     G = int(gallery.shape[0])
-    if int(gallery.shape[1]) != D or not gallery.is_contiguous():
-        raise OreError(1, f"gallery: expected a contiguous [G, {D}] tensor, got {tuple(gallery.shape)}")
+    W = 16 * -(-D // 32) if gdt == torch.uint8 else D  # MXFP4: a row is whole blocks of 16 code bytes
+    if int(gallery.shape[1]) != W or not gallery.is_contiguous():
+        raise OreError(1, f"gallery: expected a contiguous [G, {W}] tensor, got {tuple(gallery.shape)}")
     if n > 1 and (q.stride(1) != 1 or q.stride(0) < D) or n <= 1 and not q.is_contiguous():
         raise OreError(1, "q: expected dense rows at a row stride of at least D")
     d = Tensor()
@@ -1007,7 +1015,10 @@ def nearest_bins(ctx: Context, q, gallery, c: int, bin_rows: int = 128, scales=N
     is kept, and the c best of those winners are returned as (values float32 [n, c], indices int32 [n, c]) in topk()'s
     order, 1 <= c <= min(ceil(G / bin_rows), 256).  Scores are nearest()'s of the same gallery to the bit, so whenever
     the exact top c rows lie in c different bins the result is nearest()'s; a neighbour is lost only to a better row
-    of its own bin.  gallery is float16 (gallery_f16()) or int8 with scales (gallery_i8()); q as for nearest()."""
+    of its own bin.  gallery is float16 (gallery_f16()) or int8 with scales (gallery_i8()); q as for nearest().
+    ore_nearest_bins_mxfp4: uint8 MXFP4 codes [G, 16 nb] with uint8 scales [G, nb] (gallery_mxfp4()), nb = ceil(D / 32)
+    from q's D <= 4096; q is quantised to MXFP4 per block inside the kernel and the score is the scaled matrix
+    instruction's -- a first stage only, to be followed by rerank()."""
     torch = _torch()
     if isinstance(gallery, torch.Tensor) and gallery.dtype == torch.float32:
         raise OreError(1, "gallery: nearest_bins() runs on a float16 or an int8 gallery (gallery_f16(), gallery_i8()), not float32")
@@ -1023,12 +1034,24 @@ def nearest_bins(ctx: Context, q, gallery, c: int, bin_rows: int = 128, scales=N
     if n == 0:
         return values, indices
     out = (G, B, c, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr()))
-    if gdt == torch.int8:
-        check(load().ore_nearest_bins_i8(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()),
-                                         ctypes.c_void_p(scales.data_ptr()), *out), ctx.h)
+    if gdt in (torch.int8, torch.uint8):
+        entry = load().ore_nearest_bins_i8 if gdt == torch.int8 else load().ore_nearest_bins_mxfp4
+        check(entry(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), ctypes.c_void_p(scales.data_ptr()), *out), ctx.h)
     else:
         check(load().ore_nearest_bins_f16(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), *out), ctx.h)
     return values, indices
+
+
+def _is_mxfp4(gallery):
+    torch = _torch()
+    return isinstance(gallery, torch.Tensor) and gallery.dtype == torch.uint8
+
+
+def nearest_bins_segments_mxfp4(ctx: Context, n: int, G: int, bin_rows: int = 128):
+    """ore_nearest_bins_segments_mxfp4: (gallery segments, bins) of nearest_bins() on an MXFP4 gallery."""
+    s, b = ctypes.c_int32(), ctypes.c_int32()
+    check(load().ore_nearest_bins_segments_mxfp4(ctx.h, int(n), int(G), int(bin_rows), ctypes.byref(s), ctypes.byref(b)), ctx.h)
+    return s.value, b.value
 
 
 def nearest_bins_segments(ctx: Context, n: int, G: int, bin_rows: int = 128):
@@ -1051,7 +1074,10 @@ def nearest(ctx: Context, q, gallery, k: int, scales=None, rerank=None, candidat
     `candidates` results per query (default min(G, 64, 8 k); in k..min(G, 64)) and rerank() of those against `rerank`
     is returned, [n, k].  `candidates` without `rerank` is an error.  With `bin_rows` as well the first stage is
     nearest_bins() on a float16 or int8 gallery: `candidates` (default min(bins, 256, 8 k)) is then in k..min(bins, 256),
-    bins = ceil(G / bin_rows).  `bin_rows` without `rerank` is an error."""
+    bins = ceil(G / bin_rows).  `bin_rows` without `rerank` is an error.  An MXFP4 gallery (uint8 codes with uint8
+    scales, gallery_mxfp4()) is a first stage only: it needs both `rerank` and `bin_rows`."""
+    if _is_mxfp4(gallery) and (rerank is None or bin_rows is None):
+        raise OreError(1, "gallery: MXFP4 is a first stage only; give rerank= and bin_rows= (there is no top-k on FP4 scores)")
     if rerank is None and candidates is not None:
         raise OreError(1, "candidates: given without rerank; only the two-stage form has candidates")
     if rerank is None and bin_rows is not None:
@@ -1060,7 +1086,11 @@ def nearest(ctx: Context, q, gallery, k: int, scales=None, rerank=None, candidat
         torch = _torch()
         if not isinstance(rerank, torch.Tensor) or rerank.dtype not in (torch.float32, torch.float16) or rerank.dim() != 2:
             raise OreError(1, "rerank: expected a 2-D float32 or float16 CUDA tensor")
-        if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2 or tuple(rerank.shape) != tuple(gallery.shape):
+        if _is_mxfp4(gallery):  # G and the blocks: the codes' rows are 16 bytes per block of 32 d
+            same = gallery.dim() == 2 and rerank.shape[0] == gallery.shape[0] and 16 * -(-int(rerank.shape[1]) // 32) == gallery.shape[1]
+        else:
+            same = isinstance(gallery, torch.Tensor) and gallery.dim() == 2 and tuple(rerank.shape) == tuple(gallery.shape)
+        if not same:
             raise OreError(1, f"rerank: expected the gallery's [G, D], got {tuple(rerank.shape)}")
         G = int(gallery.shape[0])
         if bin_rows is not None:
@@ -1144,6 +1174,38 @@ def gallery_i8(ctx: Context, gallery):
     check(load().ore_gallery_i8(ctx.h, ctypes.c_void_p(gallery.data_ptr()), int(gallery.shape[0]), int(gallery.shape[1]),
                                 ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(scales.data_ptr())), ctx.h)
     return codes, scales
+
+
+def gallery_mxfp4(ctx: Context, gallery):
+    """ore_gallery_mxfp4: a contiguous float32 [G, D] gallery as (codes torch.uint8 [G, 16 nb], scales torch.uint8
+    [G, nb]), nb = ceil(D / 32), for nearest_bins() and the two-stage nearest(): per block of 32 elements one E8M0 scale
+    byte b (the biased exponent of the block's largest magnitude, less 2) and 4-bit E2M1 codes of x / 2^(b - 127), ties
+    to the even code, saturated at 6; two codes per byte, the even element in the low nibble."""
+    torch = _torch()
+    _check_gallery_f32(ctx, torch, gallery)
+    G, nb = int(gallery.shape[0]), -(-int(gallery.shape[1]) // 32)
+    codes = torch.empty((G, 16 * nb), dtype=torch.uint8, device=gallery.device)
+    scales = torch.empty((G, nb), dtype=torch.uint8, device=gallery.device)
+    check(load().ore_gallery_mxfp4(ctx.h, ctypes.c_void_p(gallery.data_ptr()), G, int(gallery.shape[1]),
+                                   ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(scales.data_ptr())), ctx.h)
+    return codes, scales
+
+
+def mxfp4_decode(codes, scales, D: int):
+    """The values an MXFP4 gallery stands for, float32 [G, D]: the host and torch restatement of include/ore.h's format.
+    codes uint8 [G, 16 nb] and scales uint8 [G, nb] as torch tensors (any device) or numpy arrays; the result is of the
+    same kind.  Element d of a row is (-1)^sign * magnitude * 2^(scale byte of block d // 32 - 127); byte 255 is a NaN."""
+    torch = _torch()
+    as_numpy = not isinstance(codes, torch.Tensor)
+    c, t = (torch.from_numpy(x) if as_numpy else x for x in (codes, scales))
+    G, nb = int(t.shape[0]), int(t.shape[1])
+    if c.dtype != torch.uint8 or t.dtype != torch.uint8 or tuple(c.shape) != (G, 16 * nb) or not 32 * (nb - 1) < int(D) <= 32 * nb:
+        raise OreError(1, f"mxfp4_decode: expected uint8 codes [G, 16 nb] and scales [G, nb] with nb = ceil(D / 32), D = {D}")
+    nib = torch.stack((c & 15, c >> 4), dim=2).reshape(G, nb, 32).long()  # element 2 i: the low nibble of byte i
+    lut = torch.tensor([0, 0.5, 1, 1.5, 2, 3, 4, 6, -0.0, -0.5, -1, -1.5, -2, -3, -4, -6], dtype=torch.float32, device=c.device)
+    v = torch.ldexp(lut[nib], (t.int() - 127)[:, :, None])
+    v = torch.where((t == 255)[:, :, None], torch.full_like(v, float("nan")), v).reshape(G, 32 * nb)[:, :int(D)].contiguous()
+    return v.numpy() if as_numpy else v
 
 
 def nearest_segments_i8(ctx: Context, n: int, G: int):
