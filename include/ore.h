@@ -1105,6 +1105,49 @@ ore_status ore_nearest_rerank_f32(ore_ctx* ctx, const ore_tensor* q, const float
                                   int64_t cand_stride, int32_t C, int32_t k, float* values, int32_t* indices);
 ore_status ore_nearest_rerank_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, const int32_t* candidates,
                                   int64_t cand_stride, int32_t C, int32_t k, float* values, int32_t* indices);
+/* ---- extension: inverted-file search, probe a few lists of a clustered f16 gallery --------------------------------
+ * Every search above reads the whole gallery.  An inverted file clusters it once, stores it list by list, and per query
+ * scores only the rows of the few lists whose centroids are nearest (ore_nearest_f32(q, centroids, nprobe) is that coarse
+ * stage).  ore_nearest_lists_f16 is the scan in between.
+ *  An IVF gallery is a contiguous DEVICE binary16 array [G, D] whose rows are stored list by list, and DEVICE offsets
+ *    int32 [L + 1] with 0 = offsets[0] <= ... <= offsets[L] = G: list l is rows [offsets[l], offsets[l + 1]) and may be
+ *    empty.  probes is a DEVICE int32 array, row i of it the P entries at probes + i * probe_stride, probe_stride >= P,
+ *    1 <= P <= 64: the lists of query i.  An entry outside [0, L) is padding (pad with -1); a list named twice in a row
+ *    counts once.
+ *  Result.  Row i of values / indices (contiguous DEVICE [n, k], 1 <= k <= 64) is ore_topk_f32's order applied to
+ *    s[i, j] over the rows j of the union of query i's lists: larger first, equal scores (-0 equal to +0) to the lower
+ *    position, every NaN after every number.  Indices are positions in this list-ordered gallery.  Ranks past the size
+ *    of the union hold index -1 and the value bits 0x7fc00000 (ore_nearest_rerank_*'s rule).
+ *  Bit contract.  s[i, j] is, to the bit, what ore_nearest_f16 returns for the pair: the query rounded to nearest even
+ *    to f16 inside the kernel, v_mfma_f32_16x16x32_f16 with lane l supplying d = 32 kg + 8 (l >> 4) + e, gallery row = A,
+ *    query = B, one accumulator chain over the k-groups ascending from +0.  So row i of the result depends on q[i, :],
+ *    the gallery, offsets and row i of probes alone -- not on n, on which other queries share a list, on the chunking or
+ *    on the load path -- and with every list probed it is ore_nearest_f16's result, values and indices.
+ *  q is f32 exactly as for ore_nearest_f32.  1 <= D <= ORE_IVF_MAX_D: the query tile is always resident.  The gallery may
+ *    start at any 2-byte aligned address; 16-byte loads are used where D % 8 == 0 and the base allows.
+ *  ore_ivf_chunks (host only, no device call): the static work table [count][2] = (list, first row) of an index, every
+ *    non-empty list in chunks of ORE_IVF_CHUNK_ROWS rows, the last chunk of a list shorter; count <= G / ORE_IVF_CHUNK_ROWS
+ *    + L.  With chunks_host == NULL it returns the count alone.  Build it once per index and upload it: `chunks` below is
+ *    that table on the DEVICE, n_chunks its count.  max_list_rows is an upper bound of the longest list's rows, 1..G; rows
+ *    of a list past it are not searched.  With a table other than ore_ivf_chunks' for these offsets the result is
+ *    unspecified; whatever offsets, chunks and probes hold, nothing outside the gallery's G D elements, q's rows and the
+ *    tables' stated extents is read: entries are clipped or skipped on the device.
+ *  Checked from the arguments alone, before the context and any device call (ORE_ERR_INVALID, the message names the
+ *    quantity), in this order: ore_nearest_f16's checks (null q, gallery, values, indices; q's dims; D; G; k outside
+ *    1..min(G, 64); the nstride rule); D > ORE_IVF_MAX_D; offsets null; L outside 1..2^30-1; chunks null; n_chunks
+ *    outside 1..G / ORE_IVF_CHUNK_ROWS + L; max_list_rows outside 1..G; probes null; probe_stride outside 1..2^31-1; P
+ *    outside 1..min(probe_stride, 64); n P >= 2^31.  n == 0 is ORE_OK and launches nothing.
+ *  No device-to-host read happens inside the call; everything is sized from the arguments.  Scratch (the per-list pair
+ *    tables and the partial keys [n P][ceil(max_list_rows / ORE_IVF_CHUNK_ROWS)][k]) is the context's partial buffer of
+ *    the searches, under its growth and capture rule (make one call of the shape before capturing) and
+ *    ore_ctx_set_alloc_fill: every byte read was written by the same call.  Above 256 MiB of partial keys the queries go
+ *    through in slabs. */
+#define ORE_IVF_CHUNK_ROWS 256
+#define ORE_IVF_MAX_D 512
+ore_status ore_ivf_chunks(const int32_t* offsets_host, int32_t L, int32_t* chunks_host, int32_t* count);
+ore_status ore_nearest_lists_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, const int32_t* offsets, int32_t L,
+                                 const int32_t* chunks, int32_t n_chunks, int32_t max_list_rows, const int32_t* probes,
+                                 int64_t probe_stride, int32_t P, int32_t k, float* values, int32_t* indices);
 ore_status ore_model_embed_dim(ore_model* m, int64_t* dim);
 ore_status ore_model_set_embed(ore_model* m, float* d_embed, int64_t cap_elems, int32_t flags);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);

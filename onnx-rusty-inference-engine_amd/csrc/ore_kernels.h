@@ -654,6 +654,16 @@ int nearest_bins_segments_mxfp4(long long n, long long G, int ncu, int bin_rows)
 void launch_gallery_mxfp4(const float* src, long long G, long long D, void* codes, void* scales, hipStream_t s);
 void launch_nearest_bins_mxfp4(const float* q, long long q_stride, int n, int D, const void* codes, const void* scales, long long G,
                                int bin_rows, int S, void* win, hipStream_t s);
+// the inverted-file search (ore_nearest_lists.hip; include/ore.h states the gallery, offsets, chunks and probes): per query
+// the k best rows of the union of its P probed lists, scored to the bits of launch_nearest_f16, ranks past the union
+// as index -1 and the quiet NaN.  C = ceil(max_list_rows / nearest_lists_chunk_rows()) chunk slots per pair; scratch
+// holds nearest_lists_bytes(n, P, L, C, k) bytes, every byte read written by the same call.  Six launches.
+int nearest_lists_chunk_rows();
+int nearest_lists_max_d();
+size_t nearest_lists_bytes(long long n, int P, int L, int C, int k);
+void launch_nearest_lists_f16(const float* q, long long q_stride, int n, int D, const void* gallery, long long G, const int* offsets,
+                              int L, const int* chunks, int n_chunks, int C, const int* probes, long long probe_stride, int P, int k,
+                              void* scratch, float* values, int* indices, hipStream_t s);
 // rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 

@@ -1102,6 +1102,68 @@ ore_status ore_nearest_rerank_f16(ore_ctx* ctx, const ore_tensor* q, const uint1
   return nearest_rerank_run(ctx, NearestFmt::F16, q, gallery, G, candidates, cand_stride, C, k, values, indices);
 }
 
+// ore_ivf_chunks: the work table of an inverted-file gallery, host only
+ore_status ore_ivf_chunks(const int32_t* offsets_host, int32_t L, int32_t* chunks_host, int32_t* count) {
+  if (!offsets_host || !count) return set_error(nullptr, ORE_ERR_INVALID, "null argument");
+  if (L < 1) return set_error(nullptr, ORE_ERR_INVALID, "ivf_chunks: L = %d below 1", int(L));
+  if (offsets_host[0] != 0) return set_error(nullptr, ORE_ERR_INVALID, "ivf_chunks: offsets[0] = %d, expected 0", int(offsets_host[0]));
+  const int R = nearest_lists_chunk_rows();
+  int64_t c = 0;
+  for (int32_t l = 0; l < L; ++l) {
+    if (offsets_host[l + 1] < offsets_host[l])
+      return set_error(nullptr, ORE_ERR_INVALID, "ivf_chunks: offsets[%d] = %d below offsets[%d] = %d", int(l + 1),
+                       int(offsets_host[l + 1]), int(l), int(offsets_host[l]));
+    for (int64_t r = offsets_host[l]; r < offsets_host[l + 1]; r += R, ++c)
+      if (chunks_host) {
+        chunks_host[2 * c] = l;
+        chunks_host[2 * c + 1] = int32_t(r);
+      }
+  }
+  *count = int32_t(c);  // <= G / R + L < 2^31
+  return ORE_OK;
+}
+
+// ore_nearest_lists_f16: ore_nearest_f16's checks in their order, then the new arguments in the header's, the context
+// last.  The scratch (the inversion's tables and the partial keys) is the searches' partial buffer under its capture
+// rule; above NEAREST_BINS_SLAB bytes of partial keys the queries go through in slabs
+ore_status ore_nearest_lists_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, const int32_t* offsets, int32_t L,
+                                 const int32_t* chunks, int32_t n_chunks, int32_t max_list_rows, const int32_t* probes,
+                                 int64_t probe_stride, int32_t P, int32_t k, float* values, int32_t* indices) {
+  int64_t n = 0, D = 0;
+  if (const ore_status st = nearest_check(ctx, q, gallery, G, k, values, indices, &n, &D)) return st;
+  const int R = nearest_lists_chunk_rows();
+  if (D > nearest_lists_max_d())
+    return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: D = %lld above %d, the resident query tile's limit", (long long)D, nearest_lists_max_d());
+  if (!offsets) return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: offsets is null");
+  if (L < 1 || L >= (1 << 30)) return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: L = %d outside 1..2^30-1", int(L));
+  if (!chunks) return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: chunks is null");
+  if (n_chunks < 1 || n_chunks > G / R + L)
+    return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: n_chunks = %d outside 1..%lld (G / %d + L)", int(n_chunks), (long long)(G / R + L), R);
+  if (max_list_rows < 1 || max_list_rows > G)
+    return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: max_list_rows = %d outside 1..%lld (G)", int(max_list_rows), (long long)G);
+  if (!probes) return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: probes is null");
+  if (probe_stride < 1 || !fits_i32(probe_stride))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: probe_stride = %lld outside 1..2^31-1", (long long)probe_stride);
+  if (P < 1 || P > std::min<int64_t>(probe_stride, 64))
+    return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: P = %d outside 1..%lld (min(probe_stride, 64))", int(P),
+                     (long long)std::min<int64_t>(probe_stride, 64));
+  if (!fits_i32(n * P)) return set_error(ctx, ORE_ERR_INVALID, "nearest_lists: n P = %lld pairs past 2^31-1", (long long)(n * P));
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (n == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int C = (max_list_rows + R - 1) / R;
+  const int64_t slab = std::min<int64_t>(n, std::max<int64_t>(int64_t(NEAREST_BINS_SLAB / (size_t(P) * C * k * 8)), 1));
+  if (const ore_status st = nearest_grow_part(ctx, nearest_lists_bytes(slab, P, L, C, k))) return st;
+  for (int64_t i0 = 0; i0 < n; i0 += slab) {
+    const int m = int(std::min(slab, n - i0));
+    launch_nearest_lists_f16(q->data + i0 * nstride_of(q), nstride_of(q), m, int(D), gallery, G, offsets, L, chunks, n_chunks, C,
+                             probes + i0 * probe_stride, probe_stride, P, k, ctx->nearest_part, values + i0 * k, indices + i0 * k,
+                             ctx->stream);
+  }
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
 // the three ore_nearest_segments entries: segments and the format's gallery rows per step
 static ore_status nearest_split(ore_ctx* ctx, NearestFmt fmt, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
   if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");

@@ -30,6 +30,8 @@ CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD = 0, 1  # ore_ctx_set_conv_algo (per-op ore
 PRE_REVERSE_CHANNELS = 1  # ore_preprocess_u8 / _resize_u8 / ore_model_set_input_norm flag: RGB <-> BGR
 FILTER_BILINEAR, FILTER_BILINEAR_AA = 0, 1  # ore_resize_filter (the _ex resize entries)
 FILTER_CUBIC_BIT, FILTER_BICUBIC, FILTER_BICUBIC_AA = 256, 256, 257  # ORE_FILTER_BICUBIC*: values of the filter word beside the enum
+IVF_CHUNK_ROWS = 256  # ORE_IVF_CHUNK_ROWS: gallery rows per chunk of nearest_lists()'s work table
+IVF_MAX_D = 512  # ORE_IVF_MAX_D
 CUBIC_AA_MAX_RATIO = 16  # ORE_CUBIC_AA_MAX_RATIO: the antialiased cubic filter's shrink limit
 AA_MAX_RATIO, AA_MAX_TAPS = 32, 64  # ORE_AA_MAX_RATIO / ORE_AA_MAX_TAPS: the antialiased filter's shrink limit and taps per axis
 YUV_BT601, YUV_BT709, YUV_BT601_FULL = 0, 1, 2  # ore_yuv_matrix (ore_yuv_to_rgb, the NV12 image lists)
@@ -79,6 +81,7 @@ EXPORTED = [
     "ore_nearest_rerank_f32", "ore_nearest_rerank_f16",
     "ore_nearest_bins_f16", "ore_nearest_bins_i8", "ore_nearest_bins_segments",
     "ore_gallery_mxfp4", "ore_nearest_bins_mxfp4", "ore_nearest_bins_segments_mxfp4",
+    "ore_ivf_chunks", "ore_nearest_lists_f16",
 ]
 
 
@@ -247,6 +250,8 @@ def load():
         "ore_nearest_segments_i8": (i32, [vp, i64, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "ore_nearest_rerank_f32": (i32, [vp, T, vp, i64, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_rerank_f16": (i32, [vp, T, vp, i64, vp, i64, i32, i32, vp, vp]),
+        "ore_ivf_chunks": (i32, [vp, i32, vp, vp]),
+        "ore_nearest_lists_f16": (i32, [vp, T, vp, i64, vp, i32, vp, i32, i32, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_bins_f16": (i32, [vp, T, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_bins_i8": (i32, [vp, T, vp, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_bins_segments": (i32, [vp, i64, i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),

@@ -970,6 +970,108 @@ def rerank(ctx: Context, q, gallery, candidates, k: int):
 _rerank = rerank  # nearest() has a parameter of this name
 
 
+def ivf_chunks(offsets):
+    """ore_ivf_chunks: the work table int32 [count, 2] = (list, first row) of an inverted-file gallery with the host
+    offsets int32 [L + 1] -- every non-empty list in chunks of IVF_CHUNK_ROWS rows, as a CPU tensor."""
+    torch = _torch()
+    if not isinstance(offsets, torch.Tensor) or offsets.is_cuda or offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise OreError(1, "offsets: expected a 1-D int32 CPU tensor of L + 1 entries")
+    offsets = offsets.contiguous()
+    count = ctypes.c_int32()
+    args = (ctypes.c_void_p(offsets.data_ptr()), int(offsets.numel()) - 1)
+    check(load().ore_ivf_chunks(*args, None, ctypes.byref(count)), None)
+    chunks = torch.empty((count.value, 2), dtype=torch.int32)
+    check(load().ore_ivf_chunks(*args, ctypes.c_void_p(chunks.data_ptr()), ctypes.byref(count)), None)
+    return chunks
+
+
+def nearest_lists(ctx: Context, q, gallery, offsets, chunks, probes, k: int, max_list_rows: int):
+    """ore_nearest_lists_f16 (extension): the scan of an inverted-file search.  gallery is a contiguous float16 [G, D]
+    tensor whose rows are stored list by list, offsets int32 [L + 1] (list l is rows offsets[l] .. offsets[l + 1]),
+    chunks int32 [count, 2] the table of ivf_chunks() for these offsets, all on the device; probes int32 [n, P] names
+    the lists of every row of q (probes.stride(1) == 1, probes.stride(0) >= P; an entry outside [0, L) is padding, a
+    list named twice counts once).  Returns (values float32 [n, k], indices int32 [n, k]): the k best rows of the union
+    of the row's lists in topk()'s order, scored to the bits of nearest() on a float16 gallery, indices as positions in
+    this gallery; ranks past the union hold index -1 and a NaN.  1 <= D <= 512, 1 <= P <= 64, 1 <= k <= min(G, 64);
+    max_list_rows bounds the longest list."""
+    torch = _torch()
+    names = {torch.float32: "float32", torch.float16: "float16", torch.int32: "int32"}
+    for name, t, dt, dim in (("q", q, torch.float32, 2), ("gallery", gallery, torch.float16, 2), ("offsets", offsets, torch.int32, 1),
+                             ("chunks", chunks, torch.int32, 2), ("probes", probes, torch.int32, 2)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or t.dim() != dim:
+            raise OreError(1, f"{name}: expected a {dim}-D {names[dt]} CUDA tensor")
+        if t.device.index != ctx.device:
+            raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
+    n, D = int(q.shape[0]), int(q.shape[1])
+    G, L, P = int(gallery.shape[0]), int(offsets.numel()) - 1, int(probes.shape[1])
+    if int(gallery.shape[1]) != D or not gallery.is_contiguous():
+        raise OreError(1, f"gallery: expected a contiguous [G, {D}] tensor, got {tuple(gallery.shape)}")
+    if n > 1 and (q.stride(1) != 1 or q.stride(0) < D) or n <= 1 and not q.is_contiguous():
+        raise OreError(1, "q: expected dense rows at a row stride of at least D")
+    if L < 1 or not offsets.is_contiguous():
+        raise OreError(1, "offsets: expected a contiguous [L + 1] tensor, L >= 1")
+    if int(chunks.shape[0]) < 1 or int(chunks.shape[1]) != 2 or not chunks.is_contiguous():
+        raise OreError(1, f"chunks: expected a contiguous [count, 2] tensor (ivf_chunks()), got {tuple(chunks.shape)}")
+    if int(probes.shape[0]) != n or not 1 <= P <= 64:
+        raise OreError(1, f"probes: expected [{n}, P] with P in 1..64, got {tuple(probes.shape)}")
+    if P > 1 and probes.stride(1) != 1 or n > 1 and probes.stride(0) < P:
+        raise OreError(1, "probes: expected dense rows at a row stride of at least P")
+    if not 1 <= int(k) <= min(G, 64):
+        raise OreError(1, f"k = {k} outside 1..{min(G, 64)} (min(G, 64))")
+    values = torch.empty((n, int(k)), dtype=torch.float32, device=q.device)
+    indices = torch.empty((n, int(k)), dtype=torch.int32, device=q.device)
+    if n == 0:
+        return values, indices
+    d = Tensor()
+    d.data, d.ndim, d.nstride = q.data_ptr(), 2, (int(q.stride(0)) if n > 1 else 0)
+    d.dims[0], d.dims[1] = n, D
+    check(load().ore_nearest_lists_f16(ctx.h, ctypes.byref(d), ctypes.c_void_p(gallery.data_ptr()), G, ctypes.c_void_p(offsets.data_ptr()), L,
+                                       ctypes.c_void_p(chunks.data_ptr()), int(chunks.shape[0]), int(max_list_rows),
+                                       ctypes.c_void_p(probes.data_ptr()), int(probes.stride(0)) if n > 1 else P, P, int(k),
+                                       ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(indices.data_ptr())), ctx.h)
+    return values, indices
+
+
+class IvfIndex:
+    """An inverted-file index (ivf_build()): gallery float16 [G, D] stored list by list, offsets int32 [L + 1], chunks
+    (ivf_chunks()), max_list_rows, centroids float32 [L, D] and ids int32 [G], the original row of each stored row."""
+
+    def __init__(self, ctx, gallery, offsets, chunks, max_list_rows, centroids, ids):
+        self.ctx, self.gallery, self.offsets, self.chunks = ctx, gallery, offsets, chunks
+        self.max_list_rows, self.centroids, self.ids = max_list_rows, centroids, ids
+
+    def search(self, q, k: int, nprobe: int, rerank=None):
+        """The k nearest rows of every row of q among the nprobe lists whose centroids are nearest to it: (values, indices
+        in the original row order).  The order among equal scores is by stored position (list, then original row), not
+        by original row; ranks past the probed lists' rows hold -1 and a NaN.  With rerank=, the float32 gallery in the
+        original row order, min(8 k, 64) results of the scan go through ore.rerank against it."""
+        torch = _torch()
+        probes = nearest(self.ctx, q, self.centroids, int(nprobe))[1]
+        kk = int(k) if rerank is None else min(8 * int(k), 64, int(self.gallery.shape[0]))
+        values, pos = nearest_lists(self.ctx, q, self.gallery, self.offsets, self.chunks, probes, kk, self.max_list_rows)
+        indices = torch.where(pos >= 0, self.ids[pos.clamp(min=0).long()], pos)
+        if rerank is None:
+            return values, indices
+        return _rerank(self.ctx, q, rerank, indices, int(k))
+
+
+def ivf_build(ctx: Context, gallery, centroids, slab: int = 1 << 16) -> IvfIndex:
+    """Build an IvfIndex: every row of the float32 [G, D] gallery goes to the centroid (float32 [L, D]) with the largest
+    inner product (nearest(rows, centroids, 1), in slabs of rows), the rows are ordered by (list, original row) with a
+    stable sort and packed with gallery_f16().  Not a hot path: the bookkeeping is torch."""
+    torch = _torch()
+    _check_gallery_f32(ctx, torch, gallery)
+    _check_gallery_f32(ctx, torch, centroids)
+    G, L = int(gallery.shape[0]), int(centroids.shape[0])
+    assign = torch.cat([nearest(ctx, gallery[i:i + slab], centroids, 1)[1][:, 0] for i in range(0, G, slab)])
+    ids = torch.sort(assign, stable=True)[1].to(torch.int32)
+    offsets = torch.zeros(L + 1, dtype=torch.int32)
+    offsets[1:] = torch.cumsum(torch.bincount(assign.cpu().long(), minlength=L), 0).to(torch.int32)
+    packed = gallery_f16(ctx, gallery[ids.long()].contiguous())
+    max_rows = int((offsets[1:] - offsets[:-1]).max())
+    return IvfIndex(ctx, packed, offsets.to(gallery.device), ivf_chunks(offsets).to(gallery.device), max_rows, centroids, ids)
+
+
 def _nearest_operands(ctx, q, gallery, scales):
     """The tensor checks of nearest() and nearest_bins(): (gallery dtype, n, D, G, q's descriptor)."""
     torch = _torch()
