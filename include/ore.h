@@ -1148,6 +1148,35 @@ ore_status ore_ivf_chunks(const int32_t* offsets_host, int32_t L, int32_t* chunk
 ore_status ore_nearest_lists_f16(ore_ctx* ctx, const ore_tensor* q, const uint16_t* gallery, int64_t G, const int32_t* offsets, int32_t L,
                                  const int32_t* chunks, int32_t n_chunks, int32_t max_list_rows, const int32_t* probes,
                                  int64_t probe_stride, int32_t P, int32_t k, float* values, int32_t* indices);
+/* ---- extension: spherical k-means, one Lloyd iteration on the device: the centroids of an inverted file ------------
+ * ore_nearest_lists_f16 needs a gallery clustered around centroids; this entry trains them.  One call assigns every
+ * sample row to the centroid with the largest inner product (the rule of the coarse stage) and replaces every centroid by
+ * the normalised sum of its rows.
+ *  x is f32 [S, D] exactly as q of ore_nearest_f32 (2-D to 4-D, nstride >= D honoured, any 4-byte aligned base), 1 <= D
+ *    <= ORE_KMEANS_MAX_D.  centroids and centroids_out are contiguous DEVICE f32 [L, D], 1 <= L <= ORE_KMEANS_MAX_L;
+ *    centroids_out may equal centroids, any other overlap is undefined.  assign int32 [S], scores f32 [S] (may be NULL)
+ *    and counts int32 [L] are contiguous DEVICE arrays.
+ *  Assignment, bit contract.  scores[i] and assign[i] are, to the bit, value and index of ore_nearest_f16(x, the centroids
+ *    rounded by ore_gallery_f16, k = 1) for row i: the sample rounded to nearest even to f16 inside the kernel,
+ *    v_mfma_f32_16x16x32_f16 with lane l supplying d = 32 kg + 8 (l >> 4) + e, centroid row = A, sample = B, one
+ *    accumulator chain over the k-groups ascending from +0; ore_topk_f32's order: larger first, -0 equal to +0, equal
+ *    scores to the lower centroid, every NaN after every number.  Row i depends on x[i, :] and the centroids alone.
+ *  Update.  counts[l] is the number of rows with assign == l.  sum_d is the sum of those rows' x[i, d] in f64, added in
+ *    ascending row order; norm2 = sum over d of sum_d^2 in f64 in a fixed order; centroids_out[l, d] = (float)(sum_d /
+ *    sqrt(norm2)).  A centroid with no row, or with norm2 == 0 or not finite, keeps the bits of centroids[l, :].  No
+ *    atomics: the same inputs give the same output bits, however the workgroups are scheduled.
+ *  Checked from the arguments alone, before the context and any device call (ORE_ERR_INVALID, the message names the
+ *    quantity), in this order: null x, x->data, centroids, centroids_out, assign, counts; x not 2-D to 4-D (or S < 0);
+ *    D outside 1..ORE_KMEANS_MAX_D; S > 2^31 - 65; L outside 1..ORE_KMEANS_MAX_L; the nstride rule at the top of this
+ *    file; a null context.  S == 0 is ORE_OK and launches nothing.
+ *  Three launches on the context's stream (ore_gallery_f16's rounding of the centroids, the assignment, the update) and
+ *    no device-to-host read.  Scratch (the rounded centroids, 2 L D bytes) is the context's partial buffer of the
+ *    searches, under its growth and capture rule (make one call of the shape before capturing) and
+ *    ore_ctx_set_alloc_fill: every byte read was written by the same call. */
+#define ORE_KMEANS_MAX_D 512
+#define ORE_KMEANS_MAX_L 65536
+ore_status ore_kmeans_step_f32(ore_ctx* ctx, const ore_tensor* x, const float* centroids, int32_t L, float* centroids_out,
+                               int32_t* assign, float* scores, int32_t* counts);
 ore_status ore_model_embed_dim(ore_model* m, int64_t* dim);
 ore_status ore_model_set_embed(ore_model* m, float* d_embed, int64_t cap_elems, int32_t flags);
 ore_status ore_model_enable_timing(ore_model* m, int32_t on);

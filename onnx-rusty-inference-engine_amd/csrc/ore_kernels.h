@@ -664,6 +664,17 @@ size_t nearest_lists_bytes(long long n, int P, int L, int C, int k);
 void launch_nearest_lists_f16(const float* q, long long q_stride, int n, int D, const void* gallery, long long G, const int* offsets,
                               int L, const int* chunks, int n_chunks, int C, const int* probes, long long probe_stride, int P, int k,
                               void* scratch, float* values, int* indices, hipStream_t s);
+// one Lloyd iteration of spherical k-means (ore_kmeans.hip; include/ore.h states both contracts).  assign: per row of x
+// (as q above, S rows) index and score of the best of the L rows of centroids_f16 (contiguous binary16 [L][D],
+// kmeans_scratch_bytes(L, D) bytes, made by launch_gallery_f16), to the bits of launch_nearest_f16 with k = 1; scores
+// may be null; 1 <= D <= ORE_KMEANS_MAX_D, 1 <= L <= ORE_KMEANS_MAX_L, S <= 2^31 - 65.  update: counts [L] and the
+// normalised f64 sums of the rows of every centroid as centroids_out [L][D], which may be centroids; a centroid with no
+// row or no finite non-zero norm keeps its bits.  One launch each, no atomics, no buffer.
+size_t kmeans_scratch_bytes(int L, int D);
+void launch_kmeans_assign(const float* x, long long x_stride, int S, int D, const void* centroids_f16, int L, int* assign,
+                          float* scores, hipStream_t s);
+void launch_kmeans_update(const float* x, long long x_stride, int S, int D, const float* centroids, int L, const int* assign,
+                          float* centroids_out, int* counts, hipStream_t s);
 // rows of C floats, contiguous, each divided by its Euclidean norm in place; a zero row stays zero
 void launch_l2_normalize(float* e, long long rows, int C, hipStream_t s);
 

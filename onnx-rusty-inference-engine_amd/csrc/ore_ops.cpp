@@ -1164,6 +1164,35 @@ ore_status ore_nearest_lists_f16(ore_ctx* ctx, const ore_tensor* q, const uint16
   return ORE_OK;
 }
 
+// ore_kmeans_step_f32: the checks in the header's order, the context last.  The rounded centroids live in the searches'
+// partial buffer under its capture rule; three launches
+ore_status ore_kmeans_step_f32(ore_ctx* ctx, const ore_tensor* x, const float* centroids, int32_t L, float* centroids_out,
+                               int32_t* assign, float* scores, int32_t* counts) {
+  if (!x || !x->data || !centroids || !centroids_out || !assign || !counts) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (x->ndim < 2 || x->ndim > 4 || x->dims[0] < 0)
+    return set_error(ctx, ORE_ERR_INVALID, "kmeans: x of %d dims and %lld rows, expected [S, D] in 2 to 4 dims", int(x->ndim),
+                     (long long)(x->ndim >= 1 && x->ndim <= 4 ? x->dims[0] : 0));
+  const int64_t S = x->dims[0], lim = int64_t(1) << 31;
+  int64_t D = 1;
+  for (int i = 1; i < x->ndim; ++i) D = x->dims[i] >= 1 && D >= 1 && D * x->dims[i] < lim ? D * x->dims[i] : 0;
+  if (D < 1 || D > ORE_KMEANS_MAX_D)
+    return set_error(ctx, ORE_ERR_INVALID, "kmeans: D = %lld outside 1..%d, the resident sample tile's limit", (long long)D, ORE_KMEANS_MAX_D);
+  if (S > lim - 65) return set_error(ctx, ORE_ERR_INVALID, "kmeans: S = %lld above 2^31-65", (long long)S);
+  if (L < 1 || L > ORE_KMEANS_MAX_L) return set_error(ctx, ORE_ERR_INVALID, "kmeans: L = %d outside 1..%d", int(L), ORE_KMEANS_MAX_L);
+  if (x->nstride < 0 || (x->nstride && (x->nstride < D || x->nstride >= lim || !fits_i32(x->nstride * std::max<int64_t>(S, 1) + 256))))
+    return set_error(ctx, ORE_ERR_INVALID, "kmeans: x->nstride %lld with %lld rows of %lld: below the row length or past 32-bit indexing",
+                     (long long)x->nstride, (long long)S, (long long)D);
+  if (!ctx) return set_error(ctx, ORE_ERR_INVALID, "null argument");
+  if (S == 0) return ORE_OK;
+  ORE_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (const ore_status st = nearest_grow_part(ctx, kmeans_scratch_bytes(L, int(D)))) return st;
+  launch_gallery_f16(centroids, L, D, ctx->nearest_part, ctx->stream);
+  launch_kmeans_assign(x->data, nstride_of(x), int(S), int(D), ctx->nearest_part, L, assign, scores, ctx->stream);
+  launch_kmeans_update(x->data, nstride_of(x), int(S), int(D), centroids, L, assign, centroids_out, counts, ctx->stream);
+  ORE_HIP_CHECK(ctx, hipGetLastError());
+  return ORE_OK;
+}
+
 // the three ore_nearest_segments entries: segments and the format's gallery rows per step
 static ore_status nearest_split(ore_ctx* ctx, NearestFmt fmt, int64_t n, int64_t G, int32_t* segments, int32_t* step_rows) {
   if (!ctx || !segments || !step_rows) return set_error(ctx, ORE_ERR_INVALID, "null argument");

@@ -4,7 +4,7 @@ all compute runs as HIP kernels in lib/libore.so (no CPU fallback)."""
 from ._lib import (CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD, FUSE_ALIAS, FUSE_ALL, FUSE_CONCAT, FUSE_CONCAT_POOL,  # noqa: F401
                    FUSE_CONV_POOL, FUSE_CONV_RELU, FUSE_EAGER, FUSE_FIRE, FUSE_FIRE_POOL, FUSE_FIRST_SQUEEZE,
                    FUSE_POOL_SQUEEZE, FUSE_CONV_GAP, FUSE_POOL_EXPAND, KEEP_VALUES, LIB_PATH, LOAD_F16, LOAD_NO_WINOGRAD, OreError,
-                   ABI_VERSION, IVF_CHUNK_ROWS, IVF_MAX_D, PRE_REVERSE_CHANNELS, FILTER_BILINEAR, FILTER_BILINEAR_AA, FILTER_BICUBIC, FILTER_BICUBIC_AA, CUBIC_AA_MAX_RATIO, AA_MAX_RATIO, AA_MAX_TAPS,
+                   ABI_VERSION, IVF_CHUNK_ROWS, IVF_MAX_D, KMEANS_MAX_D, KMEANS_MAX_L, PRE_REVERSE_CHANNELS, FILTER_BILINEAR, FILTER_BILINEAR_AA, FILTER_BICUBIC, FILTER_BICUBIC_AA, CUBIC_AA_MAX_RATIO, AA_MAX_RATIO, AA_MAX_TAPS,
                    YUV_BT601, YUV_BT709, YUV_BT601_FULL, IMAGE_INTERLEAVED, IMAGE_NV12, IMAGE_YUV, YUV_FORMATS, IMAGE_FLIP_H, MAX_VIEWS,
                    CAM_BOX_MAX_MAP, CAM_BOX_MAX_SIDE, EMBED_L2, load)
 from .engine import (Context, ImageList, Model, Nv12ImageList, YuvImageList, add, center_crop_geometry, class_maps, concatenation, conv_out_shape, convolution, drop_out,  # noqa: F401
@@ -13,6 +13,7 @@ from .engine import (Context, ImageList, Model, Nv12ImageList, YuvImageList, add
                      apply_orientation, orient_geometry, oriented_hw, rotation_orientation,
                      box_to_source, cam_box_reference, cam_boxes, upsample_maps, nearest, nearest_segments, gallery_f16,
                      nearest_segments_f16, gallery_i8, nearest_segments_i8, rerank, nearest_bins, nearest_bins_segments,
-                     gallery_mxfp4, mxfp4_decode, nearest_bins_segments_mxfp4, nearest_lists, ivf_chunks, ivf_build, IvfIndex)
+                     gallery_mxfp4, mxfp4_decode, nearest_bins_segments_mxfp4, nearest_lists, ivf_chunks, ivf_build, IvfIndex,
+                     kmeans_step, ivf_train)
 
 __version__ = "0.1.0"

@@ -32,6 +32,7 @@ FILTER_BILINEAR, FILTER_BILINEAR_AA = 0, 1  # ore_resize_filter (the _ex resize 
 FILTER_CUBIC_BIT, FILTER_BICUBIC, FILTER_BICUBIC_AA = 256, 256, 257  # ORE_FILTER_BICUBIC*: values of the filter word beside the enum
 IVF_CHUNK_ROWS = 256  # ORE_IVF_CHUNK_ROWS: gallery rows per chunk of nearest_lists()'s work table
 IVF_MAX_D = 512  # ORE_IVF_MAX_D
+KMEANS_MAX_D, KMEANS_MAX_L = 512, 65536  # ORE_KMEANS_MAX_D / ORE_KMEANS_MAX_L (ore_kmeans_step_f32)
 CUBIC_AA_MAX_RATIO = 16  # ORE_CUBIC_AA_MAX_RATIO: the antialiased cubic filter's shrink limit
 AA_MAX_RATIO, AA_MAX_TAPS = 32, 64  # ORE_AA_MAX_RATIO / ORE_AA_MAX_TAPS: the antialiased filter's shrink limit and taps per axis
 YUV_BT601, YUV_BT709, YUV_BT601_FULL = 0, 1, 2  # ore_yuv_matrix (ore_yuv_to_rgb, the NV12 image lists)
@@ -81,7 +82,7 @@ EXPORTED = [
     "ore_nearest_rerank_f32", "ore_nearest_rerank_f16",
     "ore_nearest_bins_f16", "ore_nearest_bins_i8", "ore_nearest_bins_segments",
     "ore_gallery_mxfp4", "ore_nearest_bins_mxfp4", "ore_nearest_bins_segments_mxfp4",
-    "ore_ivf_chunks", "ore_nearest_lists_f16",
+    "ore_ivf_chunks", "ore_nearest_lists_f16", "ore_kmeans_step_f32",
 ]
 
 
@@ -252,6 +253,7 @@ def load():
         "ore_nearest_rerank_f16": (i32, [vp, T, vp, i64, vp, i64, i32, i32, vp, vp]),
         "ore_ivf_chunks": (i32, [vp, i32, vp, vp]),
         "ore_nearest_lists_f16": (i32, [vp, T, vp, i64, vp, i32, vp, i32, i32, vp, i64, i32, i32, vp, vp]),
+        "ore_kmeans_step_f32": (i32, [vp, T, vp, i32, vp, vp, vp, vp]),
         "ore_nearest_bins_f16": (i32, [vp, T, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_bins_i8": (i32, [vp, T, vp, vp, i64, i32, i32, vp, vp]),
         "ore_nearest_bins_segments": (i32, [vp, i64, i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),

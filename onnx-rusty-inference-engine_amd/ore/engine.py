@@ -16,7 +16,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, OreError, PoolAttrs, Resize,
+from ._lib import (KMEANS_MAX_D, KMEANS_MAX_L, LOAD_F16, LOAD_NO_WINOGRAD, PRE_REVERSE_CHANNELS, ConvAttrs, OreError, PoolAttrs, Resize,
                    Tensor, check, load)
 
 __all__ = ["Context", "Model", "OreError", "convolution", "max_pool", "relu", "add", "softmax", "mul",
@@ -1070,6 +1070,76 @@ def ivf_build(ctx: Context, gallery, centroids, slab: int = 1 << 16) -> IvfIndex
     packed = gallery_f16(ctx, gallery[ids.long()].contiguous())
     max_rows = int((offsets[1:] - offsets[:-1]).max())
     return IvfIndex(ctx, packed, offsets.to(gallery.device), ivf_chunks(offsets).to(gallery.device), max_rows, centroids, ids)
+
+
+def kmeans_step(ctx: Context, x, centroids, out=None):
+    """ore_kmeans_step_f32 (extension): one Lloyd iteration of spherical k-means.  x is float32 [S, D] as q of nearest()
+    (a row slice is fine), centroids a contiguous float32 [L, D], 1 <= D <= KMEANS_MAX_D, 1 <= L <= KMEANS_MAX_L.
+    Returns (new_centroids float32 [L, D], assign int32 [S], scores float32 [S], counts int32 [L]): assign and scores
+    are nearest(x, gallery_f16(centroids), 1) to the bit; a new centroid is the float64 sum of its rows divided by that
+    sum's norm, and one with no row or a zero sum keeps its bits.  No atomics: the result depends on the inputs alone.
+    With out= the new centroids are written there; out may be `centroids` itself."""
+    torch = _torch()
+    given = (("x", x), ("centroids", centroids)) + ((("out", out),) if out is not None else ())
+    for name, t in given:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2:
+            raise OreError(1, f"{name}: expected a 2-D float32 CUDA tensor")
+    S, D, L = int(x.shape[0]), int(x.shape[1]), int(centroids.shape[0])
+    if int(centroids.shape[1]) != D or not centroids.is_contiguous():
+        raise OreError(1, f"centroids: expected a contiguous [L, {D}] tensor, got {tuple(centroids.shape)}")
+    for name, t in given:
+        if not t.is_cuda:
+            raise OreError(1, f"{name}: expected a 2-D float32 CUDA tensor")
+        if t.device.index != ctx.device:
+            raise OreError(1, f"{name}: on cuda:{t.device.index}, the context is on cuda:{ctx.device}")
+    if not 1 <= D <= KMEANS_MAX_D or not 1 <= L <= KMEANS_MAX_L:
+        raise OreError(1, f"D = {D}, L = {L} outside 1..{KMEANS_MAX_D}, 1..{KMEANS_MAX_L}")
+    if S > 1 and (x.stride(1) != 1 or x.stride(0) < D) or S <= 1 and not x.is_contiguous():
+        raise OreError(1, "x: expected dense rows at a row stride of at least D")
+    if out is None:
+        out = torch.empty_like(centroids)
+    elif out.shape != centroids.shape or not out.is_contiguous():
+        raise OreError(1, f"out: expected a contiguous {tuple(centroids.shape)} tensor, got {tuple(out.shape)}")
+    assign = torch.empty((S,), dtype=torch.int32, device=x.device)
+    scores = torch.empty((S,), dtype=torch.float32, device=x.device)
+    counts = torch.empty((L,), dtype=torch.int32, device=x.device)
+    if S == 0:  # nothing is launched: every list is empty and keeps its centroid
+        if out.data_ptr() != centroids.data_ptr():
+            out.copy_(centroids)
+        return out, assign, scores, counts.zero_()
+    d = Tensor()
+    d.data, d.ndim, d.nstride = x.data_ptr(), 2, (int(x.stride(0)) if S > 1 else 0)
+    d.dims[0], d.dims[1] = S, D
+    check(load().ore_kmeans_step_f32(ctx.h, ctypes.byref(d), ctypes.c_void_p(centroids.data_ptr()), L, ctypes.c_void_p(out.data_ptr()),
+                                     ctypes.c_void_p(assign.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
+                                     ctypes.c_void_p(counts.data_ptr())), ctx.h)
+    return out, assign, scores, counts
+
+
+def ivf_train(ctx: Context, sample, L: int, iters: int = 10, seed: int = 0, init=None):
+    """The centroids float32 [L, D] of an inverted file (ivf_build()) from `iters` kmeans_step()s over sample float32
+    [S, D].  They start as `init` float32 [L, D], used as given, or as L distinct sample rows drawn with a torch.Generator
+    seeded with `seed` and L2-normalised (a zero row stays zero).  After every step each empty list is seeded again with
+    the normalised sample row whose score is lowest at that step: distinct rows, in ascending score and then ascending
+    row, to the empty lists in ascending order.  Not a hot path: this bookkeeping is torch."""
+    torch = _torch()
+    L = int(L)
+    if init is not None:
+        if not isinstance(init, torch.Tensor) or init.dim() != 2 or int(init.shape[0]) != L:
+            raise OreError(1, f"init: expected a float32 [{L}, D] CUDA tensor")
+        cent = init.contiguous().clone()
+    else:
+        if not isinstance(sample, torch.Tensor) or sample.dim() != 2 or not 1 <= L <= int(sample.shape[0]):
+            raise OreError(1, f"L = {L} outside 1..S, the rows of the 2-D sample")
+        rows = torch.randperm(int(sample.shape[0]), generator=torch.Generator().manual_seed(int(seed)))[:L]
+        cent = torch.nn.functional.normalize(sample[rows.to(sample.device)]).contiguous()
+    for _ in range(int(iters)):
+        _, _, scores, counts = kmeans_step(ctx, sample, cent, out=cent)
+        empty = torch.nonzero(counts == 0)[:, 0][:int(sample.shape[0])]
+        if empty.numel():
+            rows = torch.sort(scores, stable=True)[1][:empty.numel()]
+            cent[empty] = torch.nn.functional.normalize(sample[rows])
+    return cent
 
 
 def _nearest_operands(ctx, q, gallery, scales):
